@@ -1,17 +1,21 @@
 #!/usr/bin/env python
 """Benchmark of the PlankAssembly hot path on MI355X (contract: see the task description).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full training step (forward + backward + gradient all-reduce + Adam) of the
 reference's headline configuration -- train_complete.yaml model (d_model 512, 8 heads, dff 1024, 6+6
 post-norm layers, dropout 0.2) at seq = 1024 (MAX_INPUT_LENGTH 1025), decoder length 128, batch 16 per
 GPU, bf16 compute / f32 master weights -- on synthetic tokenised-drawing batches that are resident in
-HBM before the timed region.  Rank 0 prints ONE JSON line: `value` = train samples/s over all GPUs;
-the greedy-decode throughput (batch 256, max_len 1024, hipGraph-replayed step), the attention/GEMM
-roofline fractions (HIP-event timed) and the CPU baseline (the oracle on the host cores) ride in
-the same line.
+HBM before the timed region.  Rank 0 prints ONE JSON line: `value` = train samples/s over all GPUs.
+
+A plain run sets up, warms up, times K steps, writes the last step's outputs (--dump-outputs) and
+prints the line.  With --full the other legs run behind the headline figure and ride in the same line:
+a longer steady-state region, prepared / host-resident batches, the exact-f32 and bf16x3 parity paths,
+the per-kernel census, the padded encoder, the greedy-decode throughput (batch 256, max_len 1024,
+hipGraph-replayed step), the attention/GEMM roofline fractions (HIP-event timed) and the CPU baseline
+(the oracle on the host cores).
 """
 from __future__ import annotations
 
@@ -468,6 +472,27 @@ def cpu_baseline(cfgd, sample_b=2, budget_s=20.0, fit_style=False):
                        f"step(s) after {warm} warm-up, {dt:.1f}s")
 
 
+DUMP_SAMPLE = 1 << 22          # entries of the parameter / gradient buffers written by --dump-outputs (16 MB each in f32)
+
+
+def dump_outputs(path, model, out):
+    """--dump-outputs: what the timed step handed its caller in the last timed step - loss and accuracy, the flat f32
+    gradient buffer the backward filled and the flat f32 parameter buffer Adam left - as float32 .npy files.  The two
+    buffers are sampled at the same fixed, seeded set of DUMP_SAMPLE positions (sorted), so two builds compare entry
+    for entry."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    flat, grads = model.flat_params.detach(), model.flat_grads.detach()
+    n = flat.numel()
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(2022))[:min(n, DUMP_SAMPLE)].sort().values
+    arrays = {"loss": out["loss"].detach().float().reshape(1), "accuracy": out["accuracy"].detach().float().reshape(1),
+              "params_sample": flat[idx.to(flat.device)].float(), "grads_sample": grads[idx.to(grads.device)].float()}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    log(f"outputs of the last timed step written to {path}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in arrays.items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -480,8 +505,21 @@ def main():
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--no-f32", action="store_true", help="skip the exact-f32 training leg (probes only)")
     ap.add_argument("--batch", type=int, default=0)
-    ap.add_argument("--long-steps", type=int, default=200, help="length of the extra steady-state region (noise estimate)")
+    ap.add_argument("--long-steps", type=int, default=200, help="length of the extra steady-state region (noise estimate, --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32); the run uses the library's ordered "
+                         "gradient reductions (PA_DETERMINISTIC=1), so that the same arguments give the same outputs on every run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure (steady state, parity paths, census, decode, rooflines, "
+                         "CPU baseline; the --no-* switches thin these out)")
     args = ap.parse_args()
+    if args.dump_outputs:
+        # Dumped outputs are compared run for run and build for build.  bf16 combines its bias, LayerNorm and embedding-table
+        # gradient sums across blocks with f32 atomics, whose order differs from run to run, and Adam carries those last-bit
+        # differences into every parameter over the timed steps.  The ordered reductions (one contributor per element, fixed
+        # order; the f32 path's default, pa_device.h) make the gradients and parameters identical from run to run.  Set before
+        # the library's first reduction reads it.
+        os.environ.setdefault("PA_DETERMINISTIC", "1")
     cfgd = CONFIGS[args.config]
     headline = args.config == "headline"
 
@@ -527,7 +565,8 @@ def main():
         # preparation launches run on the main stream (DevicePrefetcher; tools/prep_probe.py: +0.04 instead of +0.10 ms per step)
         b["_n_valid"] = int((~b["input_mask"]).sum())
         raw.append(b)
-    prepared = [model.prepare_batch(b) for b in raw]        # the same batches, prepared ahead (for `resident_prepared`)
+    # the same batches, prepared ahead: for the --full legs (`resident_prepared`, census, padded encoder) and the RCCL set-up steps
+    prepared = [model.prepare_batch(b) for b in raw] if args.full or (dist.is_initialized() and backend == "nccl") else None
 
     def step_on(batch):
         opt.zero_grad()
@@ -591,23 +630,27 @@ def main():
     assert math.isfinite(loss), "training diverged"
     samples_s = args.steps * B * world / dt
     log(f"train: {samples_s:.1f} samples/s, {dt / args.steps * 1e3:.2f} ms/step, loss {loss:.4f} (fresh batch every step)")
-    # A longer region of the same loop (--long-steps, default 200 steps ~ 1 s): `value` is bound to exactly --steps steps by the driver's contract
-    # (20 steps = 0.1 s there), so the run-to-run noise of `value` is read off this figure.
-    long_steps = max(args.long_steps, args.steps)
-    dt_long, _ = timed(raw, fresh=True, steps=long_steps, warmup=0)
-    steady = dict(value=long_steps * B * world / dt_long, unit="samples/s", steps=long_steps, ms_per_step=dt_long / long_steps * 1e3,
-                  note="the same fresh-batch loop over a longer timed region (barrier + synchronize on both sides, max over ranks)")
-    log(f"       {steady['value']:.1f} samples/s, {steady['ms_per_step']:.3f} ms/step over {long_steps} steps")
-    dt_res, _ = timed(prepared, fresh=False)               # round-1 figure: four prepared batches cycled
-    resident = dict(value=args.steps * B * world / dt_res, unit="samples/s", ms_per_step=dt_res / args.steps * 1e3,
-                    note="the same batches prepared before the timed region and cycled (what round 1 reported)")
-    log(f"       {resident['value']:.1f} samples/s, {resident['ms_per_step']:.2f} ms/step with prepared batches")
-    host_pool = [{k: (v.cpu().pin_memory() if torch.is_tensor(v) else v) for k, v in b.items() if k != "_n_valid"} for b in raw]   # (CPU mask: the prefetcher counts it itself)
-    dt_h, _ = timed(host_pool, fresh=True)
-    fresh_host = dict(value=args.steps * B * world / dt_h, unit="samples/s", ms_per_step=dt_h / args.steps * 1e3,
-                      note="batches start in pinned host memory: PCIe copy + preparation + step (never `value`)")
-    log(f"       {fresh_host['value']:.1f} samples/s, {fresh_host['ms_per_step']:.2f} ms/step from host batches")
-    del host_pool
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, out)
+    steady = resident = fresh_host = None
+    if args.full:
+        # A longer region of the same loop (--long-steps, default 200 steps ~ 1 s): `value` is bound to exactly --steps steps by the driver's contract
+        # (20 steps = 0.1 s there), so the run-to-run noise of `value` is read off this figure.
+        long_steps = max(args.long_steps, args.steps)
+        dt_long, _ = timed(raw, fresh=True, steps=long_steps, warmup=0)
+        steady = dict(value=long_steps * B * world / dt_long, unit="samples/s", steps=long_steps, ms_per_step=dt_long / long_steps * 1e3,
+                      note="the same fresh-batch loop over a longer timed region (barrier + synchronize on both sides, max over ranks)")
+        log(f"       {steady['value']:.1f} samples/s, {steady['ms_per_step']:.3f} ms/step over {long_steps} steps")
+        dt_res, _ = timed(prepared, fresh=False)               # round-1 figure: four prepared batches cycled
+        resident = dict(value=args.steps * B * world / dt_res, unit="samples/s", ms_per_step=dt_res / args.steps * 1e3,
+                        note="the same batches prepared before the timed region and cycled (what round 1 reported)")
+        log(f"       {resident['value']:.1f} samples/s, {resident['ms_per_step']:.2f} ms/step with prepared batches")
+        host_pool = [{k: (v.cpu().pin_memory() if torch.is_tensor(v) else v) for k, v in b.items() if k != "_n_valid"} for b in raw]   # (CPU mask: the prefetcher counts it itself)
+        dt_h, _ = timed(host_pool, fresh=True)
+        fresh_host = dict(value=args.steps * B * world / dt_h, unit="samples/s", ms_per_step=dt_h / args.steps * 1e3,
+                          note="batches start in pinned host memory: PCIe copy + preparation + step (never `value`)")
+        log(f"       {fresh_host['value']:.1f} samples/s, {fresh_host['ms_per_step']:.2f} ms/step from host batches")
+        del host_pool
 
     def train_step(i):
         return step_on(prepared[i % len(prepared)])
@@ -654,7 +697,7 @@ def main():
         torch.cuda.empty_cache()
         return res
 
-    if args.dtype == "bf16" and not args.no_f32:
+    if args.full and args.dtype == "bf16" and not args.no_f32:
         train_f32 = parity_leg("f32")
         train_x3 = parity_leg("x3")
 
@@ -667,7 +710,7 @@ def main():
         sync = None
 
     census = None
-    if rank == 0 and not args.no_kernels:
+    if args.full and rank == 0 and not args.no_kernels:
         # every batch of the pool (the batches the timed region cycled through): which GEMM kernel an encoder Linear goes to
         # depends on the batch's number of valid rows, so one batch cannot stand for the step
         parts = []
@@ -679,21 +722,23 @@ def main():
         census = merge_census(parts)
         log("kernel census: " + ", ".join(f"{k}: {v['launches']:.1f} launches, {v['seconds'] / v['launches'] * 1e6:.1f} us avg, "
                                            f"{v['flops'] / v['seconds'] / 1e12:.0f} TF" for k, v in census.items()))
-    fw = fwd_flops_per_sample(S_in, T_out, cfgd["d"], cfgd["ff"], cfgd["ne"], cfgd["nd"])
-    train_flops = 3.0 * fw * B                                 # per GPU step, counted at the padded length (dense-equivalent)
-    step_tflops = train_flops * args.steps / dt / 1e12
-    valid_rows = sum(bt["_pack"][2] for bt in prepared) / len(prepared) if model.unpad else B * S_in
-    # executed FLOPs: the encoder runs on the packed rows, its attention on the true lengths
-    exec_flops = 0.0
-    for bt in prepared:
-        cu = bt["_pack"][0]
-        lens = (cu[1:B + 1] - cu[:B]).tolist()
-        exec_flops += 3.0 * sum(fwd_flops_per_sample(l, T_out, cfgd["d"], cfgd["ff"], cfgd["ne"], cfgd["nd"]) for l in lens)
-    exec_tflops = exec_flops / len(prepared) * args.steps / dt / 1e12
+    step_tflops = exec_tflops = valid_rows = None
+    if args.full:
+        fw = fwd_flops_per_sample(S_in, T_out, cfgd["d"], cfgd["ff"], cfgd["ne"], cfgd["nd"])
+        train_flops = 3.0 * fw * B                                 # per GPU step, counted at the padded length (dense-equivalent)
+        step_tflops = train_flops * args.steps / dt / 1e12
+        valid_rows = sum(bt["_pack"][2] for bt in prepared) / len(prepared) if model.unpad else B * S_in
+        # executed FLOPs: the encoder runs on the packed rows, its attention on the true lengths
+        exec_flops = 0.0
+        for bt in prepared:
+            cu = bt["_pack"][0]
+            lens = (cu[1:B + 1] - cu[:B]).tolist()
+            exec_flops += 3.0 * sum(fwd_flops_per_sample(l, T_out, cfgd["d"], cfgd["ff"], cfgd["ne"], cfgd["nd"]) for l in lens)
+        exec_tflops = exec_flops / len(prepared) * args.steps / dt / 1e12
 
     # secondary: the same step with the encoder left padded (what the reference computes row for row), rank 0, N=1 only
     dense = None
-    if rank == 0 and world == 1 and not args.no_kernels and model.unpad and headline:
+    if args.full and rank == 0 and world == 1 and not args.no_kernels and model.unpad and headline:
         model.unpad = False
         dbatches = [{k: v for k, v in bt.items() if not k.startswith("_")} for bt in prepared]
         for i in range(3):
@@ -711,7 +756,7 @@ def main():
 
     # ------------------------------------------------------------------ greedy decode
     decode, dec_keep = None, None
-    if not args.no_decode and headline:
+    if args.full and not args.no_decode and headline:
         from plankassembly_amd.decode import GreedyDecoder
         sync = None
         model.register_grad_ready_hook(None)
@@ -810,11 +855,11 @@ def main():
                 decode[ddtype]["roofline_cross_attention"] = decode_cross_roofline(ddtype)
 
     kern = None
-    if rank == 0 and not args.no_kernels and headline:
+    if args.full and rank == 0 and not args.no_kernels and headline:
         kern = kernel_rooflines(B)
         log("kernel rooflines: " + ", ".join(f"{k} {v['tflops']:.0f} TF" for k, v in kern.items()))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(cfgd, fit_style=(args.config == "tiny"))
         log(f"cpu baseline: {cpu['value']:.3f} samples/s on {cpu['cores']} threads")
         if dec_keep is not None and dec_keep["got"]:
@@ -844,11 +889,13 @@ def main():
             parity = None
         prec = (" [value: bf16 MFMA, f32 accumulate / master weights; train.f32 / train.x3: the same step in exact f32 / f32 with bf16x3 products = the parity paths]"
                 if args.dtype == "bf16" else " [exact-f32 MFMA: the parity path]")
+        mfma_frac = (lambda tf: None if tf is None else tf / PEAK_BF16_TFLOPS)
         line = {
             "metric": ("train samples/sec (fwd+bwd+all-reduce+Adam), d_model=512 seq=1024" if headline else
                        f"train samples/sec (fwd+bwd+all-reduce+Adam), config {args.config}") + prec,
             "value": samples_s, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            **({"ordered_reductions": True} if os.environ.get("PA_DETERMINISTIC") == "1" else {}),
             "dtype": args.dtype, "data": "synthetic tokenised-drawing batches (SURVEY 8d), random-init weights; collated "
                                         "batches resident in HBM (+ the collate function's host-side count of valid rows), a fresh one "
                                         "every step (row packing + embedding-row grouping kernels inside the timed region)",
@@ -868,10 +915,15 @@ def main():
                              "note": "padded encoder rows are packed away before the first layer (results identical: "
                                      "they never reach the loss); `dense_padded` is the same step without packing"},
             "dense_padded": dense,
-            "train_dense_equiv_tflops_per_gpu": step_tflops, "train_dense_equiv_mfma_frac": step_tflops / PEAK_BF16_TFLOPS,
-            "train_executed_tflops_per_gpu": exec_tflops, "train_executed_mfma_frac": exec_tflops / PEAK_BF16_TFLOPS,
+            "train_dense_equiv_tflops_per_gpu": step_tflops, "train_dense_equiv_mfma_frac": mfma_frac(step_tflops),
+            "train_executed_tflops_per_gpu": exec_tflops, "train_executed_mfma_frac": mfma_frac(exec_tflops),
             "decode": decode,
         }
+        if not args.full:
+            # a plain run measures the headline figure only: the fields of the other legs come with --full
+            for k in ("steady_state", "resident_prepared", "fresh_host", "encoder_rows", "dense_padded", "train_dense_equiv_tflops_per_gpu",
+                      "train_dense_equiv_mfma_frac", "train_executed_tflops_per_gpu", "train_executed_mfma_frac", "decode"):
+                del line[k]
         if census:
             # dominant kernel family of the step by time, over the GEMM families AND the attention launches
             key = max(census, key=lambda k: census[k]["seconds"])

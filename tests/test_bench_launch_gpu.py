@@ -29,7 +29,7 @@ def _launch(n, extra_env, steps=4, warmup=2, flags=("--no-cpu", "--no-decode", "
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup),
-           *flags]
+           "--full", *flags]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -82,3 +82,43 @@ def test_driver_launch_line_two_ranks_over_rccl():
     _check_line(line, 2, 4, 2)
     assert line["rccl_ranks"]["world_size"] == 2 and line["rccl_ranks"]["backend"] == "nccl" and line["rccl_ranks"]["process_group"]
     assert line["rccl_ranks"]["ms_per_step_by_rank"]["train"]["ranks"] == 2
+
+
+def _plain_run(out_dir):
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(out_dir)]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env.pop("PA_DETERMINISTIC", None)
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_plain_run_reports_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline fields, none of the other legs, and with
+    --dump-outputs the last timed step's outputs as float32 .npy files (64 MB at most) - the same on every run: a second run
+    with the same arguments dumps bit-identical parameters, gradients and accuracy (the loss, summed across blocks with f32
+    atomics, to its last bits)."""
+    import numpy as np
+    out_dir = tmp_path / "outputs"
+    line = _plain_run(out_dir)
+    _check_line(line, 1, 3, 2)
+    assert line["dtype"] == "bf16" and line["metric"].startswith("train samples/sec") and line["ordered_reductions"] is True
+    for k in ("steady_state", "resident_prepared", "fresh_host", "decode", "roofline", "kernel_census", "kernels", "cpu_baseline"):
+        assert k not in line, k
+    assert set(line["train"]) == {"bf16", "parity_meeting"}
+    files = sorted(os.listdir(out_dir))
+    assert files == ["accuracy.npy", "grads_sample.npy", "loss.npy", "params_sample.npy"], files
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 << 20
+    arrays = {f[:-4]: np.load(out_dir / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["loss"][0] == np.float32(line["final_loss"])
+    assert arrays["params_sample"].shape == arrays["grads_sample"].shape and arrays["params_sample"].size > 1 << 20
+    assert np.abs(arrays["grads_sample"]).max() > 0
+    again_dir = tmp_path / "again"
+    _plain_run(again_dir)
+    again = {f[:-4]: np.load(again_dir / f) for f in files}
+    for k in ("params_sample", "grads_sample", "accuracy"):
+        assert np.array_equal(arrays[k], again[k]), k
+    assert abs(float(arrays["loss"][0]) - float(again["loss"][0])) <= 1e-6 * abs(float(arrays["loss"][0]))

@@ -1,4 +1,5 @@
 """CPU checks of the trainer surface: reference-style YAML parsing, CfgNode, hook names, checkpoint shape."""
+import json
 import os
 
 import torch
@@ -85,17 +86,19 @@ def test_reference_shaped_yaml_with_lightning_callbacks_block_parses(tmp_path):
     assert hp["LR"] == 1e-4 and isinstance(hp["LR"], float) and "COMPUTE_DTYPE" not in hp["MODEL"]
     cfg = CfgNode(hp)
     assert cfg.MODEL.NORMALIZE_BEFORE is True and cfg.TOKEN.PAD == 513 and cfg.DATA.MAX_INPUT_LENGTH == 1200
-    # the reference's own files, where this container has them (never on the GPU box; this is a CPU test)
-    ref_dir = "/root/reference/configs"
-    if os.path.isdir(ref_dir):
-        for name in ("train_complete", "train_visible", "train_sideface"):
-            seed, tkw, hp = load_cli_config(os.path.join(ref_dir, name + ".yaml"))
-            ours = load_cli_config(os.path.join(REPO, "configs", name + ".yaml"))[2]
-            assert seed == 2022 and "callbacks" in tkw and isinstance(hp["LR"], float)
-            theirs = {k: v for k, v in hp.items()}
-            mine = {k: (dict(v) if isinstance(v, dict) else v) for k, v in ours.items()}
-            mine["MODEL"].pop("COMPUTE_DTYPE", None)
-            assert mine == theirs, name               # the shipped hparams tree IS the reference's, plus COMPUTE_DTYPE
+    # the reference's own files, as load_cli_config parses them (seed, trainer keys, hparams tree), stored in
+    # tests/golden/reference_configs.json
+    with open(os.path.join(REPO, "tests", "golden", "reference_configs.json")) as f:
+        golden = json.load(f)
+    for name in ("train_complete", "train_visible", "train_sideface"):
+        ref = golden[name]
+        seed, hp = ref["seed"], ref["hparams"]
+        ours = load_cli_config(os.path.join(REPO, "configs", name + ".yaml"))[2]
+        assert seed == 2022 and "callbacks" in ref["trainer_keys"] and isinstance(hp["LR"], float)
+        theirs = {k: v for k, v in hp.items()}
+        mine = {k: (dict(v) if isinstance(v, dict) else v) for k, v in ours.items()}
+        mine["MODEL"].pop("COMPUTE_DTYPE", None)
+        assert mine == theirs, name               # the shipped hparams tree IS the reference's, plus COMPUTE_DTYPE
 
 
 def test_trainer_has_the_lightning_hook_surface():

@@ -2,7 +2,7 @@
 # batch 8 side by side on the one GPU against one process at batch 8 and one at batch 16 (the headline).  Aggregate samples/s
 # of the pair above the batch-16 figure = launch gaps / tails / low-occupancy phases are fillable by a concurrent stream.
 TAG=${1:-r04conc}; OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT
-F="--no-cpu --no-decode --no-kernels --no-f32 --dtype bf16 --steps 300 --warmup 20 --long-steps 300"
+F="--full --no-cpu --no-decode --no-kernels --no-f32 --dtype bf16 --steps 300 --warmup 20 --long-steps 300"
 python bench.py $F --batch 8 > $OUT/solo8.json 2> $OUT/solo8.err
 python bench.py $F --batch 8 > $OUT/pairA.json 2> $OUT/pairA.err &
 PA=$!

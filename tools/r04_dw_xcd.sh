@@ -3,7 +3,7 @@ TAG=${1:-r04dx}; OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT
 timeout 600 python -m pytest tests/test_kernels_gpu.py -q -x -k "group" > $OUT/pytest.txt 2>&1; tail -3 $OUT/pytest.txt
 echo "# bench.py --steps 100 --warmup 10 --no-decode --no-cpu --no-kernels: bf16 ms/step by grouped-dW unit order" > $OUT/dw_xcd.txt
 for rep in 1 2; do for x in 0 1; do
-  PA_DW_XCD=$x timeout 300 python bench.py --steps 100 --warmup 10 --no-decode --no-cpu --no-kernels --long-steps 100 > $OUT/b.json 2> $OUT/b.err
+  PA_DW_XCD=$x timeout 300 python bench.py --full --steps 100 --warmup 10 --no-decode --no-cpu --no-kernels --long-steps 100 > $OUT/b.json 2> $OUT/b.err
   python - $x $OUT/b.json >> $OUT/dw_xcd.txt <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][0])

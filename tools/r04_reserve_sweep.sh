@@ -8,7 +8,7 @@ echo "# bench.py --steps 100 --warmup 10 --no-decode --no-cpu --no-kernels under
 for fake in "" "32:200:8" "32:100:8" "64:200:8"; do
   for res in 0 16 32; do
     if [ -z "$fake" ] && [ "$res" != "0" ]; then continue; fi
-    MASTER_PORT=$((29600 + RANDOM % 200)) PLANK_FAKE_COLLECTIVE=$fake PA_RESERVE_CUS=$res timeout 300 python bench.py --steps 100 --warmup 10 --no-decode --no-cpu --no-kernels --long-steps 100 > $OUT/b.json 2> $OUT/b.err
+    MASTER_PORT=$((29600 + RANDOM % 200)) PLANK_FAKE_COLLECTIVE=$fake PA_RESERVE_CUS=$res timeout 300 python bench.py --full --steps 100 --warmup 10 --no-decode --no-cpu --no-kernels --long-steps 100 > $OUT/b.json 2> $OUT/b.err
     python - "$fake" "$res" $OUT/b.json >> $OUT/sweep.txt <<'PY'
 import json, sys
 fake, res, path = sys.argv[1:4]
