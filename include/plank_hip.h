@@ -603,6 +603,29 @@ int pa_decode_step(pa_model* m, void* stream);
  * Experimental: on MI355X / ROCm 7.2 the cross-queue event edges cost more than the overlap. */
 int pa_decode_step_pair(pa_model* a, pa_model* b, void* stream_a, void* stream_b);
 int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void** first_end, void** t_dev);
+/* Beam search over the same step.  K beams per drawing, 1 <= K <= PA_BEAM_MAX: the caller runs the encoder and
+ * pa_decode_begin on the batch with every drawing repeated K times (row b*K + k is beam k of drawing b), then switches the decode to
+ * beam mode.  pa_decode_step then ends each step with the beam selection instead of the greedy arg-max:
+ *   - per row, the K most probable candidates of the greedy step's own distribution (vocab entries and pointers j < t, first-max order,
+ *     p = 0 never taken); a finished row has the one candidate (PAD, attach -1, log p 0);
+ *   - per drawing, the K best of the K*K candidates by score + logf(p) (f32; ties to the smaller parent beam, then the better rank)
+ *     become the new beams; a beam that emits END is finished and frozen;
+ *   - rows whose parent is another row take the parent's history (self-attention caches, hidden-state cache, tokens, attach).
+ * Everything is read from device memory: the step still captures into one hipGraph.  K = 1 gives the greedy tokens, with PAD / -1
+ * after a row's first END.  pa_decode_step_pair returns PA_EINVAL for a decode in beam mode (beams run as one lane); the next
+ * pa_decode_begin returns the handle to greedy mode.
+ *   pa_decode_beam_ws_bytes: bytes of the beam workspace for `rows` = B*K rows (the batch pa_decode_begin was given), memory length S
+ *     and Tmax (the same values as pa_decode_ws_bytes); PA_EINVAL for K outside [1, PA_BEAM_MAX] or rows not a multiple of K.
+ *   pa_decode_beam_begin: after pa_decode_begin, lays out `ws` (256-byte aligned, pa_decode_beam_ws_bytes bytes) and resets the beam
+ *     state on `stream`: score 0 for beam 0 of every drawing and -inf for the others, nothing finished, every row its own parent.
+ *     PA_EINVAL for a decode that was not begun, a bad K, rows % K != 0 or a workspace too small.
+ *   pa_decode_beam_buffers: device pointers of scores f32 [rows] (cumulative log-probability), parents int32 [rows] (the row each beam
+ *     came from in the last step) and finished int32 [rows] (1 = has emitted END).  Tokens / attach / first_end of every beam are the
+ *     pa_decode_buffers arrays. */
+#define PA_BEAM_MAX 16
+int64_t pa_decode_beam_ws_bytes(pa_model* m, int32_t rows, int32_t S, int32_t Tmax, int32_t K);
+int pa_decode_beam_begin(pa_model* m, int32_t K, void* ws, int64_t ws_bytes, void* stream);
+int pa_decode_beam_buffers(pa_model* m, void** scores, void** parents, void** finished);
 /* Cross-attention of one decode step in absorbed ("multi-query") form (reference plankassembly/models.py:284-307, the
  * cross-attention of nn.TransformerDecoderLayer with K = W_k memory + b_k, V = W_v memory + b_v): per batch element and head
  * ctx[b][h][:] = sum_s softmax_s(qt[b][h] . mem[s]) mem[s] over the element's memory rows, where the caller has put

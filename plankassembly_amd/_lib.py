@@ -185,6 +185,9 @@ def lib():
             "pa_decode_step": (I, [P, P]),
             "pa_decode_step_pair": (I, [P, P, P, P]),
             "pa_decode_buffers": (I, [P, P, P, P, P]),
+            "pa_decode_beam_ws_bytes": (I64, [P, I, I, I, I]),
+            "pa_decode_beam_begin": (I, [P, I, P, I64, P]),
+            "pa_decode_beam_buffers": (I, [P, P, P, P]),
             "pa_dec_cross_mq": (I, [P, P, P, P, P, I, I, I, I, P]),
             "pa_dec_cross_mq32": (I, [P, P, P, P, P, I, I, I, I, P]),
             "pa_dec_cross_mq_ws": (I, [P, P, P, P, P, I, I, I, I, P, I64, P]),

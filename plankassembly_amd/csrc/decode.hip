@@ -15,6 +15,19 @@
 #include "pa_device.h"
 #include "model.h"
 
+struct BeamSeg {
+    char* ptr;
+    int64_t row_stride, outer_stride, scr_off, scr_outer;
+    int32_t outer, unit, by_pos, pos_add, vec16, pad_;
+};
+constexpr int BEAM_MAX_SEG = 40;
+struct BeamCopy {
+    char* scratch;
+    int64_t scr_row;
+    int32_t nseg, pad_;
+    BeamSeg seg[BEAM_MAX_SEG];
+};
+
 struct DecodeLayout {
     int B = 0, S = 0, Tmax = 0;
     std::vector<void*> cross_k, cross_v, self_k, self_v;   // per decoder layer, per-head contiguous: [B][H][S|Tmax][dh]
@@ -52,6 +65,11 @@ struct DecodeLayout {
     bool mq_self_bf = false;
     std::vector<void*> wo_ts; std::vector<float*> bo_ts;
     void* mq_sp = nullptr; int64_t mq_sp_bytes = 0;   // range blocks of the absorbed cross-attention (decode_mq.h): tickets (zero between launches) + partials
+    // beam search (pa_decode_beam_begin; 0 = greedy): K beams per drawing over the B rows, state in the caller's beam workspace
+    int beamK = 0;
+    float *bm_score = nullptr, *bm_clp = nullptr;
+    int32_t *bm_fin = nullptr, *bm_parent = nullptr, *bm_ctok = nullptr, *bm_catt = nullptr;
+    BeamCopy bm_copy{};                        // segment table of the history reorder (passed to the copy kernel by value)
 };
 
 namespace {
@@ -258,6 +276,108 @@ __device__ __forceinline__ bool ptr_allowed(int i, int j) {      // reference mo
 
 constexpr int MAX_T = 2048;
 
+// The distribution of row b at step t (reference models.py:168-186, eval branch), shared by the greedy kernel and the beam
+// candidate kernel so that the two cannot drift apart.  row_dist_prepare computes the softmax statistics (vocabulary, and for
+// sz = t + 1 >= 6 the pointer logits over the hidden prefix into `plog` plus the switch gate); row_dist_visit then hands every
+// candidate of this thread to f(p, index) - vocab entries k < V as index k, pointers j < jend as index V + j - with the same f32
+// arithmetic each time it is called, so a caller may walk the candidates more than once.  Every thread of the block must call both.
+struct RowDist { float vmax, vsum, pmax, psum, prob; };
+template <typename T>
+__device__ __forceinline__ RowDist row_dist_prepare(const float* vr, int V, const T* pfeat, const T* hb, const T* cache, int64_t nb,
+                                                    int t, int d, const float* sw_w, const float* sw_b, float* plog, float* sh, float* s_sw) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sz = t + 1;
+    RowDist r{-INFINITY, 0.f, -INFINITY, 0.f, 0.f};
+    // vocab softmax statistics
+    float vmax = -INFINITY;
+    for (int k = tid; k < V; k += 256) vmax = fmaxf(vmax, vr[k]);
+    vmax = block_max(vmax, sh);
+    float vsum = 0.f;
+    for (int k = tid; k < V; k += 256) vsum += expf(vr[k] - vmax);
+    vsum = block_sum(vsum, sh);
+    r.vmax = vmax; r.vsum = vsum;
+    if (sz < 6) return r;                                             // models.py:172-173: un-gated vocab softmax
+    // pointer logits over the hidden prefix (row j = t is written by the caller but masked: j >= i)
+    // each wave takes 8 cached rows at a time, all their loads issued (unconditionally: rows clamped, tail discarded)
+    // before the first reduction; the pointer-feature row stays in registers.  Per row the arithmetic order is the
+    // one-row-at-a-time order (chunk by chunk per lane, then the wave sum): logits and greedy tokens are unchanged.
+    const T* pf = pfeat;
+    auto ptr_logits = [&](auto NCH_) {
+        constexpr int NCH = decltype(NCH_)::value, PUN = 8;           // NCH = d / 256 chunks of 4 columns per lane
+        f32x4 pa[NCH];
+#pragma unroll
+        for (int q = 0; q < NCH; ++q) pa[q] = ld4<T>(pf + (lane << 2) + q * 256);
+        for (int j0 = wave * PUN; j0 < t; j0 += 4 * PUN) {
+            f32x4 hh[PUN][NCH];
+#pragma unroll
+            for (int u = 0; u < PUN; ++u) {
+                const T* row = cache + (int64_t)min(j0 + u, t - 1) * nb * d + (lane << 2);
+#pragma unroll
+                for (int q = 0; q < NCH; ++q) hh[u][q] = ld4<T>(row + q * 256);
+            }
+#pragma unroll
+            for (int u = 0; u < PUN; ++u) {
+                float sacc = 0.f;
+#pragma unroll
+                for (int q = 0; q < NCH; ++q)
+                    sacc += pa[q][0] * hh[u][q][0] + pa[q][1] * hh[u][q][1] + pa[q][2] * hh[u][q][2] + pa[q][3] * hh[u][q][3];
+                sacc = wave_sum(sacc);
+                if (lane == 0 && j0 + u < t) plog[j0 + u] = sacc / (float)d;
+            }
+        }
+    };
+    if (d == 512) ptr_logits(std::integral_constant<int, 2>{});
+    else if (d == 256) ptr_logits(std::integral_constant<int, 1>{});
+    else if (d == 768) ptr_logits(std::integral_constant<int, 3>{});
+    else if (d == 1024) ptr_logits(std::integral_constant<int, 4>{});
+    else {
+        for (int j = wave; j < t; j += 4) {
+            float s = 0.f;
+            for (int c = lane << 2; c < d; c += 256) {
+                const f32x4 a = ld4<T>(pf + c), hh = ld4<T>(cache + (int64_t)j * nb * d + c);
+                s += a[0] * hh[0] + a[1] * hh[1] + a[2] * hh[2] + a[3] * hh[3];
+            }
+            s = wave_sum(s);
+            if (lane == 0) plog[j] = s / (float)d;
+        }
+    }
+    if (wave == 0) {
+        float s = 0.f;
+        for (int c = lane << 2; c < d; c += 256) {
+            const f32x4 hh = ld4<T>(hb + c); const f32x4 w = *reinterpret_cast<const f32x4*>(sw_w + c);
+            s += hh[0] * w[0] + hh[1] * w[1] + hh[2] * w[2] + hh[3] * w[3];
+        }
+        s = wave_sum(s);
+        if (lane == 0) *s_sw = s + sw_b[0];
+    }
+    __syncthreads();
+    r.prob = 1.0f / (1.0f + expf(-*s_sw));
+    float pmax = -INFINITY;
+    for (int j = tid; j < t; j += 256) pmax = fmaxf(pmax, plog[j]);
+    pmax = block_max(pmax, sh);
+    float psum = 0.f;
+    for (int j = tid; j < t; j += 256) psum += expf(plog[j] - pmax);
+    psum = block_sum(psum, sh);
+    r.pmax = pmax; r.psum = psum;
+    return r;
+}
+
+template <typename F>
+__device__ __forceinline__ void row_dist_visit(const RowDist& r, const float* vr, int V, const float* plog, int t, int jend, F&& f) {
+    const int tid = threadIdx.x, sz = t + 1, i = t;
+    if (sz < 6) {                                                     // models.py:172-173: un-gated vocab softmax
+        for (int k = tid; k < V; k += 256) f(expf(vr[k] - r.vmax) / r.vsum, k);
+        return;
+    }
+    const float gate_v = 1.0f - r.prob;
+    for (int k = tid; k < V; k += 256) f((expf(vr[k] - r.vmax) / r.vsum) * gate_v, k);
+    for (int j = tid; j < jend; j += 256) {
+        float val = 1e-6f;                                            // models.py:183-184 fill after gating
+        if (ptr_allowed(i, j)) val = (j < i) ? (expf(plog[j] - r.pmax) / r.psum) * r.prob : 0.f;
+        f(val, V + j);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int ldv, const T* pfeat, const T* h, T* hid_cache,
                                                          const float* sw_w, const float* sw_b, int64_t* tokens,
@@ -274,7 +394,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int 
     __shared__ ArgMax sha[4];
     __shared__ float s_sw;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int t = *t_dev, sz = t + 1, i = t;
+    const int t = *t_dev, sz = t + 1;
     const T* hb = h + (int64_t)b * d;
     // hidden-state cache laid out [Tmax][B][d]: the 256 blocks walk the rows j in step, and with a per-sequence
     // [B][Tmax][d] layout (1 MB apart) they would all hit the same HBM channel at the same time
@@ -282,86 +402,9 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int 
     T* cache = hid_cache + (int64_t)b * d;                          // row j of this sequence: cache + j * nb * d
     for (int c = tid; c < d; c += 256) cache[(int64_t)t * nb * d + c] = hb[c];
     const float* vr = vlog + (int64_t)b * ldv;
-    // vocab softmax statistics
-    float vmax = -INFINITY;
-    for (int k = tid; k < V; k += 256) vmax = fmaxf(vmax, vr[k]);
-    vmax = block_max(vmax, sh);
-    float vsum = 0.f;
-    for (int k = tid; k < V; k += 256) vsum += expf(vr[k] - vmax);
-    vsum = block_sum(vsum, sh);
+    const RowDist rd = row_dist_prepare<T>(vr, V, pfeat + (int64_t)b * d, hb, cache, nb, t, d, sw_w, sw_b, plog, sh, &s_sw);
     ArgMax best{-INFINITY, 0x7fffffff};
-    if (sz < 6) {                                                     // models.py:172-173: un-gated vocab softmax
-        for (int k = tid; k < V; k += 256) best = better(best, ArgMax{expf(vr[k] - vmax) / vsum, k});
-    } else {
-        // pointer logits over the hidden prefix (row j = t is written above but masked: j >= i)
-        // each wave takes 8 cached rows at a time, all their loads issued (unconditionally: rows clamped, tail discarded)
-        // before the first reduction; the pointer-feature row stays in registers.  Per row the arithmetic order is the
-        // one-row-at-a-time order (chunk by chunk per lane, then the wave sum): logits and greedy tokens are unchanged.
-        const T* pf = pfeat + (int64_t)b * d;
-        auto ptr_logits = [&](auto NCH_) {
-            constexpr int NCH = decltype(NCH_)::value, PUN = 8;           // NCH = d / 256 chunks of 4 columns per lane
-            f32x4 pa[NCH];
-#pragma unroll
-            for (int q = 0; q < NCH; ++q) pa[q] = ld4<T>(pf + (lane << 2) + q * 256);
-            for (int j0 = wave * PUN; j0 < t; j0 += 4 * PUN) {
-                f32x4 hh[PUN][NCH];
-#pragma unroll
-                for (int u = 0; u < PUN; ++u) {
-                    const T* row = cache + (int64_t)min(j0 + u, t - 1) * nb * d + (lane << 2);
-#pragma unroll
-                    for (int q = 0; q < NCH; ++q) hh[u][q] = ld4<T>(row + q * 256);
-                }
-#pragma unroll
-                for (int u = 0; u < PUN; ++u) {
-                    float sacc = 0.f;
-#pragma unroll
-                    for (int q = 0; q < NCH; ++q)
-                        sacc += pa[q][0] * hh[u][q][0] + pa[q][1] * hh[u][q][1] + pa[q][2] * hh[u][q][2] + pa[q][3] * hh[u][q][3];
-                    sacc = wave_sum(sacc);
-                    if (lane == 0 && j0 + u < t) plog[j0 + u] = sacc / (float)d;
-                }
-            }
-        };
-        if (d == 512) ptr_logits(std::integral_constant<int, 2>{});
-        else if (d == 256) ptr_logits(std::integral_constant<int, 1>{});
-        else if (d == 768) ptr_logits(std::integral_constant<int, 3>{});
-        else if (d == 1024) ptr_logits(std::integral_constant<int, 4>{});
-        else {
-            for (int j = wave; j < t; j += 4) {
-                float s = 0.f;
-                for (int c = lane << 2; c < d; c += 256) {
-                    const f32x4 a = ld4<T>(pf + c), hh = ld4<T>(cache + (int64_t)j * nb * d + c);
-                    s += a[0] * hh[0] + a[1] * hh[1] + a[2] * hh[2] + a[3] * hh[3];
-                }
-                s = wave_sum(s);
-                if (lane == 0) plog[j] = s / (float)d;
-            }
-        }
-        if (wave == 0) {
-            float s = 0.f;
-            for (int c = lane << 2; c < d; c += 256) {
-                const f32x4 hh = ld4<T>(hb + c); const f32x4 w = *reinterpret_cast<const f32x4*>(sw_w + c);
-                s += hh[0] * w[0] + hh[1] * w[1] + hh[2] * w[2] + hh[3] * w[3];
-            }
-            s = wave_sum(s);
-            if (lane == 0) s_sw = s + sw_b[0];
-        }
-        __syncthreads();
-        const float prob = 1.0f / (1.0f + expf(-s_sw));
-        float pmax = -INFINITY;
-        for (int j = tid; j < t; j += 256) pmax = fmaxf(pmax, plog[j]);
-        pmax = block_max(pmax, sh);
-        float psum = 0.f;
-        for (int j = tid; j < t; j += 256) psum += expf(plog[j] - pmax);
-        psum = block_sum(psum, sh);
-        const float gate_v = 1.0f - prob;
-        for (int k = tid; k < V; k += 256) best = better(best, ArgMax{(expf(vr[k] - vmax) / vsum) * gate_v, k});
-        for (int j = tid; j < sz; j += 256) {
-            float val = 1e-6f;                                        // models.py:183-184 fill after gating
-            if (ptr_allowed(i, j)) val = (j < i) ? (expf(plog[j] - pmax) / psum) * prob : 0.f;
-            best = better(best, ArgMax{val, V + j});
-        }
-    }
+    row_dist_visit(rd, vr, V, plog, t, sz, [&](float p, int k) { best = better(best, ArgMax{p, k}); });
     // block arg-max (first maximum)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -397,6 +440,153 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int 
     if (tid == 0) {
         const unsigned k = atomicAdd(reinterpret_cast<unsigned*>(t_dev + 1), 1u);
         if (k == gridDim.x - 1) { t_dev[1] = 0; t_dev[0] = t + 1; }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Beam search.  Rows are hypotheses: row b * K + k is beam k of drawing b.  The step up to the heads is the
+// greedy step on B * K rows; its end is these three kernels instead of dec_sample_kernel.
+
+// Per-row top-K of the distribution (row_dist_prepare / row_dist_visit, the greedy kernel's own p values), ranked by the greedy
+// kernel's first-max order (larger p, then the smaller index), candidates with p = 0 and the self pointer j = t left out.  K rounds of
+// the block arg-max, round k taking the best candidate ordered strictly after the one of round k - 1 (the order is total, so no
+// candidate is marked).  Writes cand_lp = logf(p), cand_tok (a pointer resolves its token from this row's own history,
+// models.py:248-251), cand_att for ranks 0 .. K-1; ranks without a candidate get (-inf, PAD, -1).  A finished row has the one
+// candidate (0, PAD, -1).  Also writes this row's hidden state into hid_cache, as the greedy kernel does.
+template <typename T>
+__global__ __launch_bounds__(256) void dec_beam_cand_kernel(const float* vlog, int ldv, const T* pfeat, const T* h, T* hid_cache,
+                                                            const float* sw_w, const float* sw_b, const int64_t* tokens,
+                                                            const int32_t* finished, const int32_t* t_dev, int Tmax, int d, int V,
+                                                            int K, int pad_tok, float* cand_lp, int32_t* cand_tok, int32_t* cand_att) {
+    __shared__ float plog[MAX_T];
+    __shared__ float sh[4];
+    __shared__ ArgMax sha[4];
+    __shared__ float s_sw;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t = *t_dev;
+    const T* hb = h + (int64_t)b * d;
+    const int64_t nb = gridDim.x;
+    T* cache = hid_cache + (int64_t)b * d;                          // [Tmax][rows][d], as in dec_sample_kernel
+    for (int c = tid; c < d; c += 256) cache[(int64_t)t * nb * d + c] = hb[c];
+    float* lp = cand_lp + (int64_t)b * K;
+    int32_t* ct = cand_tok + (int64_t)b * K;
+    int32_t* ca = cand_att + (int64_t)b * K;
+    if (finished[b]) {                                              // frozen beam (uniform branch: one row per block)
+        if (tid < K) { lp[tid] = tid == 0 ? 0.f : -INFINITY; ct[tid] = pad_tok; ca[tid] = -1; }
+        return;
+    }
+    const float* vr = vlog + (int64_t)b * ldv;
+    const RowDist rd = row_dist_prepare<T>(vr, V, pfeat + (int64_t)b * d, hb, cache, nb, t, d, sw_w, sw_b, plog, sh, &s_sw);
+    ArgMax prev{INFINITY, -1};
+    for (int k = 0; k < K; ++k) {
+        ArgMax best{-INFINITY, 0x7fffffff};
+        row_dist_visit(rd, vr, V, plog, t, t, [&](float p, int idx) {       // (jend = t: the self pointer is no candidate)
+            if (p > 0.f && (p < prev.v || (p == prev.v && idx > prev.i))) best = better(best, ArgMax{p, idx});
+        });
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            ArgMax other{__shfl_xor(best.v, o), __shfl_xor(best.i, o)};
+            best = better(best, other);
+        }
+        if (lane == 0) sha[wave] = best;
+        __syncthreads();
+        best = better(better(sha[0], sha[1]), better(sha[2], sha[3]));
+        __syncthreads();                                            // (sha is rewritten by the next round)
+        if (tid == 0) {
+            if (best.i == 0x7fffffff) { lp[k] = -INFINITY; ct[k] = pad_tok; ca[k] = -1; }
+            else {
+                int64_t tok = best.i, ptr = -1;
+                if (best.i >= V) { ptr = best.i - V; tok = tokens[(int64_t)b * Tmax + ptr]; }
+                lp[k] = logf(best.v); ct[k] = (int32_t)tok; ca[k] = (int32_t)ptr;
+            }
+        }
+        prev = best;
+    }
+}
+
+// Merge per drawing (one block, K * K <= 256 candidates, thread c = parent beam c / K, per-row rank c % K): ranked by
+// score[parent] + cand_lp (f32) descending, ties to the smaller parent beam, then the better rank - i.e. to the smaller c.  The best K
+// become the new beams: score, finished, first_end, parent row, and the token / attach at position t.  Everything of the drawing is
+// read before anything is written (the new beams replace their parents' rows).
+__global__ __launch_bounds__(256) void dec_beam_merge_kernel(const float* cand_lp, const int32_t* cand_tok, const int32_t* cand_att,
+                                                             float* scores, int32_t* finished, int32_t* first_end, int32_t* parent,
+                                                             int64_t* tokens, int64_t* attach, const int32_t* t_dev, int Tmax, int K,
+                                                             int end_tok) {
+    __shared__ float sc[256];
+    __shared__ int32_t n_par[16], n_tok[16], n_att[16], n_fin[16], n_fe[16];
+    __shared__ float n_sc[16];
+    const int tid = threadIdx.x, KK = K * K, r0 = blockIdx.x * K;
+    const int t = *t_dev;
+    float mine = -INFINITY;
+    int kp = 0, tok = 0, att = -1, fin = 0, fe = -1;
+    if (tid < KK) {
+        kp = tid / K;
+        mine = scores[r0 + kp] + cand_lp[(int64_t)r0 * K + tid];
+        tok = cand_tok[(int64_t)r0 * K + tid]; att = cand_att[(int64_t)r0 * K + tid];
+        fin = finished[r0 + kp]; fe = first_end[r0 + kp];
+        sc[tid] = mine;
+    }
+    __syncthreads();
+    if (tid < KK) {
+        int pos = 0;
+        for (int j = 0; j < KK; ++j) pos += (sc[j] > mine || (sc[j] == mine && j < tid)) ? 1 : 0;
+        if (pos < K) {
+            const bool ended = fin || tok == end_tok;
+            n_par[pos] = r0 + kp; n_tok[pos] = tok; n_att[pos] = att; n_sc[pos] = mine;
+            n_fin[pos] = ended ? 1 : 0;
+            n_fe[pos] = fin ? fe : (tok == end_tok ? t : -1);
+        }
+    }
+    __syncthreads();
+    if (tid < K) {
+        const int r = r0 + tid;
+        scores[r] = n_sc[tid]; finished[r] = n_fin[tid]; first_end[r] = n_fe[tid]; parent[r] = n_par[tid];
+        tokens[(int64_t)r * Tmax + t] = n_tok[tid];
+        attach[(int64_t)r * Tmax + t] = n_att[tid];
+    }
+}
+
+// History reorder: every row r whose parent p = parent[r] is another row takes p's history.  Two launches: dir 0 copies the parent's
+// history into r's slot of the scratch, dir 1 copies the slot back into row r - so every row reads its parent's OLD history.  A segment
+// is one per-row cache: `outer` pieces `outer_stride` bytes apart, each (t + pos_add) * unit contiguous bytes (per-head self-attention
+// caches, the row caches of the absorbed self-attention, tokens / attach), or - `by_pos` - t + pos_add pieces of `unit` bytes
+// (hid_cache, [Tmax][rows][d]).
+__global__ __launch_bounds__(256) void dec_beam_copy_kernel(const BeamCopy cp, const int32_t* parent, const int32_t* t_dev, int dir) {
+    const int r = blockIdx.y, p = parent[r];
+    if (p == r) return;
+    const int t = *t_dev;
+    char* slot = cp.scratch + (int64_t)r * cp.scr_row;
+    for (int s = 0; s < cp.nseg; ++s) {
+        const BeamSeg g = cp.seg[s];
+        const int npos = t + g.pos_add;
+        const int64_t outer = g.by_pos ? npos : g.outer;
+        const int64_t inner = g.by_pos ? (int64_t)g.unit : (int64_t)npos * g.unit;     // bytes
+        char* row = g.ptr + (int64_t)(dir == 0 ? p : r) * g.row_stride;
+        char* scr = slot + g.scr_off;
+        if (g.vec16) {
+            const int64_t nv = inner >> 4, total = outer * nv;
+            for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+                const int64_t o = e / nv, i = (e - o * nv) << 4;
+                u32x4* a = reinterpret_cast<u32x4*>(row + o * g.outer_stride + i);
+                u32x4* c = reinterpret_cast<u32x4*>(scr + o * g.scr_outer + i);
+                if (dir == 0) *c = *a; else *a = *c;
+            }
+        } else {                                                    // (8-byte units: tokens / attach)
+            const int64_t nv = inner >> 3, total = outer * nv;
+            for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+                const int64_t o = e / nv, i = (e - o * nv) << 3;
+                int64_t* a = reinterpret_cast<int64_t*>(row + o * g.outer_stride + i);
+                int64_t* c = reinterpret_cast<int64_t*>(scr + o * g.scr_outer + i);
+                if (dir == 0) *c = *a; else *a = *c;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void dec_beam_init_kernel(float* scores, int32_t* finished, int32_t* parent, int rows, int K) {
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < rows; r += gridDim.x * 256) {
+        scores[r] = (r % K) == 0 ? 0.f : -INFINITY;                 // only beam 0 of a drawing is live at t = 0
+        finished[r] = 0; parent[r] = r;
     }
 }
 
@@ -544,6 +734,29 @@ DecodeModes decode_modes(const pa_model_cfg& c, int B, int S) {
     return r;
 }
 
+// The self-attention form of the step (shared by pa_decode_begin and the beam workspace query, whose reorder copies what this form caches).
+struct StepForm { bool mq_contract, mq_self, mq_self_bf; };
+StepForm step_form(const pa_model_cfg& c, int B, int S, int Tmax) {
+    const int d = c.d_model;
+    const DecodeModes md = decode_modes(c, B, S);
+    StepForm r;
+    static const int contract_env = getenv("PLANK_DECODE_MQ_CONTRACT") ? atoi(getenv("PLANK_DECODE_MQ_CONTRACT")) : -1;
+    r.mq_contract = md.mq && d / c.n_head == 64 && (contract_env >= 0 ? contract_env != 0 : c.dtype == PA_F32);
+    // exact f32: the self-attention in the same form - the step caches the layer-input rows x_t instead of K and V (half the bytes of what is
+    // then the largest stream of the f32 step), q~ = W_k^T q, W_v behind the softmax (q . b_k cancels, b_v is added once).  PLANK_DECODE_MQ_SELF=0.
+    static const int self_env = getenv("PLANK_DECODE_MQ_SELF") ? atoi(getenv("PLANK_DECODE_MQ_SELF")) : 1;
+    r.mq_self = md.mq && r.mq_contract && c.dtype == PA_F32 && self_env != 0 && Tmax <= 16000;
+    // bf16 (round 6; needs the f32 residual stream's step form): pays from ~200 batch elements on - measured in one session, B 256 x 1024 steps:
+    // 0.969 -> 0.929 ms / step (264 k -> 276 k tokens/s; half the bytes of the self-attention stream against one more launch and a K = H d
+    // out-projection per layer); B 64: 0.557 -> 0.662, B 16: 0.476 -> 0.609 (profiles/r06_decode_self_absorbed.txt).
+    // PLANK_DECODE_MQ_SELF_BF16: 0 never, 1 always, unset = B >= PLANK_DECODE_MQ_SELF_MINB (200).
+    static const int self_bf_env = getenv("PLANK_DECODE_MQ_SELF_BF16") ? atoi(getenv("PLANK_DECODE_MQ_SELF_BF16")) : -1;
+    static const int self_bf_minb = getenv("PLANK_DECODE_MQ_SELF_MINB") ? atoi(getenv("PLANK_DECODE_MQ_SELF_MINB")) : 200;
+    r.mq_self_bf = md.mq && !r.mq_contract && c.dtype == PA_BF16 && md.f32res && d / c.n_head == 64 && Tmax <= MQ_MAXS &&
+                    (self_bf_env >= 0 ? self_bf_env != 0 : B >= self_bf_minb);
+    return r;
+}
+
 size_t dec_layout(pa_model* m, DecodeLayout* L, char* base, int B, int S, int Tmax) {
     const pa_model_cfg& c = m->cfg;
     const size_t e = c.dtype == PA_BF16 ? 2 : 4, d = c.d_model, ff = c.d_ff;
@@ -610,6 +823,70 @@ int launch_attn(pa_model* m, T* out, const T* q, int ldq, T* kc, T* vc, int Lmax
     return 0;
 }
 
+// Segment table of the beam history reorder (dec_beam_copy_kernel) for `rows` hypothesis rows in step form `sf`; L may be a layout
+// without pointers (the workspace query).  Returns the scratch bytes of one row, or a negative PA_E* code.
+int64_t beam_segments(const pa_model_cfg& c, const StepForm& sf, const DecodeLayout* L, int rows, int Tmax, BeamCopy* cp) {
+    const int64_t e = c.dtype == PA_BF16 ? 2 : 4, d = c.d_model, H = c.n_head, dh = d / H;
+    int n = 0;
+    int64_t off = 0;
+    auto add = [&](void* ptr, int64_t row_stride, int outer, int64_t outer_stride, int unit, int by_pos, int pos_add) {
+        if (n >= BEAM_MAX_SEG) { n = BEAM_MAX_SEG + 1; return; }
+        BeamSeg& g = cp->seg[n++];
+        g.ptr = (char*)ptr; g.row_stride = row_stride; g.outer = outer; g.outer_stride = outer_stride; g.unit = unit;
+        g.by_pos = by_pos; g.pos_add = pos_add; g.pad_ = 0;
+        g.vec16 = (unit % 16 == 0 && row_stride % 16 == 0 && outer_stride % 16 == 0) ? 1 : 0;
+        g.scr_off = off; g.scr_outer = by_pos ? unit : (int64_t)Tmax * unit;
+        off += ((by_pos ? (int64_t)Tmax * unit : (int64_t)outer * Tmax * unit) + 15) / 16 * 16;
+    };
+    for (int i = 0; i < c.n_dec; ++i) {
+        if (sf.mq_self || sf.mq_self_bf) {      // row cache of the layer inputs [rows][Tmax][d] (self_v is not read in these forms)
+            add(L ? L->self_k[i] : nullptr, Tmax * d * e, 1, 0, (int)(d * e), 0, 1);
+        } else {                                // per-head K / V caches [rows][H][Tmax][dh]
+            add(L ? L->self_k[i] : nullptr, H * Tmax * dh * e, (int)H, Tmax * dh * e, (int)(dh * e), 0, 1);
+            add(L ? L->self_v[i] : nullptr, H * Tmax * dh * e, (int)H, Tmax * dh * e, (int)(dh * e), 0, 1);
+        }
+    }
+    add(L ? L->hid_cache : nullptr, d * e, 0, (int64_t)rows * d * e, (int)(d * e), 1, 1);     // [Tmax][rows][d]
+    add(L ? (void*)L->tokens : nullptr, (int64_t)Tmax * 8, 1, 0, 8, 0, 0);                    // positions 0 .. t-1
+    add(L ? (void*)L->attach : nullptr, (int64_t)Tmax * 8, 1, 0, 8, 0, 0);
+    if (n > BEAM_MAX_SEG) return PA_ESHAPE;
+    cp->nseg = n; cp->pad_ = 0;
+    cp->scr_row = (off + 255) / 256 * 256;
+    return cp->scr_row;
+}
+
+// Beam workspace: scores f32 [rows], finished / parent int32 [rows], candidates (f32 log p, int32 token, int32 attach) [rows][K], then
+// the reorder scratch [rows][scr_row].
+size_t beam_layout(DecodeLayout* L, char* base, int rows, int K, int64_t scr_row) {
+    Arena a{base, 0};
+    L->bm_score = (float*)a.take((size_t)rows * 4); L->bm_fin = (int32_t*)a.take((size_t)rows * 4);
+    L->bm_parent = (int32_t*)a.take((size_t)rows * 4);
+    L->bm_clp = (float*)a.take((size_t)rows * K * 4); L->bm_ctok = (int32_t*)a.take((size_t)rows * K * 4);
+    L->bm_catt = (int32_t*)a.take((size_t)rows * K * 4);
+    L->bm_copy.scratch = (char*)a.take((size_t)rows * scr_row);
+    return a.off;
+}
+
+// The end of a beam step (in place of dec_sample_kernel): candidates, merge, history reorder.  The next step's input embedding is
+// dec_embed_kernel at the start of the next step (it reads the token at t - 1 of each row, i.e. of the new beam).
+template <typename T>
+int beam_tail(pa_model* m, int ldv, hipStream_t s) {
+    const pa_model_cfg& c = m->cfg;
+    DecodeLayout* L = m->dec;
+    const int rows = L->B, K = L->beamK, tl = m->tail();
+    PA_LAUNCH(dec_beam_cand_kernel<T>, dim3(rows), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h, (T*)L->hid_cache,
+              (const float*)m->pf[tl + T_SW_W], (const float*)m->pf[tl + T_SW_B], L->tokens, L->bm_fin, L->t_dev, L->Tmax, c.d_model, c.vocab,
+              K, c.pad, L->bm_clp, L->bm_ctok, L->bm_catt);
+    PA_LAUNCH(dec_beam_merge_kernel, dim3(rows / K), dim3(256), 0, s, L->bm_clp, L->bm_ctok, L->bm_catt, L->bm_score, L->bm_fin,
+              L->first_end, L->bm_parent, L->tokens, L->attach, L->t_dev, L->Tmax, K, c.end);
+    if (K > 1) {
+        const dim3 g(std::max(4, std::min(64, 4096 / rows)), rows);
+        PA_LAUNCH(dec_beam_copy_kernel, g, dim3(256), 0, s, L->bm_copy, L->bm_parent, L->t_dev, 0);
+        PA_LAUNCH(dec_beam_copy_kernel, g, dim3(256), 0, s, L->bm_copy, L->bm_parent, L->t_dev, 1);
+    }
+    return 0;
+}
+
 // One decode step in 2 * n_dec + 1 parts, each ending right after an attention launch (part 2i: self-attention of layer i,
 // part 2i + 1: its cross-attention; the last part is the tail: final norm, heads, sampling).  The attention launches are the
 // HBM-bound third of the step (they stream the K/V caches); everything between them is a chain of latency-bound launches on B
@@ -658,7 +935,8 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
     // fence, ticket) costs the same again.  Fourth fusion of this decode step that does not pay.  The embedding
     // of step 0 is all zeros (models.py:114-123 with no token yet): pa_decode_begin clears x.
     static const int fuse_tail = getenv("PLANK_DECODE_FUSE_TAIL") ? atoi(getenv("PLANK_DECODE_FUSE_TAIL")) : 0;
-    if (part == 0 && !fuse_tail) {
+    const bool unfused = !fuse_tail || L->beamK > 0;          // (a beam step always takes the unfused tail: beam_tail)
+    if (part == 0 && unfused) {
         const int g1 = (B * (d / 4) + 255) / 256;
         if (L->f32res)
             PA_LAUNCH(dec_embed_kernel<float>, dim3(g1), dim3(256), 0, s, (float*)L->x, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
@@ -727,11 +1005,13 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
             if (!tail_norm)
                 PA_LAUNCH(dec_cast_kernel, dim3((B * d / 4 + 255) / 256), dim3(256), 0, s, (bf16*)L->h, (const float*)L->hf, (int64_t)B * d / 4);
             RC(linear(m, L->h, PL(tl + T_PTR_W), PF(tl + T_PTR_B), L->pfeat, d, B, d, d, 0, nullptr, -1, st));
-            PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
-                               (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
-                               c.vocab, c.end, fuse_tail, (float*)L->x, (T*)nullptr, (bf16*)L->xb, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
-                               c.out_dof);
-            if (!fuse_tail) PA_LAUNCH(dec_advance_kernel, dim3(1), dim3(64), 0, s, L->t_dev);
+            if (L->beamK > 0) RC(beam_tail<T>(m, ldv, s));
+            else
+                PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
+                                   (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
+                                   c.vocab, c.end, fuse_tail, (float*)L->x, (T*)nullptr, (bf16*)L->xb, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
+                                   c.out_dof);
+            if (unfused) PA_LAUNCH(dec_advance_kernel, dim3(1), dim3(64), 0, s, L->t_dev);
             return 0;
         }
         const int i = part / 2, pb = m->dec_base(i);
@@ -812,11 +1092,13 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
         const int tl = m->tail(), ldv = (c.vocab + 7) / 8 * 8;
         RC(linear(m, L->h, PL(tl + T_VOCAB_W), PF(tl + T_VOCAB_B), L->vlog, ldv, B, c.vocab, d, 0, nullptr, PA_F32, st));
         RC(linear(m, L->h, PL(tl + T_PTR_W), PF(tl + T_PTR_B), L->pfeat, d, B, d, d, 0, nullptr, -1, st));
-        PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
-                           (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
-                           c.vocab, c.end, fuse_tail, (float*)nullptr, (T*)L->x, (bf16*)nullptr, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
-                           c.out_dof);
-        if (!fuse_tail) PA_LAUNCH(dec_advance_kernel, dim3(1), dim3(64), 0, s, L->t_dev);
+        if (L->beamK > 0) RC(beam_tail<T>(m, ldv, s));
+        else
+            PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
+                               (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
+                               c.vocab, c.end, fuse_tail, (float*)nullptr, (T*)L->x, (bf16*)nullptr, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
+                               c.out_dof);
+        if (unfused) PA_LAUNCH(dec_advance_kernel, dim3(1), dim3(64), 0, s, L->t_dev);
         return 0;
     }
     const int i = part / 2;
@@ -900,21 +1182,10 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
     const void* memory = c.has_enc_norm ? m->memory : m->X[c.n_enc];
     hipStream_t s = (hipStream_t)stream;
     const DecodeModes md = decode_modes(c, B, S);
+    const StepForm sf = step_form(c, B, S, Tmax);
     L->fold = md.fold; L->f32res = md.f32res; L->mq = md.mq;           // (what each is and where it was measured: decode_modes)
-    static const int contract_env = getenv("PLANK_DECODE_MQ_CONTRACT") ? atoi(getenv("PLANK_DECODE_MQ_CONTRACT")) : -1;
-    L->mq_contract = L->mq && d / c.n_head == 64 && (contract_env >= 0 ? contract_env != 0 : c.dtype == PA_F32);
-    // exact f32: the self-attention in the same form - the step caches the layer-input rows x_t instead of K and V (half the bytes of what is
-    // then the largest stream of the f32 step), q~ = W_k^T q, W_v behind the softmax (q . b_k cancels, b_v is added once).  PLANK_DECODE_MQ_SELF=0.
-    static const int self_env = getenv("PLANK_DECODE_MQ_SELF") ? atoi(getenv("PLANK_DECODE_MQ_SELF")) : 1;
-    L->mq_self = L->mq && L->mq_contract && c.dtype == PA_F32 && self_env != 0 && Tmax <= 16000;
-    // bf16 (round 6; needs the f32 residual stream's step form): pays from ~200 batch elements on - measured in one session, B 256 x 1024 steps:
-    // 0.969 -> 0.929 ms / step (264 k -> 276 k tokens/s; half the bytes of the self-attention stream against one more launch and a K = H d
-    // out-projection per layer); B 64: 0.557 -> 0.662, B 16: 0.476 -> 0.609 (profiles/r06_decode_self_absorbed.txt).
-    // PLANK_DECODE_MQ_SELF_BF16: 0 never, 1 always, unset = B >= PLANK_DECODE_MQ_SELF_MINB (200).
-    static const int self_bf_env = getenv("PLANK_DECODE_MQ_SELF_BF16") ? atoi(getenv("PLANK_DECODE_MQ_SELF_BF16")) : -1;
-    static const int self_bf_minb = getenv("PLANK_DECODE_MQ_SELF_MINB") ? atoi(getenv("PLANK_DECODE_MQ_SELF_MINB")) : 200;
-    L->mq_self_bf = L->mq && !L->mq_contract && c.dtype == PA_BF16 && md.f32res && d / c.n_head == 64 && Tmax <= MQ_MAXS &&
-                    (self_bf_env >= 0 ? self_bf_env != 0 : B >= self_bf_minb);
+    L->mq_contract = sf.mq_contract; L->mq_self = sf.mq_self; L->mq_self_bf = sf.mq_self_bf;   // (step_form)
+    L->beamK = 0;                                               // greedy until pa_decode_beam_begin
     if (L->mq) {
         // absorbed cross-attention: the step reads the encoder output rows themselves - no K / V projection of the memory at all
         hipError_t hm = hipMemcpyAsync(L->mem, memory, (size_t)m->NE * d * e, hipMemcpyDeviceToDevice, s);
@@ -1009,6 +1280,7 @@ extern "C" int pa_decode_step(pa_model* m, void* stream) {
 extern "C" int pa_decode_step_pair(pa_model* a, pa_model* b, void* stream_a, void* stream_b) {
     if (!a || !b || !a->dec || !b->dec || a->dec->B <= 0 || b->dec->B <= 0) return PA_EINVAL;
     if (a->cfg.n_dec != b->cfg.n_dec || a->cfg.dtype != b->cfg.dtype) return PA_EINVAL;
+    if (a->dec->beamK > 0 || b->dec->beamK > 0) return PA_EINVAL;     // beams run as one lane
     const int n = 2 * a->cfg.n_dec;
     std::vector<hipEvent_t>& ev = a->dec->pair_ev;
     if ((int)ev.size() != 2 * n) {
@@ -1071,5 +1343,36 @@ extern "C" int pa_dec_self_mq32(float* ctx, const float* qt, const float* xcache
 extern "C" int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void** first_end, void** t_dev) {
     if (!m || !m->dec || !tokens || !attach || !first_end || !t_dev) return PA_EINVAL;
     *tokens = m->dec->tokens; *attach = m->dec->attach; *first_end = m->dec->first_end; *t_dev = m->dec->t_dev;
+    return 0;
+}
+
+// Beam search over a begun decode (include/plank_hip.h).
+extern "C" int64_t pa_decode_beam_ws_bytes(pa_model* m, int32_t rows, int32_t S, int32_t Tmax, int32_t K) {
+    if (!m || K < 1 || K > PA_BEAM_MAX || rows <= 0 || rows % K != 0 || S <= 0 || Tmax <= 0 || Tmax > MAX_T) return PA_EINVAL;
+    BeamCopy cp;
+    const int64_t scr = beam_segments(m->cfg, step_form(m->cfg, rows, S, Tmax), nullptr, rows, Tmax, &cp);
+    if (scr < 0) return scr;
+    DecodeLayout tmp;
+    return (int64_t)beam_layout(&tmp, nullptr, rows, K, scr) + 256;
+}
+
+extern "C" int pa_decode_beam_begin(pa_model* m, int32_t K, void* ws, int64_t ws_bytes, void* stream) {
+    if (!m || !m->dec || m->dec->B <= 0 || !ws || K < 1 || K > PA_BEAM_MAX || m->dec->B % K != 0) return PA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return PA_EALIGN;
+    DecodeLayout* L = m->dec;
+    const int rows = L->B;
+    const StepForm sf{L->mq_contract, L->mq_self, L->mq_self_bf};
+    const int64_t scr = beam_segments(m->cfg, sf, L, rows, L->Tmax, &L->bm_copy);
+    if (scr < 0) return (int)scr;
+    const size_t need = beam_layout(L, (char*)ws, rows, K, scr);
+    if ((int64_t)need > ws_bytes) { L->beamK = 0; return PA_EINVAL; }
+    PA_LAUNCH(dec_beam_init_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, L->bm_score, L->bm_fin, L->bm_parent, rows, K);
+    L->beamK = K;
+    return 0;
+}
+
+extern "C" int pa_decode_beam_buffers(pa_model* m, void** scores, void** parents, void** finished) {
+    if (!m || !m->dec || m->dec->beamK <= 0 || !scores || !parents || !finished) return PA_EINVAL;
+    *scores = m->dec->bm_score; *parents = m->dec->bm_parent; *finished = m->dec->bm_fin;
     return 0;
 }

@@ -229,3 +229,106 @@ class GreedyDecoder:
         tokens = torch.cat([b[0][:, :n] for b in bufs]) if len(bufs) > 1 else bufs[0][0][:, :n].clone()
         attach = torch.cat([b[1][:, :n] for b in bufs]) if len(bufs) > 1 else bufs[0][1][:, :n].clone()
         return tokens, attach
+
+
+def _repeat_batch(batch, K):
+    """Every drawing repeated K times, drawing-major (row b*K + k is beam k of drawing b)."""
+    out = {}
+    for k, v in batch.items():
+        if k.startswith("_"):
+            continue                                   # packing / groupings belong to the repeated batch: recomputed
+        if torch.is_tensor(v):
+            out[k] = v.repeat_interleave(K, dim=0)
+        elif isinstance(v, list):
+            out[k] = [x for x in v for _ in range(K)]
+        else:
+            out[k] = v
+    return out
+
+
+class BeamDecoder(GreedyDecoder):
+    """Beam search over the KV-cached decode step (include/plank_hip.h pa_decode_beam_*).
+
+    The decode runs B*K hypothesis rows - the encoder on the batch with every drawing repeated K times - and each captured step
+    ends with the beam selection (per-row top-K of the greedy step's own distribution, merge per drawing, history reorder)
+    instead of the greedy arg-max.  Always one lane.  ``length_penalty`` (alpha) only changes the final ranking of a drawing's
+    beams, by score / len^alpha (len = first END + 1, or Tmax); 0 ranks by the raw cumulative log-probability.  K = 1 gives the
+    greedy tokens up to each row's first END (PAD / attach -1 after it)."""
+
+    def __init__(self, model, beam_size, length_penalty=0.0, use_graph=None, check_every=16, strict_graph=False):
+        super().__init__(model, use_graph=use_graph, check_every=check_every, strict_graph=strict_graph, lanes=1)
+        self.beam_size = int(beam_size)
+        self.length_penalty = float(length_penalty)
+        model._ensure_handle()
+        # the library validates K (1 <= K <= PA_BEAM_MAX): PlankHipError here rather than at the first run
+        need = int(L.lib().pa_decode_beam_ws_bytes(model._handle, self.beam_size, 1, 1, self.beam_size))
+        if need < 0:
+            L.check(need, "pa_decode_beam_ws_bytes")
+        self._bws = None
+        self._bkey = None
+
+    def begin(self, batch, max_len=None):
+        """Encoder on the repeated batch + pa_decode_begin + pa_decode_beam_begin.  Returns (rows = B*K, Tmax)."""
+        m, K, lib = self.model, self.beam_size, L.lib()
+        rep = _repeat_batch(batch, K)
+        if m.unpad:
+            rep = m.prepare_batch(rep, groups=False)
+        rows, Tmax = super().begin(rep, max_len)
+        ln = self._lanes[0]
+        b = ln.keep[0]
+        need = int(lib.pa_decode_beam_ws_bytes(ln.h(), b.B, b.S, Tmax, K))
+        if need < 0:
+            L.check(need, "pa_decode_beam_ws_bytes")
+        if self._bws is None or self._bws.numel() < need + 256:
+            self._bws = torch.empty(need + 256, dtype=torch.uint8, device=m.flat_params.device)
+        base = (self._bws.data_ptr() + 255) // 256 * 256
+        L.check(lib.pa_decode_beam_begin(ln.h(), K, C.c_void_p(base), C.c_int64(self._bws.numel() - (base - self._bws.data_ptr())),
+                                         L.stream()), "pa_decode_beam_begin")
+        key = (self._bws.data_ptr(), K, ln.key)
+        if key != self._bkey:
+            self._graph = None
+        self._bkey = key
+        return rows, Tmax
+
+    def _beam_buffers(self, rows):
+        ptrs = [C.c_void_p() for _ in range(3)]
+        L.check(L.lib().pa_decode_beam_buffers(self._lanes[0].h(), *[C.byref(p) for p in ptrs]), "pa_decode_beam_buffers")
+        base = self._bws.data_ptr()
+
+        def view(p, dtype):
+            off = p.value - base
+            return self._bws[off: off + rows * 4].view(dtype)
+
+        return view(ptrs[0], torch.float32), view(ptrs[1], torch.int32), view(ptrs[2], torch.int32)
+
+    def run(self, batch, max_len=None, early_stop=True):
+        """Full beam search.  Returns a dict: ``tokens`` / ``attach`` int64 [B, n] (the best beam), ``beam_tokens`` /
+        ``beam_attach`` int64 [B, K, n], ``scores`` f32 [B, K] (cumulative log-probability), ``finished`` bool [B, K] and
+        ``lengths`` int64 [B, K], beams in final-ranking order.  n = max over rows of first END + 1 once every beam has
+        finished, else Tmax - the same with and without ``early_stop``."""
+        K = self.beam_size
+        rows, Tmax = self.begin(batch, max_len)
+        B = rows // K
+        tokens, attach, first_end = self._lanes[0].buffers(rows, Tmax)
+        scores, _, finished = self._beam_buffers(rows)
+        done = 0
+        while done < Tmax:
+            k = min(self.check_every, Tmax - done) if early_stop else Tmax - done
+            self.steps(k)
+            done += k
+            if early_stop and bool((finished != 0).all().cpu()):
+                break
+        self.last_steps = done
+        fe = first_end.view(B, K).long().cpu()
+        fin = (finished.view(B, K) != 0).cpu()
+        n = int(fe.max()) + 1 if bool(fin.all()) else Tmax
+        sc = scores.view(B, K).cpu()
+        lengths = torch.where(fe >= 0, fe + 1, torch.full_like(fe, Tmax))
+        key = sc / lengths.to(torch.float32) ** self.length_penalty if self.length_penalty != 0.0 else sc
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        dev = tokens.device
+        od = order.to(dev)
+        bt = tokens.view(B, K, Tmax)[:, :, :n].gather(1, od[:, :, None].expand(B, K, n)).contiguous()
+        ba = attach.view(B, K, Tmax)[:, :, :n].gather(1, od[:, :, None].expand(B, K, n)).contiguous()
+        return {"tokens": bt[:, 0].clone(), "attach": ba[:, 0].clone(), "beam_tokens": bt, "beam_attach": ba,
+                "scores": sc.gather(1, order), "finished": fin.gather(1, order), "lengths": lengths.gather(1, order)}

@@ -135,7 +135,7 @@ class PlankModel(nn.Module):
     def __init__(self, num_model=512, num_head=8, num_feedforward=1024, dropout=0.1, activation="relu",
                  normalize_before=True, num_encoder_layers=6, num_decoder_layers=6, num_view=3, num_type=2,
                  num_input_dof=4, num_output_dof=6, max_input_length=400, max_output_length=128, vocab_size=514,
-                 token=None, compute_dtype=None):
+                 token=None, compute_dtype=None, beam_size=1, length_penalty=0.0):
         super().__init__()
         # the reference hands the string to torch's Transformer layers (models.py:60-61,66-67), which take "relu" or "gelu"
         if activation not in ("relu", "gelu"):
@@ -146,6 +146,11 @@ class PlankModel(nn.Module):
         compute_dtype = compute_dtype or os.environ.get("PLANK_COMPUTE_DTYPE", "f32")
         if compute_dtype not in ("f32", "bf16", "x3"):
             raise ValueError("compute_dtype must be 'f32', 'bf16' or 'x3'")
+        # eval_step's decoder: greedy (1) or beam search with this many beams per drawing (decode.BeamDecoder, 1 <= K <= 16)
+        if isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= int(beam_size) <= 16:
+            raise ValueError(f"BEAM_SIZE must be an integer in [1, 16], got {beam_size!r}")
+        self.beam_size, self.length_penalty = int(beam_size), float(length_penalty)
+        self._beam_decoders = {}
         self.compute_mode = compute_dtype                      # what the caller asked for
         self.split3 = compute_dtype == "x3"
         self.compute_dtype = "f32" if self.split3 else compute_dtype     # storage / kernel dtype: 'x3' is f32 with split products
@@ -304,6 +309,7 @@ class PlankModel(nn.Module):
             self._handle = None
         self._ws = None
         self._decoder = None
+        self._beam_decoders = {}
         self._drop_x3_cache()
 
     def _drop_x3_cache(self):
@@ -849,18 +855,39 @@ class PlankModel(nn.Module):
         return valid_seq[:num_plank * self.num_output_dof].reshape(-1, self.num_output_dof)
 
     def eval_step(self, batch):
-        """reference models.py:267-323: greedy autoregressive sampling (KV-cached HIP decode)."""
+        """reference models.py:267-323: greedy autoregressive sampling (KV-cached HIP decode); beam search instead when the
+        model was built with beam_size > 1 (cfg.MODEL.BEAM_SIZE)."""
+        if self.beam_size > 1:
+            return self.beam_search(batch, self.beam_size, self.length_penalty)
         from .decode import GreedyDecoder
         self._ensure_handle()
         self._refresh_shadow()
         if self._decoder is None:
             self._decoder = GreedyDecoder(self)
         output, attach = self._decoder.run(batch)
+        return self._eval_dict(batch, output, attach)
+
+    def _eval_dict(self, batch, output, attach):
         predicts, groundtruths = [], []
         for i in range(output.shape[0]):
             predicts.append(self.parse_sequence(output[i]))
             groundtruths.append(self.parse_sequence(batch["output_value"][i].to(output.device)))
         return {"samples": output, "attach": attach, "predicts": predicts, "groundtruths": groundtruths}
+
+    def beam_search(self, batch, beam_size, length_penalty=0.0):
+        """Beam-search decode (decode.BeamDecoder): the eval_step dict of the best beam of every drawing plus ``scores``
+        [B, K], the cumulative log-probabilities of all beams in final-ranking order."""
+        from .decode import BeamDecoder
+        self._ensure_handle()
+        self._refresh_shadow()
+        key = (int(beam_size), float(length_penalty))
+        dec = self._beam_decoders.get(key)
+        if dec is None:
+            dec = self._beam_decoders[key] = BeamDecoder(self, beam_size, length_penalty)
+        r = dec.run(batch)
+        out = self._eval_dict(batch, r["tokens"], r["attach"])
+        out["scores"] = r["scores"]
+        return out
 
     def forward(self, batch):
         """reference models.py:325-330."""
@@ -892,12 +919,19 @@ class PlankModel(nn.Module):
 
 
 def build_model(cfg):
-    """reference models.py:333-343.  Optional ``cfg.MODEL.COMPUTE_DTYPE`` ('f32' | 'bf16' | 'x3')."""
+    """reference models.py:333-343.  Optional ``cfg.MODEL.COMPUTE_DTYPE`` ('f32' | 'bf16' | 'x3'), ``cfg.MODEL.BEAM_SIZE``
+    (eval_step decodes by beam search with this many beams, 1 <= K <= 16; absent or 1: greedy) and ``cfg.MODEL.LENGTH_PENALTY``
+    (alpha of the final beam ranking score / len^alpha, default 0)."""
     model_cfg = cfg.MODEL
-    dtype = getattr(model_cfg, "COMPUTE_DTYPE", None) if not isinstance(model_cfg, dict) else model_cfg.get("COMPUTE_DTYPE")
+
+    def opt(key, default=None):
+        v = getattr(model_cfg, key, None) if not isinstance(model_cfg, dict) else model_cfg.get(key)
+        return default if v is None else v
+
+    dtype = opt("COMPUTE_DTYPE")
     return PlankModel(
         cfg.MODEL.NUM_MODEL, cfg.MODEL.NUM_HEAD, cfg.MODEL.NUM_FEEDFORWARD, cfg.MODEL.DROPOUT,
         cfg.MODEL.ACTIVATION, cfg.MODEL.NORMALIZE_BEFORE, cfg.MODEL.NUM_ENCODER_LAYERS,
         cfg.MODEL.NUM_DECODER_LAYERS, cfg.DATA.NUM_VIEW, cfg.DATA.NUM_TYPE, cfg.DATA.NUM_INPUT_DOF,
         cfg.DATA.NUM_OUTPUT_DOF, cfg.DATA.MAX_INPUT_LENGTH, cfg.DATA.MAX_OUTPUT_LENGTH, cfg.DATA.VOCAB_SIZE,
-        cfg.TOKEN, compute_dtype=dtype)
+        cfg.TOKEN, compute_dtype=dtype, beam_size=opt("BEAM_SIZE", 1), length_penalty=float(opt("LENGTH_PENALTY", 0.0)))
