@@ -626,6 +626,43 @@ int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void** first_en
 int64_t pa_decode_beam_ws_bytes(pa_model* m, int32_t rows, int32_t S, int32_t Tmax, int32_t K);
 int pa_decode_beam_begin(pa_model* m, int32_t K, void* ws, int64_t ws_bytes, void* stream);
 int pa_decode_beam_buffers(pa_model* m, void** scores, void** parents, void** finished);
+/* Sampling over the same step.  N samples per drawing, 1 <= N <= PA_SAMPLE_MAX: the caller runs the encoder and
+ * pa_decode_begin on the batch with every drawing repeated N times (row b*N + n is sample n of drawing b), then switches the decode to
+ * sampling mode.  pa_decode_step then ends each step with one random draw per row instead of the greedy arg-max:
+ *   - the candidates are the greedy step's own distribution: vocab entries and pointers j < t with p > 0, ranked by p descending, ties
+ *     to the smaller index;
+ *   - weights w = expf((logf(p) - logf(p_max)) / temperature) (p / p_max at temperature 1); top_k > 0 keeps the first top_k in rank
+ *     order, top_p < 1 then the shortest rank-order prefix whose sum of w reaches top_p times the sum of the kept w;
+ *   - u = (h >> 8) 2^-24 with h = mix32(t ^ mix32(n ^ mix32(b ^ mix32(seed + 0x9e3779b9)))) (b = drawing, n = sample, t = step);
+ *     the first kept candidate in index order (vocab, then pointers) whose inclusive prefix sum of w exceeds u times the total;
+ *   - a pointer j writes the row's own token at j and attach j; the row's score gains logf(p) of the chosen candidate (untempered,
+ *     unfiltered: the model's log-likelihood of the sample); a row that has emitted END is frozen (PAD, attach -1, score + 0).
+ * Everything is read from device memory, the parameters included: the step captures into one hipGraph, and pa_decode_sample_set
+ * changes seed / temperature / top_k / top_p for the next steps without a new capture.  The same parameters give bitwise the same
+ * samples on every run.  top_k = 1 gives the greedy tokens up to each row's first END.  pa_decode_step_pair returns PA_EINVAL for a
+ * decode in sampling mode; pa_decode_begin returns the handle to greedy mode; pa_decode_beam_begin and pa_decode_sample_begin replace
+ * each other's mode (the last one called wins).  Vocabularies above 2048 entries: PA_ESHAPE.
+ *   pa_sample_params: seed; n_per_drawing = N; temperature > 0 and finite; top_k >= 0 (0 = off); 0 < top_p <= 1 (1 = off).
+ *   pa_decode_sample_ws_bytes: bytes of the sampling workspace for `rows` = B*N rows (the batch pa_decode_begin was given).
+ *   pa_decode_sample_begin: after pa_decode_begin, lays out `ws` (256-byte aligned, pa_decode_sample_ws_bytes bytes), writes the
+ *     parameters and zeroes the scores on `stream` (a kernel: no host-to-device copy).  PA_EINVAL for a decode that was not begun, N
+ *     outside [1, PA_SAMPLE_MAX], rows not a multiple of N, a bad temperature / top_k / top_p or a workspace too small.
+ *   pa_decode_sample_set: new parameters for a decode in sampling mode, on `stream`, same workspace, scores kept; N must be the N of
+ *     pa_decode_sample_begin.  PA_EINVAL otherwise, or for bad parameters.
+ *   pa_decode_sample_buffers: device pointer of scores f32 [rows] (cumulative log-probability of every sample).  Tokens / attach /
+ *     first_end of every sample are the pa_decode_buffers arrays. */
+typedef struct {
+    uint32_t seed;
+    int32_t n_per_drawing;
+    float temperature;
+    int32_t top_k;
+    float top_p;
+} pa_sample_params;
+#define PA_SAMPLE_MAX 64
+int64_t pa_decode_sample_ws_bytes(pa_model* m, int32_t rows);
+int pa_decode_sample_begin(pa_model* m, const pa_sample_params* p, void* ws, int64_t ws_bytes, void* stream);
+int pa_decode_sample_set(pa_model* m, const pa_sample_params* p, void* stream);
+int pa_decode_sample_buffers(pa_model* m, void** scores);
 /* Cross-attention of one decode step in absorbed ("multi-query") form (reference plankassembly/models.py:284-307, the
  * cross-attention of nn.TransformerDecoderLayer with K = W_k memory + b_k, V = W_v memory + b_v): per batch element and head
  * ctx[b][h][:] = sum_s softmax_s(qt[b][h] . mem[s]) mem[s] over the element's memory rows, where the caller has put

@@ -188,6 +188,10 @@ def lib():
             "pa_decode_beam_ws_bytes": (I64, [P, I, I, I, I]),
             "pa_decode_beam_begin": (I, [P, I, P, I64, P]),
             "pa_decode_beam_buffers": (I, [P, P, P, P]),
+            "pa_decode_sample_ws_bytes": (I64, [P, I]),
+            "pa_decode_sample_begin": (I, [P, P, P, I64, P]),
+            "pa_decode_sample_set": (I, [P, P, P]),
+            "pa_decode_sample_buffers": (I, [P, P]),
             "pa_dec_cross_mq": (I, [P, P, P, P, P, I, I, I, I, P]),
             "pa_dec_cross_mq32": (I, [P, P, P, P, P, I, I, I, I, P]),
             "pa_dec_cross_mq_ws": (I, [P, P, P, P, P, I, I, I, I, P, I64, P]),
@@ -199,6 +203,12 @@ def lib():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = res, args
     return _lib
+
+
+class SampleParams(C.Structure):
+    """include/plank_hip.h pa_sample_params."""
+    _fields_ = [("seed", C.c_uint32), ("n_per_drawing", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32),
+                ("top_p", C.c_float)]
 
 
 def check(rc: int, what: str):

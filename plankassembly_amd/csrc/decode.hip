@@ -9,6 +9,7 @@
 //   * sampling kernel fuses: pointer logits against the hidden-state cache, switch head, vocab /
 //     pointer softmax, gating, the 1e-6 pointer-mask fill, first-max argmax, pointer copy, END tracking
 //     (reference models.py:168-186 eval branch of _create_dist and 235-256 _sample).
+#include <cmath>
 #include <math.h>
 #include <new>
 #include <string.h>
@@ -70,6 +71,10 @@ struct DecodeLayout {
     float *bm_score = nullptr, *bm_clp = nullptr;
     int32_t *bm_fin = nullptr, *bm_parent = nullptr, *bm_ctok = nullptr, *bm_catt = nullptr;
     BeamCopy bm_copy{};                        // segment table of the history reorder (passed to the copy kernel by value)
+    // sampling (pa_decode_sample_begin; 0 = not sampling): N samples per drawing over the B rows, state in the caller's sample workspace
+    int sampleN = 0;
+    void* sm_prm = nullptr;                    // the device parameter block (SampleParamsDev)
+    float* sm_score = nullptr;
 };
 
 namespace {
@@ -590,6 +595,203 @@ __global__ __launch_bounds__(256) void dec_beam_init_kernel(float* scores, int32
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Sampling.  Rows are samples: row b * N + n is sample n of drawing b.  The step up to the heads is the greedy
+// step on B * N rows; its end is dec_sample_draw_kernel instead of dec_sample_kernel.  The parameters live in device memory
+// (pa_decode_sample_begin / _set write them with dec_sample_init_kernel), so new parameters need no new graph capture.
+struct SampleParamsDev { uint32_t seed; int32_t n; float temperature; int32_t top_k; float top_p; };
+constexpr int SAMPLE_MAX_V = 2048;                                  // vocabulary bound of the staged candidate arrays
+constexpr int SAMPLE_MAX_C = SAMPLE_MAX_V + MAX_T;
+
+__device__ __forceinline__ int block_sum_i(int v, int* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    __syncthreads();
+    return v;
+}
+__device__ __forceinline__ int block_min_i(int v, int* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = min(min(sh[0], sh[1]), min(sh[2], sh[3]));
+    __syncthreads();
+    return v;
+}
+
+// u in [0, 1) of sample n of drawing b at step t: a pure function of (seed, b, n, t) (tests/sample_reference.py restates it)
+__device__ __forceinline__ float sample_u(uint32_t seed, uint32_t b, uint32_t n, uint32_t t) {
+    const uint32_t h = mix32(t ^ mix32(n ^ mix32(b ^ mix32(seed + 0x9e3779b9u))));
+    return (float)(h >> 8) * 0x1p-24f;
+}
+
+// One block per row.  Writes the row's hidden state into hid_cache (as the greedy kernel does), stages the candidates' p of
+// row_dist_visit (vocab k at k, pointer j < t at V + j; the self pointer is no candidate) and their weights w in LDS, then:
+//   top-k  (k > 0): bisection on the p bit pattern (p >= 0: the bits order as the values) for the k-th largest p, then - if the
+//                   boundary p value is shared - on the index, for the smaller indices of that tie group (rank order: p
+//                   descending, ties to the smaller index);
+//   top-p  (< 1):   the same two bisections for the shortest rank-order prefix whose sum of w reaches top_p * (sum of kept w);
+//                   every probe is the same fixed-order block sum with the excluded terms zeroed - f32 addition of
+//                   non-negative terms is monotone, so the probes are monotone in the threshold;
+//   draw:           per-thread contiguous index ranges, an exclusive scan of the 256 partial sums, and the first kept candidate
+//                   whose inclusive prefix sum exceeds u * W (W = the prefix sum at the last candidate); none: the last kept one.
+// Integer block reductions and fixed-order float ones only: the same seed gives the same tokens and scores on every run.
+template <typename T>
+__global__ __launch_bounds__(256) void dec_sample_draw_kernel(const float* vlog, int ldv, const T* pfeat, const T* h, T* hid_cache,
+                                                              const float* sw_w, const float* sw_b, int64_t* tokens, int64_t* attach,
+                                                              int32_t* first_end, const int32_t* t_dev, int Tmax, int d, int V,
+                                                              int end_tok, int pad_tok, const SampleParamsDev* prm, float* scores) {
+    __shared__ float plog[MAX_T];
+    __shared__ float sp[SAMPLE_MAX_C], sw[SAMPLE_MAX_C];           // p and w of candidate i
+    __shared__ float sh[4], scan[4];
+    __shared__ int shi[4];
+    __shared__ float s_sw, s_W;
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t = *t_dev;
+    const T* hb = h + (int64_t)r * d;
+    const int64_t nb = gridDim.x;
+    T* cache = hid_cache + (int64_t)r * d;                          // [Tmax][rows][d], as in dec_sample_kernel
+    for (int c = tid; c < d; c += 256) cache[(int64_t)t * nb * d + c] = hb[c];
+    if (first_end[r] >= 0) {                                        // finished: frozen (uniform branch: one row per block)
+        if (tid == 0) { tokens[(int64_t)r * Tmax + t] = pad_tok; attach[(int64_t)r * Tmax + t] = -1; }
+        return;
+    }
+    const SampleParamsDev P = *prm;
+    const float* vr = vlog + (int64_t)r * ldv;
+    const RowDist rd = row_dist_prepare<T>(vr, V, pfeat + (int64_t)r * d, hb, cache, nb, t, d, sw_w, sw_b, plog, sh, &s_sw);
+    const int nc = t + 1 < 6 ? V : V + t;                           // candidates: vocab, then the pointers j < t
+    float pmax = -INFINITY;
+    row_dist_visit(rd, vr, V, plog, t, t, [&](float p, int i) { sp[i] = p; pmax = fmaxf(pmax, p); });
+    pmax = block_max(pmax, sh);                                     // (its barriers also publish sp)
+    const float tau = P.temperature, lpmax = logf(pmax);
+    for (int i = tid; i < nc; i += 256) {
+        const float p = sp[i];
+        sw[i] = !(p > 0.f) ? 0.f : (tau == 1.0f ? p / pmax : expf((logf(p) - lpmax) / tau));
+    }
+    __syncthreads();
+    const uint32_t hi0 = __float_as_uint(pmax) + 1;                 // no candidate's p bits reach this
+    auto pbits = [&](int i) { return __float_as_uint(sp[i]); };
+    // keep the rank-order prefix {p bits > th} + {p bits == th, index <= ith}: zero the others' w
+    auto cut = [&](uint32_t th, int ith) {
+        for (int i = tid; i < nc; i += 256) {
+            const uint32_t pb = pbits(i);
+            if (!(pb > th || (pb == th && i <= ith))) sw[i] = 0.f;
+        }
+        __syncthreads();
+    };
+    if (P.top_k > 0) {
+        auto count_ge = [&](uint32_t th) {                          // candidates with p > 0 and p bits >= th
+            int c = 0;
+            for (int i = tid; i < nc; i += 256) c += (sp[i] > 0.f && pbits(i) >= th) ? 1 : 0;
+            return block_sum_i(c, shi);
+        };
+        const int n_pos = count_ge(1u);
+        if (n_pos > P.top_k) {                                      // (otherwise top-k keeps every candidate)
+            uint32_t lo = 1u, hi = hi0;                             // count_ge(lo) >= k > count_ge(hi)
+            int c_hi = 0, c_lo = n_pos;
+            while (hi - lo > 1u) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                const int c = count_ge(mid);
+                if (c >= P.top_k) { lo = mid; c_lo = c; } else { hi = mid; c_hi = c; }
+            }
+            const int need = P.top_k - c_hi;                        // taken from the tie group p bits == lo, smaller indices first
+            int ith = nc - 1;
+            if (c_lo - c_hi > need) {
+                int ilo = -1, ihi = nc - 1;                         // count(group, index <= ilo) < need <= count(group, index <= ihi)
+                while (ihi - ilo > 1) {
+                    const int mid = ilo + (ihi - ilo) / 2;
+                    int c = 0;
+                    for (int i = tid; i <= mid; i += 256) c += (sp[i] > 0.f && pbits(i) == lo) ? 1 : 0;
+                    if (block_sum_i(c, shi) >= need) ihi = mid; else ilo = mid;
+                }
+                ith = ihi;
+            }
+            cut(lo, ith);
+        }
+    }
+    if (P.top_p < 1.0f) {
+        auto wsum = [&](uint32_t th, int ith) {                     // fixed-order sum of the kept w inside the prefix (th, ith)
+            float s = 0.f;
+            for (int i = tid; i < nc; i += 256) {
+                const uint32_t pb = pbits(i);
+                s += (pb > th || (pb == th && i <= ith)) ? sw[i] : 0.f;
+            }
+            return block_sum(s, sh);
+        };
+        const float target = P.top_p * wsum(0u, nc - 1);            // (> 0: the top candidate is kept with w = 1)
+        uint32_t lo = 0u, hi = hi0;                                 // wsum over p bits >= lo reaches target, over >= hi not
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (wsum(mid, nc - 1) >= target) lo = mid; else hi = mid;
+        }
+        int c = 0;
+        for (int i = tid; i < nc; i += 256) c += (pbits(i) == lo && sw[i] > 0.f) ? 1 : 0;
+        int ith = nc - 1;
+        if (block_sum_i(c, shi) > 1) {
+            int ilo = -1, ihi = nc - 1;                             // wsum(lo, ilo) < target <= wsum(lo, ihi)
+            while (ihi - ilo > 1) {
+                const int mid = ilo + (ihi - ilo) / 2;
+                if (wsum(lo, mid) >= target) ihi = mid; else ilo = mid;
+            }
+            ith = ihi;
+        }
+        cut(lo, ith);
+    }
+    // the draw: thread tid owns candidates [i0, i1) in index order
+    const int per = (nc + 255) / 256;
+    const int i0 = min(tid * per, nc), i1 = min(i0 + per, nc);
+    float part = 0.f;
+    for (int i = i0; i < i1; ++i) part += sw[i];
+    float inc = part;                                               // inclusive scan of the partial sums within the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float y = __shfl_up(inc, o);
+        if (lane >= o) inc += y;
+    }
+    if (lane == 63) scan[wave] = inc;
+    __syncthreads();
+    float off = 0.f;
+    for (int w = 0; w < wave; ++w) off += scan[w];
+    float excl = __shfl_up(inc, 1);
+    excl = lane == 0 ? off : off + excl;
+    if (i0 < nc && i1 == nc) s_W = excl + part;                     // W: the prefix sum at the last candidate
+    __syncthreads();
+    const float uW = sample_u(P.seed, (uint32_t)(r / P.n), (uint32_t)(r % P.n), (uint32_t)t) * s_W;
+    int pick = 0x7fffffff, last = -1;
+    {
+        float loc = 0.f;
+        for (int i = i0; i < i1; ++i) {
+            const float w = sw[i];
+            loc += w;
+            if (w > 0.f) {
+                last = i;
+                if (pick == 0x7fffffff && excl + loc > uW) pick = i;
+            }
+        }
+    }
+    pick = block_min_i(pick, shi);
+    if (pick == 0x7fffffff) pick = -block_min_i(-last, shi);       // rounding left no crossing: the last kept candidate
+    if (tid == 0) {
+        const int idx = pick < 0 ? 0 : pick;                        // (the top candidate always has w = 1: pick >= 0)
+        int64_t tok = idx, ptr = -1;
+        if (idx >= V) { ptr = idx - V; tok = tokens[(int64_t)r * Tmax + ptr]; }     // models.py:248-251
+        tokens[(int64_t)r * Tmax + t] = tok;
+        attach[(int64_t)r * Tmax + t] = ptr;
+        scores[r] += logf(sp[idx]);                                 // the untempered, unfiltered p
+        if (tok == end_tok) first_end[r] = t;
+    }
+}
+
+// The parameter block (by kernel argument: no host-to-device copy) and, at pa_decode_sample_begin, zero scores.
+__global__ __launch_bounds__(256) void dec_sample_init_kernel(SampleParamsDev* prm, SampleParamsDev p, float* scores, int rows) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *prm = p;
+    if (scores)
+        for (int r = blockIdx.x * 256 + threadIdx.x; r < rows; r += gridDim.x * 256) scores[r] = 0.f;
+}
+
 // last decoder layer's norm3 and decoder.norm back to back on the same rows, plus the bf16 copy of the result (f32-residual step):
 // one wave per row, two-pass statistics in registers - three launches (two LayerNorms, dec_cast_kernel) of the serial chain in one
 __global__ __launch_bounds__(256) void dec_tail_norm_kernel(float* hf, bf16* h, const float* z, const float* g3, const float* b3, float eps3,
@@ -887,6 +1089,19 @@ int beam_tail(pa_model* m, int ldv, hipStream_t s) {
     return 0;
 }
 
+// The end of a sampling step (in place of dec_sample_kernel): one draw per row.  The next step's input embedding is dec_embed_kernel at
+// the start of the next step, as for beam search - the same launch count as the greedy step.
+template <typename T>
+int sample_tail(pa_model* m, int ldv, hipStream_t s) {
+    const pa_model_cfg& c = m->cfg;
+    DecodeLayout* L = m->dec;
+    const int tl = m->tail();
+    PA_LAUNCH(dec_sample_draw_kernel<T>, dim3(L->B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h, (T*)L->hid_cache,
+              (const float*)m->pf[tl + T_SW_W], (const float*)m->pf[tl + T_SW_B], L->tokens, L->attach, L->first_end, L->t_dev, L->Tmax,
+              c.d_model, c.vocab, c.end, c.pad, (const SampleParamsDev*)L->sm_prm, L->sm_score);
+    return 0;
+}
+
 // One decode step in 2 * n_dec + 1 parts, each ending right after an attention launch (part 2i: self-attention of layer i,
 // part 2i + 1: its cross-attention; the last part is the tail: final norm, heads, sampling).  The attention launches are the
 // HBM-bound third of the step (they stream the K/V caches); everything between them is a chain of latency-bound launches on B
@@ -935,7 +1150,7 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
     // fence, ticket) costs the same again.  Fourth fusion of this decode step that does not pay.  The embedding
     // of step 0 is all zeros (models.py:114-123 with no token yet): pa_decode_begin clears x.
     static const int fuse_tail = getenv("PLANK_DECODE_FUSE_TAIL") ? atoi(getenv("PLANK_DECODE_FUSE_TAIL")) : 0;
-    const bool unfused = !fuse_tail || L->beamK > 0;          // (a beam step always takes the unfused tail: beam_tail)
+    const bool unfused = !fuse_tail || L->beamK > 0 || L->sampleN > 0;   // (beam and sampling steps always take the unfused tail)
     if (part == 0 && unfused) {
         const int g1 = (B * (d / 4) + 255) / 256;
         if (L->f32res)
@@ -1006,6 +1221,7 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
                 PA_LAUNCH(dec_cast_kernel, dim3((B * d / 4 + 255) / 256), dim3(256), 0, s, (bf16*)L->h, (const float*)L->hf, (int64_t)B * d / 4);
             RC(linear(m, L->h, PL(tl + T_PTR_W), PF(tl + T_PTR_B), L->pfeat, d, B, d, d, 0, nullptr, -1, st));
             if (L->beamK > 0) RC(beam_tail<T>(m, ldv, s));
+            else if (L->sampleN > 0) RC(sample_tail<T>(m, ldv, s));
             else
                 PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
                                    (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
@@ -1093,6 +1309,7 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
         RC(linear(m, L->h, PL(tl + T_VOCAB_W), PF(tl + T_VOCAB_B), L->vlog, ldv, B, c.vocab, d, 0, nullptr, PA_F32, st));
         RC(linear(m, L->h, PL(tl + T_PTR_W), PF(tl + T_PTR_B), L->pfeat, d, B, d, d, 0, nullptr, -1, st));
         if (L->beamK > 0) RC(beam_tail<T>(m, ldv, s));
+        else if (L->sampleN > 0) RC(sample_tail<T>(m, ldv, s));
         else
             PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
                                (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
@@ -1185,7 +1402,7 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
     const StepForm sf = step_form(c, B, S, Tmax);
     L->fold = md.fold; L->f32res = md.f32res; L->mq = md.mq;           // (what each is and where it was measured: decode_modes)
     L->mq_contract = sf.mq_contract; L->mq_self = sf.mq_self; L->mq_self_bf = sf.mq_self_bf;   // (step_form)
-    L->beamK = 0;                                               // greedy until pa_decode_beam_begin
+    L->beamK = 0; L->sampleN = 0;                               // greedy until pa_decode_beam_begin / pa_decode_sample_begin
     if (L->mq) {
         // absorbed cross-attention: the step reads the encoder output rows themselves - no K / V projection of the memory at all
         hipError_t hm = hipMemcpyAsync(L->mem, memory, (size_t)m->NE * d * e, hipMemcpyDeviceToDevice, s);
@@ -1281,6 +1498,7 @@ extern "C" int pa_decode_step_pair(pa_model* a, pa_model* b, void* stream_a, voi
     if (!a || !b || !a->dec || !b->dec || a->dec->B <= 0 || b->dec->B <= 0) return PA_EINVAL;
     if (a->cfg.n_dec != b->cfg.n_dec || a->cfg.dtype != b->cfg.dtype) return PA_EINVAL;
     if (a->dec->beamK > 0 || b->dec->beamK > 0) return PA_EINVAL;     // beams run as one lane
+    if (a->dec->sampleN > 0 || b->dec->sampleN > 0) return PA_EINVAL; // so does sampling
     const int n = 2 * a->cfg.n_dec;
     std::vector<hipEvent_t>& ev = a->dec->pair_ev;
     if ((int)ev.size() != 2 * n) {
@@ -1367,12 +1585,65 @@ extern "C" int pa_decode_beam_begin(pa_model* m, int32_t K, void* ws, int64_t ws
     const size_t need = beam_layout(L, (char*)ws, rows, K, scr);
     if ((int64_t)need > ws_bytes) { L->beamK = 0; return PA_EINVAL; }
     PA_LAUNCH(dec_beam_init_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, L->bm_score, L->bm_fin, L->bm_parent, rows, K);
-    L->beamK = K;
+    L->beamK = K; L->sampleN = 0;                               // (beam mode replaces sampling mode)
     return 0;
 }
 
 extern "C" int pa_decode_beam_buffers(pa_model* m, void** scores, void** parents, void** finished) {
     if (!m || !m->dec || m->dec->beamK <= 0 || !scores || !parents || !finished) return PA_EINVAL;
     *scores = m->dec->bm_score; *parents = m->dec->bm_parent; *finished = m->dec->bm_fin;
+    return 0;
+}
+
+// Sampling over a begun decode (include/plank_hip.h).
+namespace {
+// the parameter checks shared by pa_decode_sample_begin and pa_decode_sample_set
+bool sample_params_ok(const pa_sample_params* p, int rows) {
+    return p && p->n_per_drawing >= 1 && p->n_per_drawing <= PA_SAMPLE_MAX && rows % p->n_per_drawing == 0 &&
+           std::isfinite(p->temperature) && p->temperature > 0.f && p->top_k >= 0 && p->top_p > 0.f && p->top_p <= 1.f;
+}
+// sampling workspace: the parameter block, then scores f32 [rows]
+size_t sample_layout(DecodeLayout* L, char* base, int rows) {
+    Arena a{base, 0};
+    L->sm_prm = a.take(sizeof(SampleParamsDev));
+    L->sm_score = (float*)a.take((size_t)rows * 4);
+    return a.off;
+}
+int sample_write_params(DecodeLayout* L, const pa_sample_params* p, float* zero_scores, void* stream) {
+    const SampleParamsDev v{p->seed, p->n_per_drawing, p->temperature, p->top_k, p->top_p};
+    const int rows = L->B;
+    PA_LAUNCH(dec_sample_init_kernel, dim3(zero_scores ? (rows + 255) / 256 : 1), dim3(256), 0, (hipStream_t)stream,
+              (SampleParamsDev*)L->sm_prm, v, zero_scores, rows);
+    return 0;
+}
+}  // namespace
+
+extern "C" int64_t pa_decode_sample_ws_bytes(pa_model* m, int32_t rows) {
+    if (!m || rows <= 0) return PA_EINVAL;
+    DecodeLayout tmp;
+    return (int64_t)sample_layout(&tmp, nullptr, rows) + 256;
+}
+
+extern "C" int pa_decode_sample_begin(pa_model* m, const pa_sample_params* p, void* ws, int64_t ws_bytes, void* stream) {
+    if (!m || !m->dec || m->dec->B <= 0 || !ws || !sample_params_ok(p, m->dec->B)) return PA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return PA_EALIGN;
+    if (m->cfg.vocab > SAMPLE_MAX_V) return PA_ESHAPE;
+    DecodeLayout* L = m->dec;
+    DecodeLayout tmp;
+    if ((int64_t)sample_layout(&tmp, nullptr, L->B) > ws_bytes) return PA_EINVAL;
+    sample_layout(L, (char*)ws, L->B);
+    RC(sample_write_params(L, p, L->sm_score, stream));
+    L->sampleN = p->n_per_drawing; L->beamK = 0;                // (sampling mode replaces beam mode)
+    return 0;
+}
+
+extern "C" int pa_decode_sample_set(pa_model* m, const pa_sample_params* p, void* stream) {
+    if (!m || !m->dec || m->dec->sampleN <= 0 || !sample_params_ok(p, m->dec->B) || p->n_per_drawing != m->dec->sampleN) return PA_EINVAL;
+    return sample_write_params(m->dec, p, nullptr, stream);
+}
+
+extern "C" int pa_decode_sample_buffers(pa_model* m, void** scores) {
+    if (!m || !m->dec || m->dec->sampleN <= 0 || !scores) return PA_EINVAL;
+    *scores = m->dec->sm_score;
     return 0;
 }

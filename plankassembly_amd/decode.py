@@ -20,6 +20,7 @@ Linears is fewer launches per step, not a second stream.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import torch
@@ -319,16 +320,115 @@ class BeamDecoder(GreedyDecoder):
             if early_stop and bool((finished != 0).all().cpu()):
                 break
         self.last_steps = done
-        fe = first_end.view(B, K).long().cpu()
-        fin = (finished.view(B, K) != 0).cpu()
-        n = int(fe.max()) + 1 if bool(fin.all()) else Tmax
-        sc = scores.view(B, K).cpu()
-        lengths = torch.where(fe >= 0, fe + 1, torch.full_like(fe, Tmax))
-        key = sc / lengths.to(torch.float32) ** self.length_penalty if self.length_penalty != 0.0 else sc
-        order = torch.sort(key, dim=1, descending=True, stable=True).indices
-        dev = tokens.device
-        od = order.to(dev)
-        bt = tokens.view(B, K, Tmax)[:, :, :n].gather(1, od[:, :, None].expand(B, K, n)).contiguous()
-        ba = attach.view(B, K, Tmax)[:, :, :n].gather(1, od[:, :, None].expand(B, K, n)).contiguous()
-        return {"tokens": bt[:, 0].clone(), "attach": ba[:, 0].clone(), "beam_tokens": bt, "beam_attach": ba,
-                "scores": sc.gather(1, order), "finished": fin.gather(1, order), "lengths": lengths.gather(1, order)}
+        return _ranked("beam", tokens, attach, first_end, scores, finished != 0, B, K, Tmax, self.length_penalty)
+
+
+def _ranked(prefix, tokens, attach, first_end, scores, finished, B, K, Tmax, length_penalty):
+    """The final ranking shared by beam search and sampling: the K rows b*K + k of every drawing b ordered by score / len^alpha
+    descending, stable (len = first END + 1, or Tmax; alpha = 0 ranks by the raw score).  n = max over rows of first END + 1 once
+    every row has finished, else Tmax.  Returns the decoders' result dict, ``<prefix>_tokens`` / ``<prefix>_attach`` [B, K, n]."""
+    fe = first_end.view(B, K).long().cpu()
+    fin = finished.view(B, K).cpu()
+    n = int(fe.max()) + 1 if bool(fin.all()) else Tmax
+    sc = scores.view(B, K).cpu()
+    lengths = torch.where(fe >= 0, fe + 1, torch.full_like(fe, Tmax))
+    key = sc / lengths.to(torch.float32) ** length_penalty if length_penalty != 0.0 else sc
+    order = torch.sort(key, dim=1, descending=True, stable=True).indices
+    dev = tokens.device
+    od = order.to(dev)
+    bt = tokens.view(B, K, Tmax)[:, :, :n].gather(1, od[:, :, None].expand(B, K, n)).contiguous()
+    ba = attach.view(B, K, Tmax)[:, :, :n].gather(1, od[:, :, None].expand(B, K, n)).contiguous()
+    return {"tokens": bt[:, 0].clone(), "attach": ba[:, 0].clone(), f"{prefix}_tokens": bt, f"{prefix}_attach": ba,
+            "scores": sc.gather(1, order), "finished": fin.gather(1, order), "lengths": lengths.gather(1, order)}
+
+
+def sample_params(num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+    """Checked sampling parameters (include/plank_hip.h pa_sample_params): ValueError for a value the library would refuse."""
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+    if not is_int(num_samples) or not 1 <= num_samples <= 64:
+        raise ValueError(f"NUM_SAMPLES must be an integer in [1, 64], got {num_samples!r}")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"TEMPERATURE must be a finite number > 0, got {temperature!r}")
+    if not is_int(top_k) or top_k < 0:
+        raise ValueError(f"TOP_K must be an integer >= 0 (0 = off), got {top_k!r}")
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0 < top_p <= 1:
+        raise ValueError(f"TOP_P must be a number in (0, 1] (1 = off), got {top_p!r}")
+    if not is_int(seed) or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"SAMPLE_SEED must be an integer in [0, 2^32), got {seed!r}")
+    return L.SampleParams(seed, num_samples, float(temperature), top_k, float(top_p))
+
+
+class SampleDecoder(GreedyDecoder):
+    """Seeded top-k / top-p sampling over the KV-cached decode step (include/plank_hip.h pa_decode_sample_*).
+
+    The decode runs B*N sample rows - the encoder on the batch with every drawing repeated N times, row b*N + n is sample n of
+    drawing b - and each captured step ends with one random draw per row (dec_sample_draw_kernel) instead of the greedy arg-max.
+    The draw of sample n of drawing b at step t depends on (seed, b, n, t) only, so drawings are keyed by their position in the
+    batch.  Always one lane.  Every sample carries its score, the sum of log p of its tokens under the model (untempered,
+    unfiltered); ``length_penalty`` (alpha) ranks a drawing's samples by score / len^alpha.  top_k = 1 gives the greedy tokens up
+    to each row's first END (PAD / attach -1 after it)."""
+
+    def __init__(self, model, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0, use_graph=None,
+                 check_every=16, strict_graph=False):
+        super().__init__(model, use_graph=use_graph, check_every=check_every, strict_graph=strict_graph, lanes=1)
+        self.params = sample_params(num_samples, temperature, top_k, top_p, seed)
+        self.num_samples = int(num_samples)
+        self.length_penalty = float(length_penalty)
+        model._ensure_handle()
+        self._sws = None
+        self._skey = None
+
+    def begin(self, batch, max_len=None):
+        """Encoder on the repeated batch + pa_decode_begin + pa_decode_sample_begin.  Returns (rows = B*N, Tmax)."""
+        m, N, lib = self.model, self.num_samples, L.lib()
+        rep = _repeat_batch(batch, N)
+        if m.unpad:
+            rep = m.prepare_batch(rep, groups=False)
+        rows, Tmax = super().begin(rep, max_len)
+        ln = self._lanes[0]
+        need = int(lib.pa_decode_sample_ws_bytes(ln.h(), rows))
+        if need < 0:
+            L.check(need, "pa_decode_sample_ws_bytes")
+        if self._sws is None or self._sws.numel() < need + 256:
+            self._sws = torch.empty(need + 256, dtype=torch.uint8, device=m.flat_params.device)
+        base = (self._sws.data_ptr() + 255) // 256 * 256
+        L.check(lib.pa_decode_sample_begin(ln.h(), C.byref(self.params), C.c_void_p(base),
+                                           C.c_int64(self._sws.numel() - (base - self._sws.data_ptr())), L.stream()),
+                "pa_decode_sample_begin")
+        key = (self._sws.data_ptr(), N, ln.key)
+        if key != self._skey:
+            self._graph = None
+        self._skey = key
+        return rows, Tmax
+
+    def _scores(self, rows):
+        p = C.c_void_p()
+        L.check(L.lib().pa_decode_sample_buffers(self._lanes[0].h(), C.byref(p)), "pa_decode_sample_buffers")
+        off = p.value - self._sws.data_ptr()
+        return self._sws[off: off + rows * 4].view(torch.float32)
+
+    def run(self, batch, max_len=None, early_stop=True, seed=None):
+        """N samples per drawing.  ``seed``: this call's seed instead of the decoder's (pa_decode_sample_set: the captured step is
+        reused).  Returns a dict: ``tokens`` / ``attach`` int64 [B, n] (the best sample), ``sample_tokens`` / ``sample_attach``
+        int64 [B, N, n], ``scores`` f32 [B, N] (log-likelihood of each sample), ``finished`` bool [B, N] and ``lengths`` int64
+        [B, N], samples in final-ranking order.  n = max over rows of first END + 1 once every sample has finished, else Tmax -
+        the same with and without ``early_stop``."""
+        N = self.num_samples
+        rows, Tmax = self.begin(batch, max_len)
+        if seed is not None:
+            p = self.params
+            q = sample_params(N, p.temperature, p.top_k, p.top_p, seed)
+            L.check(L.lib().pa_decode_sample_set(self._lanes[0].h(), C.byref(q), L.stream()), "pa_decode_sample_set")
+        B = rows // N
+        tokens, attach, first_end = self._lanes[0].buffers(rows, Tmax)
+        scores = self._scores(rows)
+        done = 0
+        while done < Tmax:
+            k = min(self.check_every, Tmax - done) if early_stop else Tmax - done
+            self.steps(k)
+            done += k
+            if early_stop and bool((first_end >= 0).all().cpu()):
+                break
+        self.last_steps = done
+        return _ranked("sample", tokens, attach, first_end, scores, first_end >= 0, B, N, Tmax, self.length_penalty)

@@ -135,7 +135,8 @@ class PlankModel(nn.Module):
     def __init__(self, num_model=512, num_head=8, num_feedforward=1024, dropout=0.1, activation="relu",
                  normalize_before=True, num_encoder_layers=6, num_decoder_layers=6, num_view=3, num_type=2,
                  num_input_dof=4, num_output_dof=6, max_input_length=400, max_output_length=128, vocab_size=514,
-                 token=None, compute_dtype=None, beam_size=1, length_penalty=0.0):
+                 token=None, compute_dtype=None, beam_size=1, length_penalty=0.0, num_samples=0, temperature=1.0, top_k=0,
+                 top_p=1.0, sample_seed=0):
         super().__init__()
         # the reference hands the string to torch's Transformer layers (models.py:60-61,66-67), which take "relu" or "gelu"
         if activation not in ("relu", "gelu"):
@@ -151,6 +152,15 @@ class PlankModel(nn.Module):
             raise ValueError(f"BEAM_SIZE must be an integer in [1, 16], got {beam_size!r}")
         self.beam_size, self.length_penalty = int(beam_size), float(length_penalty)
         self._beam_decoders = {}
+        # or sampling with this many samples per drawing (decode.SampleDecoder, 1 <= N <= 64; 0 = off)
+        from .decode import sample_params
+        off = num_samples == 0 and isinstance(num_samples, int) and not isinstance(num_samples, bool)
+        sample_params(1 if off else num_samples, temperature, top_k, top_p, sample_seed)       # ValueError for a bad value
+        if not off and self.beam_size > 1:
+            raise ValueError(f"NUM_SAMPLES ({num_samples}) and BEAM_SIZE ({beam_size}) > 1 exclude each other")
+        self.num_samples = int(num_samples)
+        self.sample_cfg = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(sample_seed))
+        self._sample_decoders = {}
         self.compute_mode = compute_dtype                      # what the caller asked for
         self.split3 = compute_dtype == "x3"
         self.compute_dtype = "f32" if self.split3 else compute_dtype     # storage / kernel dtype: 'x3' is f32 with split products
@@ -310,6 +320,7 @@ class PlankModel(nn.Module):
         self._ws = None
         self._decoder = None
         self._beam_decoders = {}
+        self._sample_decoders = {}
         self._drop_x3_cache()
 
     def _drop_x3_cache(self):
@@ -856,9 +867,12 @@ class PlankModel(nn.Module):
 
     def eval_step(self, batch):
         """reference models.py:267-323: greedy autoregressive sampling (KV-cached HIP decode); beam search instead when the
-        model was built with beam_size > 1 (cfg.MODEL.BEAM_SIZE)."""
+        model was built with beam_size > 1 (cfg.MODEL.BEAM_SIZE), seeded sampling of num_samples per drawing, best returned,
+        when it was built with num_samples >= 1 (cfg.MODEL.NUM_SAMPLES)."""
         if self.beam_size > 1:
             return self.beam_search(batch, self.beam_size, self.length_penalty)
+        if self.num_samples >= 1:
+            return self.sample(batch, self.num_samples, length_penalty=self.length_penalty, **self.sample_cfg)
         from .decode import GreedyDecoder
         self._ensure_handle()
         self._refresh_shadow()
@@ -887,6 +901,23 @@ class PlankModel(nn.Module):
         r = dec.run(batch)
         out = self._eval_dict(batch, r["tokens"], r["attach"])
         out["scores"] = r["scores"]
+        return out
+
+    def sample(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0):
+        """Seeded sampling decode (decode.SampleDecoder): the eval_step dict of the best sample of every drawing (by score /
+        len^length_penalty) plus ``scores`` [B, N] (log-likelihood of every sample) and ``sample_tokens`` / ``sample_attach``
+        [B, N, n], samples in final-ranking order.  The same seed and batch give the same samples on every call."""
+        from .decode import SampleDecoder
+        self._ensure_handle()
+        self._refresh_shadow()
+        key = (int(num_samples), float(temperature), int(top_k), float(top_p), float(length_penalty))
+        dec = self._sample_decoders.get(key)
+        if dec is None:
+            dec = self._sample_decoders[key] = SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, length_penalty)
+        r = dec.run(batch, seed=seed)
+        out = self._eval_dict(batch, r["tokens"], r["attach"])
+        out["scores"] = r["scores"]
+        out["sample_tokens"], out["sample_attach"] = r["sample_tokens"], r["sample_attach"]
         return out
 
     def forward(self, batch):
@@ -920,8 +951,11 @@ class PlankModel(nn.Module):
 
 def build_model(cfg):
     """reference models.py:333-343.  Optional ``cfg.MODEL.COMPUTE_DTYPE`` ('f32' | 'bf16' | 'x3'), ``cfg.MODEL.BEAM_SIZE``
-    (eval_step decodes by beam search with this many beams, 1 <= K <= 16; absent or 1: greedy) and ``cfg.MODEL.LENGTH_PENALTY``
-    (alpha of the final beam ranking score / len^alpha, default 0)."""
+    (eval_step decodes by beam search with this many beams, 1 <= K <= 16; absent or 1: greedy), ``cfg.MODEL.LENGTH_PENALTY``
+    (alpha of the final beam / sample ranking score / len^alpha, default 0) and the sampling keys ``cfg.MODEL.NUM_SAMPLES``
+    (eval_step samples this many per drawing and returns the best, 1 <= N <= 64; absent or 0: greedy), ``TEMPERATURE`` (> 0,
+    default 1), ``TOP_K`` (>= 0, 0 = off), ``TOP_P`` (in (0, 1], 1 = off) and ``SAMPLE_SEED`` (default 0).  A bad value, or
+    NUM_SAMPLES >= 1 together with BEAM_SIZE > 1, raises ValueError."""
     model_cfg = cfg.MODEL
 
     def opt(key, default=None):
@@ -934,4 +968,6 @@ def build_model(cfg):
         cfg.MODEL.ACTIVATION, cfg.MODEL.NORMALIZE_BEFORE, cfg.MODEL.NUM_ENCODER_LAYERS,
         cfg.MODEL.NUM_DECODER_LAYERS, cfg.DATA.NUM_VIEW, cfg.DATA.NUM_TYPE, cfg.DATA.NUM_INPUT_DOF,
         cfg.DATA.NUM_OUTPUT_DOF, cfg.DATA.MAX_INPUT_LENGTH, cfg.DATA.MAX_OUTPUT_LENGTH, cfg.DATA.VOCAB_SIZE,
-        cfg.TOKEN, compute_dtype=dtype, beam_size=opt("BEAM_SIZE", 1), length_penalty=float(opt("LENGTH_PENALTY", 0.0)))
+        cfg.TOKEN, compute_dtype=dtype, beam_size=opt("BEAM_SIZE", 1), length_penalty=float(opt("LENGTH_PENALTY", 0.0)),
+        num_samples=opt("NUM_SAMPLES", 0), temperature=opt("TEMPERATURE", 1.0), top_k=opt("TOP_K", 0), top_p=opt("TOP_P", 1.0),
+        sample_seed=opt("SAMPLE_SEED", 0))
