@@ -663,6 +663,40 @@ int64_t pa_decode_sample_ws_bytes(pa_model* m, int32_t rows);
 int pa_decode_sample_begin(pa_model* m, const pa_sample_params* p, void* ws, int64_t ws_bytes, void* stream);
 int pa_decode_sample_set(pa_model* m, const pa_sample_params* p, void* stream);
 int pa_decode_sample_buffers(pa_model* m, void** scores);
+/* Forced prefixes over the same step, in any mode: completion of a partly known sequence, and - with every
+ * position forced - the log-likelihood of a sequence the caller brings.  The prefix table gives per row r (a row of the batch
+ * pa_decode_begin was given: a sample, a beam, a batch element) a length plen[r], 0 <= plen <= Tmax, and for t < plen[r] the forced
+ * candidate: ptok[r][t] with patt[r][t] = -1 for the vocab entry ptok, or patt = j >= 0 for the pointer candidate j.  At step t a row
+ * with t < plen[r] ("forced row"):
+ *   - writes its hidden state and computes the distribution exactly as a free row does;
+ *   - takes the forced candidate without arg-max, ranking or draw (the random number of sampling stays a function of (seed, b, n, t));
+ *     token ptok and attach patt are written, a pointer writing the row's own token at patt as a free step does (the caller makes sure
+ *     that ptok agrees with it);
+ *   - stores lp = logf(p of the forced candidate) in prefix_lp[r][t] and adds it, in step order, to prefix_score[r] - and in beam and
+ *     sampling mode to the mode's own score, which stays the log-likelihood of the whole sequence;
+ *   - a forced END sets first_end (beam mode: finished) as a free END does.  In beam and sampling mode a row frozen by END ignores the
+ *     rest of its prefix.  Greedy mode freezes nothing: positions after END are still forced and stored in prefix_lp up to plen, but
+ *     prefix_score stops after the row's first END (END's own lp included);
+ *   - a forced candidate that does not exist at its step (a pointer with patt >= t or at t < 5, a token outside the vocabulary) scores
+ *     -inf and reads nothing out of bounds; such a token is written as PAD.
+ * Beam mode: the K rows of a drawing must carry the same prefix.  A forced live row has the single candidate at rank 0, so during the
+ * prefix beam 0 carries the hypothesis and beams 1 .. K-1 stay at -inf, as at t = 0 without a prefix; the first free step fans out
+ * from beam 0, and prefix_score / prefix_lp of the drawing are those of its row b*K.  Rows with t >= plen[r] behave exactly as without
+ * a table, in the same step.  Without pa_decode_prefix_begin every mode launches the kernels it launched before and gives the same
+ * bits; a step with a table takes the unfused tail.  Everything is read from device memory: the step captures into one hipGraph and
+ * a new table needs no new capture.  pa_decode_begin clears the prefix; pa_decode_step_pair returns PA_EINVAL with a prefix set.
+ *   pa_decode_prefix_ws_bytes: bytes of the prefix workspace for `rows` rows and Tmax positions.
+ *   pa_decode_prefix_begin: after pa_decode_begin and after any pa_decode_beam_begin / pa_decode_sample_begin.  plen int32 [rows],
+ *     ptok / patt int64 [rows][Tmax] are DEVICE pointers (positions t >= plen[r] are not read by the step); a kernel on `stream` copies
+ *     them into `ws` (256-byte aligned, pa_decode_prefix_ws_bytes bytes; plen clamped to [0, Tmax]) and zeroes prefix_score /
+ *     prefix_lp - no host-to-device copy.  PA_EINVAL for a decode that was not begun, a null table or a workspace too small.
+ *   pa_decode_prefix_set: a new table for a decode with a prefix, on `stream`, same workspace (prefix_score / prefix_lp zeroed again).
+ *   pa_decode_prefix_buffers: device pointers of prefix_score f32 [rows] and prefix_lp f32 [rows][Tmax] (0 where nothing was forced). */
+int64_t pa_decode_prefix_ws_bytes(pa_model* m, int32_t rows, int32_t Tmax);
+int pa_decode_prefix_begin(pa_model* m, const int32_t* plen, const int64_t* ptok, const int64_t* patt, void* ws, int64_t ws_bytes,
+                           void* stream);
+int pa_decode_prefix_set(pa_model* m, const int32_t* plen, const int64_t* ptok, const int64_t* patt, void* stream);
+int pa_decode_prefix_buffers(pa_model* m, void** prefix_score, void** prefix_lp);
 /* Cross-attention of one decode step in absorbed ("multi-query") form (reference plankassembly/models.py:284-307, the
  * cross-attention of nn.TransformerDecoderLayer with K = W_k memory + b_k, V = W_v memory + b_v): per batch element and head
  * ctx[b][h][:] = sum_s softmax_s(qt[b][h] . mem[s]) mem[s] over the element's memory rows, where the caller has put

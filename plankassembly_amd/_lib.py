@@ -192,6 +192,10 @@ def lib():
             "pa_decode_sample_begin": (I, [P, P, P, I64, P]),
             "pa_decode_sample_set": (I, [P, P, P]),
             "pa_decode_sample_buffers": (I, [P, P]),
+            "pa_decode_prefix_ws_bytes": (I64, [P, I, I]),
+            "pa_decode_prefix_begin": (I, [P, P, P, P, P, I64, P]),
+            "pa_decode_prefix_set": (I, [P, P, P, P, P]),
+            "pa_decode_prefix_buffers": (I, [P, P, P]),
             "pa_dec_cross_mq": (I, [P, P, P, P, P, I, I, I, I, P]),
             "pa_dec_cross_mq32": (I, [P, P, P, P, P, I, I, I, I, P]),
             "pa_dec_cross_mq_ws": (I, [P, P, P, P, P, I, I, I, I, P, I64, P]),

@@ -75,6 +75,10 @@ struct DecodeLayout {
     int sampleN = 0;
     void* sm_prm = nullptr;                    // the device parameter block (SampleParamsDev)
     float* sm_score = nullptr;
+    // forced prefixes (pa_decode_prefix_begin; any mode): the table and its scores in the caller's prefix workspace
+    bool px_on = false;
+    int32_t *px_len = nullptr, *px_tok = nullptr, *px_att = nullptr;   // [rows], [rows][Tmax], [rows][Tmax]
+    float *px_score = nullptr, *px_lp = nullptr;                      // [rows], [rows][Tmax]
 };
 
 namespace {
@@ -367,20 +371,63 @@ __device__ __forceinline__ RowDist row_dist_prepare(const float* vr, int V, cons
     return r;
 }
 
+// p of one candidate, the expressions row_dist_visit hands out and the forced path (section 14) evaluates for its one index: the vocab
+// softmax term (un-gated; sz >= 6 multiplies it by 1 - prob) and the pointer j of step i = t.
+__device__ __forceinline__ float dist_p_vocab(const RowDist& r, const float* vr, int k) { return expf(vr[k] - r.vmax) / r.vsum; }
+__device__ __forceinline__ float dist_p_ptr(const RowDist& r, const float* plog, int i, int j) {
+    float val = 1e-6f;                                                // models.py:183-184 fill after gating
+    if (ptr_allowed(i, j)) val = (j < i) ? (expf(plog[j] - r.pmax) / r.psum) * r.prob : 0.f;
+    return val;
+}
+
 template <typename F>
 __device__ __forceinline__ void row_dist_visit(const RowDist& r, const float* vr, int V, const float* plog, int t, int jend, F&& f) {
     const int tid = threadIdx.x, sz = t + 1, i = t;
     if (sz < 6) {                                                     // models.py:172-173: un-gated vocab softmax
-        for (int k = tid; k < V; k += 256) f(expf(vr[k] - r.vmax) / r.vsum, k);
+        for (int k = tid; k < V; k += 256) f(dist_p_vocab(r, vr, k), k);
         return;
     }
     const float gate_v = 1.0f - r.prob;
-    for (int k = tid; k < V; k += 256) f((expf(vr[k] - r.vmax) / r.vsum) * gate_v, k);
-    for (int j = tid; j < jend; j += 256) {
-        float val = 1e-6f;                                            // models.py:183-184 fill after gating
-        if (ptr_allowed(i, j)) val = (j < i) ? (expf(plog[j] - r.pmax) / r.psum) * r.prob : 0.f;
-        f(val, V + j);
+    for (int k = tid; k < V; k += 256) f(dist_p_vocab(r, vr, k) * gate_v, k);
+    for (int j = tid; j < jend; j += 256) f(dist_p_ptr(r, plog, i, j), V + j);
+}
+
+// The p row_dist_visit hands out for the single index idx (vocab k as k, pointer j as V + j).  An index that is no candidate at step
+// t - outside the table, a pointer while sz < 6, a pointer j >= t - has p = 0 and reads nothing.
+__device__ __forceinline__ float row_dist_at(const RowDist& r, const float* vr, int V, const float* plog, int t, int idx) {
+    if (idx < 0) return 0.f;
+    if (t + 1 < 6) return idx < V ? dist_p_vocab(r, vr, idx) : 0.f;
+    if (idx < V) return dist_p_vocab(r, vr, idx) * (1.0f - r.prob);
+    const int j = idx - V;
+    return j < t ? dist_p_ptr(r, plog, t, j) : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Forced prefixes.  The prefix arena of pa_decode_prefix_begin: per row r a length plen[r] and the forced
+// candidate of every position t < plen[r] - ptok, and patt = -1 for the vocab entry ptok or j >= 0 for the pointer candidate j -
+// plus what the forced positions scored: lp [rows][Tmax] per token and score [rows], their sum in step order.  plen = NULL: no table;
+// the end-of-step kernels then do exactly what they did without this argument.  A row is forced or free per step (t < plen[r]) - one
+// row per block, so the branch is uniform - and a forced row takes its candidate without arg-max, ranking or draw.
+struct PrefixDev { const int32_t* plen; const int32_t* ptok; const int32_t* patt; float* score; float* lp; int32_t pad_tok; int32_t pad_; };
+
+// The forced candidate of row r at step t: lp = logf(p) of its index with row_dist_visit's own arithmetic, the token and attach to
+// write (a pointer takes the row's own token at patt, models.py:248-251).  A candidate that does not exist at this step scores -inf
+// and reads nothing out of bounds; a token outside the vocabulary is written as PAD, so that the next step's embedding stays inside
+// its table.  One thread calls it, after row_dist_prepare; it also stores lp in the per-token buffer.
+struct Forced { float lp; int64_t tok, att; };
+__device__ __forceinline__ Forced forced_candidate(const PrefixDev& px, int r, int t, int Tmax, const RowDist& rd, const float* vr, int V,
+                                                   const float* plog, const int64_t* tokens) {
+    const int ft = px.ptok[(int64_t)r * Tmax + t], fa = px.patt[(int64_t)r * Tmax + t];
+    const bool tok_ok = ft >= 0 && ft < V;
+    Forced f{-INFINITY, tok_ok ? ft : px.pad_tok, -1};
+    if (fa < 0) {
+        if (tok_ok) f.lp = logf(row_dist_at(rd, vr, V, plog, t, ft));
+    } else if (fa < t && t + 1 >= 6) {
+        f.att = fa; f.tok = tokens[(int64_t)r * Tmax + fa];
+        f.lp = logf(row_dist_at(rd, vr, V, plog, t, V + fa));
     }
+    px.lp[(int64_t)r * Tmax + t] = f.lp;
+    return f;
 }
 
 template <typename T>
@@ -392,7 +439,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int 
                                                          // embedding of this row and the step counter - what dec_embed_kernel and
                                                          // dec_advance_kernel did as two more launches of the serial chain
                                                          int fuse, float* x32, T* xT, bf16* x_lp, const float* value,
-                                                         const float* coord, const float* pos, int dof) {
+                                                         const float* coord, const float* pos, int dof, const PrefixDev px) {
     __shared__ float plog[MAX_T];
     __shared__ long long s_tok;
     __shared__ float sh[4];
@@ -408,6 +455,18 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int 
     for (int c = tid; c < d; c += 256) cache[(int64_t)t * nb * d + c] = hb[c];
     const float* vr = vlog + (int64_t)b * ldv;
     const RowDist rd = row_dist_prepare<T>(vr, V, pfeat + (int64_t)b * d, hb, cache, nb, t, d, sw_w, sw_b, plog, sh, &s_sw);
+    if (px.plen && t < px.plen[b]) {                                // forced row (section 14; the host passes fuse = 0 with a table)
+        if (tid == 0) {
+            const Forced f = forced_candidate(px, b, t, Tmax, rd, vr, V, plog, tokens);
+            tokens[(int64_t)b * Tmax + t] = f.tok;
+            attach[(int64_t)b * Tmax + t] = f.att;
+            if (first_end[b] < 0) {                                 // greedy freezes nothing: forced and scored up to plen, summed up to END
+                px.score[b] += f.lp;
+                if (f.tok == end_tok) first_end[b] = t;
+            }
+        }
+        return;
+    }
     ArgMax best{-INFINITY, 0x7fffffff};
     row_dist_visit(rd, vr, V, plog, t, sz, [&](float p, int k) { best = better(best, ArgMax{p, k}); });
     // block arg-max (first maximum)
@@ -462,7 +521,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void dec_beam_cand_kernel(const float* vlog, int ldv, const T* pfeat, const T* h, T* hid_cache,
                                                             const float* sw_w, const float* sw_b, const int64_t* tokens,
                                                             const int32_t* finished, const int32_t* t_dev, int Tmax, int d, int V,
-                                                            int K, int pad_tok, float* cand_lp, int32_t* cand_tok, int32_t* cand_att) {
+                                                            int K, int pad_tok, float* cand_lp, int32_t* cand_tok, int32_t* cand_att,
+                                                            const PrefixDev px) {
     __shared__ float plog[MAX_T];
     __shared__ float sh[4];
     __shared__ ArgMax sha[4];
@@ -482,6 +542,14 @@ __global__ __launch_bounds__(256) void dec_beam_cand_kernel(const float* vlog, i
     }
     const float* vr = vlog + (int64_t)b * ldv;
     const RowDist rd = row_dist_prepare<T>(vr, V, pfeat + (int64_t)b * d, hb, cache, nb, t, d, sw_w, sw_b, plog, sh, &s_sw);
+    if (px.plen && t < px.plen[b]) {                                // forced live row (section 14): the one candidate at rank 0
+        if (tid == 0) {
+            const Forced f = forced_candidate(px, b, t, Tmax, rd, vr, V, plog, tokens);
+            lp[0] = f.lp; ct[0] = (int32_t)f.tok; ca[0] = (int32_t)f.att;
+            px.score[b] += f.lp;
+        } else if (tid < K) { lp[tid] = -INFINITY; ct[tid] = pad_tok; ca[tid] = -1; }
+        return;
+    }
     ArgMax prev{INFINITY, -1};
     for (int k = 0; k < K; ++k) {
         ArgMax best{-INFINITY, 0x7fffffff};
@@ -643,7 +711,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const float* vlog, int ldv, const T* pfeat, const T* h, T* hid_cache,
                                                               const float* sw_w, const float* sw_b, int64_t* tokens, int64_t* attach,
                                                               int32_t* first_end, const int32_t* t_dev, int Tmax, int d, int V,
-                                                              int end_tok, int pad_tok, const SampleParamsDev* prm, float* scores) {
+                                                              int end_tok, int pad_tok, const SampleParamsDev* prm, float* scores,
+                                                              const PrefixDev px) {
     __shared__ float plog[MAX_T];
     __shared__ float sp[SAMPLE_MAX_C], sw[SAMPLE_MAX_C];           // p and w of candidate i
     __shared__ float sh[4], scan[4];
@@ -662,6 +731,17 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const float* vlog,
     const SampleParamsDev P = *prm;
     const float* vr = vlog + (int64_t)r * ldv;
     const RowDist rd = row_dist_prepare<T>(vr, V, pfeat + (int64_t)r * d, hb, cache, nb, t, d, sw_w, sw_b, plog, sh, &s_sw);
+    if (px.plen && t < px.plen[r]) {                                // forced live row (section 14): no draw, u is not consumed
+        if (tid == 0) {
+            const Forced f = forced_candidate(px, r, t, Tmax, rd, vr, V, plog, tokens);
+            tokens[(int64_t)r * Tmax + t] = f.tok;
+            attach[(int64_t)r * Tmax + t] = f.att;
+            scores[r] += f.lp;
+            px.score[r] += f.lp;
+            if (f.tok == end_tok) first_end[r] = t;
+        }
+        return;
+    }
     const int nc = t + 1 < 6 ? V : V + t;                           // candidates: vocab, then the pointers j < t
     float pmax = -INFINITY;
     row_dist_visit(rd, vr, V, plog, t, t, [&](float p, int i) { sp[i] = p; pmax = fmaxf(pmax, p); });
@@ -790,6 +870,21 @@ __global__ __launch_bounds__(256) void dec_sample_init_kernel(SampleParamsDev* p
     if (blockIdx.x == 0 && threadIdx.x == 0) *prm = p;
     if (scores)
         for (int r = blockIdx.x * 256 + threadIdx.x; r < rows; r += gridDim.x * 256) scores[r] = 0.f;
+}
+
+// The prefix arena from the caller's table (device memory; section 14): lengths clamped to [0, Tmax], tokens and pointers narrowed to
+// int32 (a value that does not fit becomes one that is no candidate), prefix_score and prefix_lp zero.
+__global__ __launch_bounds__(256) void dec_prefix_init_kernel(int32_t* len, int32_t* tok, int32_t* att, float* score, float* lp,
+                                                              const int32_t* plen, const int64_t* ptok, const int64_t* patt, int rows,
+                                                              int Tmax) {
+    const int64_t n = (int64_t)rows * Tmax;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t tk = ptok[i], at = patt[i];
+        tok[i] = (tk < 0 || tk > 0x7fffffff) ? -1 : (int32_t)tk;
+        att[i] = at < 0 ? -1 : (at > 0x7fffffff ? 0x7fffffff : (int32_t)at);
+        lp[i] = 0.f;
+        if (i < rows) { len[i] = min(max(plen[i], 0), Tmax); score[i] = 0.f; }
+    }
 }
 
 // last decoder layer's norm3 and decoder.norm back to back on the same rows, plus the bf16 copy of the result (f32-residual step):
@@ -1069,6 +1164,13 @@ size_t beam_layout(DecodeLayout* L, char* base, int rows, int K, int64_t scr_row
     return a.off;
 }
 
+// The prefix table as the end-of-step kernels take it (no table: all NULL, and the kernels do what they did without it).
+PrefixDev prefix_arg(const pa_model* m) {
+    const DecodeLayout* L = m->dec;
+    if (!L->px_on) return PrefixDev{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    return PrefixDev{L->px_len, L->px_tok, L->px_att, L->px_score, L->px_lp, m->cfg.pad, 0};
+}
+
 // The end of a beam step (in place of dec_sample_kernel): candidates, merge, history reorder.  The next step's input embedding is
 // dec_embed_kernel at the start of the next step (it reads the token at t - 1 of each row, i.e. of the new beam).
 template <typename T>
@@ -1078,7 +1180,7 @@ int beam_tail(pa_model* m, int ldv, hipStream_t s) {
     const int rows = L->B, K = L->beamK, tl = m->tail();
     PA_LAUNCH(dec_beam_cand_kernel<T>, dim3(rows), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h, (T*)L->hid_cache,
               (const float*)m->pf[tl + T_SW_W], (const float*)m->pf[tl + T_SW_B], L->tokens, L->bm_fin, L->t_dev, L->Tmax, c.d_model, c.vocab,
-              K, c.pad, L->bm_clp, L->bm_ctok, L->bm_catt);
+              K, c.pad, L->bm_clp, L->bm_ctok, L->bm_catt, prefix_arg(m));
     PA_LAUNCH(dec_beam_merge_kernel, dim3(rows / K), dim3(256), 0, s, L->bm_clp, L->bm_ctok, L->bm_catt, L->bm_score, L->bm_fin,
               L->first_end, L->bm_parent, L->tokens, L->attach, L->t_dev, L->Tmax, K, c.end);
     if (K > 1) {
@@ -1098,7 +1200,7 @@ int sample_tail(pa_model* m, int ldv, hipStream_t s) {
     const int tl = m->tail();
     PA_LAUNCH(dec_sample_draw_kernel<T>, dim3(L->B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h, (T*)L->hid_cache,
               (const float*)m->pf[tl + T_SW_W], (const float*)m->pf[tl + T_SW_B], L->tokens, L->attach, L->first_end, L->t_dev, L->Tmax,
-              c.d_model, c.vocab, c.end, c.pad, (const SampleParamsDev*)L->sm_prm, L->sm_score);
+              c.d_model, c.vocab, c.end, c.pad, (const SampleParamsDev*)L->sm_prm, L->sm_score, prefix_arg(m));
     return 0;
 }
 
@@ -1150,7 +1252,8 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
     // fence, ticket) costs the same again.  Fourth fusion of this decode step that does not pay.  The embedding
     // of step 0 is all zeros (models.py:114-123 with no token yet): pa_decode_begin clears x.
     static const int fuse_tail = getenv("PLANK_DECODE_FUSE_TAIL") ? atoi(getenv("PLANK_DECODE_FUSE_TAIL")) : 0;
-    const bool unfused = !fuse_tail || L->beamK > 0 || L->sampleN > 0;   // (beam and sampling steps always take the unfused tail)
+    const bool unfused = !fuse_tail || L->beamK > 0 || L->sampleN > 0 || L->px_on;   // (beam, sampling and prefix steps always take the unfused tail)
+    const int fuse_greedy = unfused ? 0 : fuse_tail;
     if (part == 0 && unfused) {
         const int g1 = (B * (d / 4) + 255) / 256;
         if (L->f32res)
@@ -1225,8 +1328,8 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
             else
                 PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
                                    (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
-                                   c.vocab, c.end, fuse_tail, (float*)L->x, (T*)nullptr, (bf16*)L->xb, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
-                                   c.out_dof);
+                                   c.vocab, c.end, fuse_greedy, (float*)L->x, (T*)nullptr, (bf16*)L->xb, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
+                                   c.out_dof, prefix_arg(m));
             if (unfused) PA_LAUNCH(dec_advance_kernel, dim3(1), dim3(64), 0, s, L->t_dev);
             return 0;
         }
@@ -1313,8 +1416,8 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
         else
             PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
                                (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
-                               c.vocab, c.end, fuse_tail, (float*)nullptr, (T*)L->x, (bf16*)nullptr, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
-                               c.out_dof);
+                               c.vocab, c.end, fuse_greedy, (float*)nullptr, (T*)L->x, (bf16*)nullptr, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
+                               c.out_dof, prefix_arg(m));
         if (unfused) PA_LAUNCH(dec_advance_kernel, dim3(1), dim3(64), 0, s, L->t_dev);
         return 0;
     }
@@ -1403,6 +1506,7 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
     L->fold = md.fold; L->f32res = md.f32res; L->mq = md.mq;           // (what each is and where it was measured: decode_modes)
     L->mq_contract = sf.mq_contract; L->mq_self = sf.mq_self; L->mq_self_bf = sf.mq_self_bf;   // (step_form)
     L->beamK = 0; L->sampleN = 0;                               // greedy until pa_decode_beam_begin / pa_decode_sample_begin
+    L->px_on = false;                                           // and no forced prefix until pa_decode_prefix_begin
     if (L->mq) {
         // absorbed cross-attention: the step reads the encoder output rows themselves - no K / V projection of the memory at all
         hipError_t hm = hipMemcpyAsync(L->mem, memory, (size_t)m->NE * d * e, hipMemcpyDeviceToDevice, s);
@@ -1499,6 +1603,7 @@ extern "C" int pa_decode_step_pair(pa_model* a, pa_model* b, void* stream_a, voi
     if (a->cfg.n_dec != b->cfg.n_dec || a->cfg.dtype != b->cfg.dtype) return PA_EINVAL;
     if (a->dec->beamK > 0 || b->dec->beamK > 0) return PA_EINVAL;     // beams run as one lane
     if (a->dec->sampleN > 0 || b->dec->sampleN > 0) return PA_EINVAL; // so does sampling
+    if (a->dec->px_on || b->dec->px_on) return PA_EINVAL;             // and a decode with a forced prefix
     const int n = 2 * a->cfg.n_dec;
     std::vector<hipEvent_t>& ev = a->dec->pair_ev;
     if ((int)ev.size() != 2 * n) {
@@ -1645,5 +1750,53 @@ extern "C" int pa_decode_sample_set(pa_model* m, const pa_sample_params* p, void
 extern "C" int pa_decode_sample_buffers(pa_model* m, void** scores) {
     if (!m || !m->dec || m->dec->sampleN <= 0 || !scores) return PA_EINVAL;
     *scores = m->dec->sm_score;
+    return 0;
+}
+
+// Forced prefixes over a begun decode, in any mode (include/plank_hip.h).
+namespace {
+// prefix workspace: plen int32 [rows], ptok / patt int32 [rows][Tmax], prefix_score f32 [rows], prefix_lp f32 [rows][Tmax]
+size_t prefix_layout(DecodeLayout* L, char* base, int rows, int Tmax) {
+    Arena a{base, 0};
+    L->px_len = (int32_t*)a.take((size_t)rows * 4);
+    L->px_tok = (int32_t*)a.take((size_t)rows * Tmax * 4); L->px_att = (int32_t*)a.take((size_t)rows * Tmax * 4);
+    L->px_score = (float*)a.take((size_t)rows * 4); L->px_lp = (float*)a.take((size_t)rows * Tmax * 4);
+    return a.off;
+}
+int prefix_write(DecodeLayout* L, const int32_t* plen, const int64_t* ptok, const int64_t* patt, void* stream) {
+    const int64_t n = (int64_t)L->B * L->Tmax;
+    PA_LAUNCH(dec_prefix_init_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+              L->px_len, L->px_tok, L->px_att, L->px_score, L->px_lp, plen, ptok, patt, L->B, L->Tmax);
+    return 0;
+}
+}  // namespace
+
+extern "C" int64_t pa_decode_prefix_ws_bytes(pa_model* m, int32_t rows, int32_t Tmax) {
+    if (!m || rows <= 0 || Tmax <= 0 || Tmax > MAX_T) return PA_EINVAL;
+    DecodeLayout tmp;
+    return (int64_t)prefix_layout(&tmp, nullptr, rows, Tmax) + 256;
+}
+
+extern "C" int pa_decode_prefix_begin(pa_model* m, const int32_t* plen, const int64_t* ptok, const int64_t* patt, void* ws,
+                                      int64_t ws_bytes, void* stream) {
+    if (!m || !m->dec || m->dec->B <= 0 || !plen || !ptok || !patt || !ws) return PA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return PA_EALIGN;
+    DecodeLayout* L = m->dec;
+    DecodeLayout tmp;
+    if ((int64_t)prefix_layout(&tmp, nullptr, L->B, L->Tmax) > ws_bytes) return PA_EINVAL;
+    prefix_layout(L, (char*)ws, L->B, L->Tmax);
+    RC(prefix_write(L, plen, ptok, patt, stream));
+    L->px_on = true;
+    return 0;
+}
+
+extern "C" int pa_decode_prefix_set(pa_model* m, const int32_t* plen, const int64_t* ptok, const int64_t* patt, void* stream) {
+    if (!m || !m->dec || !m->dec->px_on || !plen || !ptok || !patt) return PA_EINVAL;
+    return prefix_write(m->dec, plen, ptok, patt, stream);
+}
+
+extern "C" int pa_decode_prefix_buffers(pa_model* m, void** prefix_score, void** prefix_lp) {
+    if (!m || !m->dec || !m->dec->px_on || !prefix_score || !prefix_lp) return PA_EINVAL;
+    *prefix_score = m->dec->px_score; *prefix_lp = m->dec->px_lp;
     return 0;
 }

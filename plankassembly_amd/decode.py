@@ -105,6 +105,59 @@ def _split_batch(batch, lo, hi):
     return out
 
 
+def prefix_table(prefix, B, Tmax, vocab_size, end_token, pad_token, strict=True):
+    """Checked forced prefix (include/plank_hip.h pa_decode_prefix_begin) of a batch of B drawings.
+
+    ``prefix``: a dict with ``tokens`` int [B, P], optional ``attach`` int [B, P] (-1 = the vocab entry ``tokens``, j >= 0 = the
+    pointer candidate j; default all -1) and optional ``lengths`` int [B] (default: up to and including the row's first END, else up
+    to its first PAD, else P).  Returns CPU tensors (lengths int64 [B], tokens int64 [B, Tmax], attach int64 [B, Tmax]), zero /
+    -1 beyond each row's length.  ValueError for P > Tmax, a length outside [0, P], a token outside [0, vocab_size) inside a row's
+    length and - ``strict``, what the decoders ask for - a pointer with attach[t] >= t, a pointer at t < 5, an attach below -1, or
+    tokens[t] != tokens[attach[t]].  ``strict=False`` (PlankModel.score) leaves those to the kernel, which scores a candidate that
+    does not exist as -inf."""
+    if not isinstance(prefix, dict) or "tokens" not in prefix:
+        raise ValueError("prefix must be a dict with 'tokens' [B, P] (and optional 'attach', 'lengths')")
+    tok = torch.as_tensor(prefix["tokens"]).detach().cpu().long()
+    if tok.dim() != 2 or tok.shape[0] != B:
+        raise ValueError(f"prefix tokens must be [B = {B}, P], got {tuple(tok.shape)}")
+    P = tok.shape[1]
+    if P > Tmax:
+        raise ValueError(f"prefix of {P} positions is longer than the decode (Tmax {Tmax})")
+    att = prefix.get("attach")
+    att = torch.full_like(tok, -1) if att is None else torch.as_tensor(att).detach().cpu().long()
+    if att.shape != tok.shape:
+        raise ValueError(f"prefix attach must have the shape of tokens {tuple(tok.shape)}, got {tuple(att.shape)}")
+    pos = torch.arange(P)[None, :].expand(B, P)
+    lengths = prefix.get("lengths")
+    if lengths is None:
+        def first(mask, add):
+            return torch.where(mask.any(1), mask.long().argmax(1) + add, torch.full((B,), P))
+        lengths = torch.minimum(first(tok == end_token, 1), first(tok == pad_token, 0)) if P > 0 else torch.zeros(B, dtype=torch.long)
+    else:
+        lengths = torch.as_tensor(lengths).detach().cpu().long().reshape(-1)
+        if lengths.shape[0] != B or bool(((lengths < 0) | (lengths > P)).any()):
+            raise ValueError(f"prefix lengths must be [B = {B}] values in [0, P = {P}]")
+    inside = pos < lengths[:, None]
+    if bool((inside & ((tok < 0) | (tok >= vocab_size))).any()):
+        raise ValueError(f"prefix token outside [0, {vocab_size}) inside a row's length")
+    if strict:
+        ptr = inside & (att != -1)
+        if bool((inside & (att < -1)).any()):
+            raise ValueError("prefix attach below -1")
+        if bool((ptr & (att >= pos)).any()):
+            raise ValueError("prefix pointer with attach[t] >= t")
+        if bool((ptr & (pos < 5)).any()):
+            raise ValueError("prefix pointer at t < 5 (the first plank has no pointer candidates)")
+        src = tok.gather(1, att.clamp(0, max(P - 1, 0))) if P > 0 else tok
+        if bool((ptr & (src != tok)).any()):
+            raise ValueError("prefix tokens[t] != tokens[attach[t]] at a pointer")
+    ptok = torch.zeros(B, Tmax, dtype=torch.long)
+    patt = torch.full((B, Tmax), -1, dtype=torch.long)
+    ptok[:, :P] = torch.where(inside, tok, torch.zeros_like(tok))
+    patt[:, :P] = torch.where(inside, att, torch.full_like(att, -1))
+    return lengths, ptok, patt
+
+
 class GreedyDecoder:
     def __init__(self, model, use_graph=None, check_every=16, strict_graph=False, lanes=None):
         """``strict_graph``: a failed hipGraph capture raises instead of falling back to eager launches (benchmarks must
@@ -127,6 +180,11 @@ class GreedyDecoder:
         self._side = None
         self._active = 0
         self.last_steps = 0
+        self._pws = None                                   # prefix workspace (pa_decode_prefix_begin) and what the graph captured of it
+        self._pkey = None
+        self._pkeep = None
+        self.last_prefix_scores = None
+        self.last_prefix_logprobs = None
 
     def __del__(self):
         try:
@@ -210,23 +268,85 @@ class GreedyDecoder:
             else:
                 self._step_eager()
 
-    def run(self, batch, max_len=None, early_stop=True):
+    def _check_prefix(self, prefix, batch, max_len, strict=True):
+        """The checked table of ``prefix`` (prefix_table) for this batch, before anything is launched; None without a prefix."""
+        if prefix is None:
+            return None
+        if self.max_lanes >= 2:
+            raise ValueError("a forced prefix needs the one-lane decode (lanes=1)")
+        m = self.model
+        return prefix_table(prefix, batch["input_value"].shape[0], int(max_len or m.max_output_length), m.vocab_size, m.token.END,
+                            m.token.PAD, strict=strict)
+
+    def _prefix_begin(self, table, repeat, rows, Tmax):
+        """pa_decode_prefix_begin on the begun decode (every drawing's prefix repeated ``repeat`` times, _repeat_batch's layout), or -
+        table None - nothing.  A captured step is dropped when the prefix appears, goes away or its workspace moves; a new table on
+        the same workspace replays the same graph.  Returns (prefix_score [rows], prefix_lp [rows, Tmax]) device views, or None."""
+        key = None
+        if table is not None:
+            lib, ln = L.lib(), self._lanes[0]
+            dev = self.model.flat_params.device
+            lengths, ptok, patt = table
+            plen = lengths.repeat_interleave(repeat).to(torch.int32).to(dev)
+            ptok = ptok.repeat_interleave(repeat, dim=0).contiguous().to(dev)
+            patt = patt.repeat_interleave(repeat, dim=0).contiguous().to(dev)
+            assert plen.shape[0] == rows and ptok.shape == (rows, Tmax)
+            need = int(lib.pa_decode_prefix_ws_bytes(ln.h(), rows, Tmax))
+            if need < 0:
+                L.check(need, "pa_decode_prefix_ws_bytes")
+            if self._pws is None or self._pws.numel() < need + 256:
+                self._pws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+            base = (self._pws.data_ptr() + 255) // 256 * 256
+            L.check(lib.pa_decode_prefix_begin(ln.h(), L.ptr(plen), L.ptr(ptok), L.ptr(patt), C.c_void_p(base),
+                                               C.c_int64(self._pws.numel() - (base - self._pws.data_ptr())), L.stream()),
+                    "pa_decode_prefix_begin")
+            self._pkeep = (plen, ptok, patt)
+            key = self._pws.data_ptr()
+        if key != self._pkey:
+            self._graph = None
+        self._pkey = key
+        if table is None:
+            return None
+        ptrs = [C.c_void_p() for _ in range(2)]
+        L.check(L.lib().pa_decode_prefix_buffers(self._lanes[0].h(), *[C.byref(p) for p in ptrs]), "pa_decode_prefix_buffers")
+        o0, o1 = ptrs[0].value - self._pws.data_ptr(), ptrs[1].value - self._pws.data_ptr()
+        return (self._pws[o0: o0 + rows * 4].view(torch.float32),
+                self._pws[o1: o1 + rows * Tmax * 4].view(torch.float32).view(rows, Tmax))
+
+    def run(self, batch, max_len=None, early_stop=True, prefix=None, max_steps=None, strict_prefix=True):
         """Full greedy decode.  Returns (samples int64 [B, n], attach int64 [B, n]) with the
-        reference's early-stop length n."""
+        reference's early-stop length n.
+
+        ``prefix`` (prefix_table): every row's first ``lengths`` positions are forced instead of taken by
+        arg-max, and scored: ``last_prefix_scores`` f32 [B] (sum of log p over the forced positions up to and including the row's
+        first END) and ``last_prefix_logprobs`` f32 [B, n] (per position, 0 where nothing was forced) are left on the decoder as CPU
+        tensors (None after a run without a prefix).  The loop never stops before max(lengths) steps and n is at least that.
+        ``max_steps``: run exactly this many steps (n = max_steps; the scorer).  ``strict_prefix=False``: prefix_table's
+        non-strict checks (the scorer)."""
+        table = self._check_prefix(prefix, batch, max_len, strict_prefix)
         B, Tmax = self.begin(batch, max_len)
+        pbuf = self._prefix_begin(table, 1, B, Tmax)
         bufs = [self._lanes[i].buffers(hi - lo, Tmax) for i, (lo, hi) in enumerate(self._bounds)]
+        min_steps = int(table[0].max()) if table is not None and B > 0 else 0
         done = 0
         n = Tmax
-        while done < Tmax:
+        if max_steps is not None:
+            n = max(0, min(int(max_steps), Tmax))
+            self.steps(n)
+            done = n
+        while max_steps is None and done < Tmax:
             k = min(self.check_every, Tmax - done) if early_stop else Tmax - done
             self.steps(k)
             done += k
-            if early_stop:
+            if early_stop and done >= min_steps:
                 fe = torch.cat([b[2] for b in bufs]).cpu()
                 if bool((fe >= 0).all()):
-                    n = int(fe.max()) + 1
+                    n = max(int(fe.max()) + 1, min_steps)
                     break
         self.last_steps = done
+        self.last_prefix_scores = self.last_prefix_logprobs = None
+        if pbuf is not None:
+            self.last_prefix_scores, self.last_prefix_logprobs = pbuf[0].cpu(), pbuf[1][:, :n].cpu()
         tokens = torch.cat([b[0][:, :n] for b in bufs]) if len(bufs) > 1 else bufs[0][0][:, :n].clone()
         attach = torch.cat([b[1][:, :n] for b in bufs]) if len(bufs) > 1 else bufs[0][1][:, :n].clone()
         return tokens, attach
@@ -302,13 +422,20 @@ class BeamDecoder(GreedyDecoder):
 
         return view(ptrs[0], torch.float32), view(ptrs[1], torch.int32), view(ptrs[2], torch.int32)
 
-    def run(self, batch, max_len=None, early_stop=True):
+    def run(self, batch, max_len=None, early_stop=True, prefix=None):
         """Full beam search.  Returns a dict: ``tokens`` / ``attach`` int64 [B, n] (the best beam), ``beam_tokens`` /
         ``beam_attach`` int64 [B, K, n], ``scores`` f32 [B, K] (cumulative log-probability), ``finished`` bool [B, K] and
         ``lengths`` int64 [B, K], beams in final-ranking order.  n = max over rows of first END + 1 once every beam has
-        finished, else Tmax - the same with and without ``early_stop``."""
+        finished, else Tmax - the same with and without ``early_stop``.
+
+        ``prefix`` (prefix_table, per drawing; DESIGN.md section 14): the first ``lengths`` positions of every drawing are forced;
+        beam 0 carries the hypothesis through them and the first free step fans out.  The dict always has ``prefix_scores`` f32
+        [B, K] and ``prefix_logprobs`` f32 [B, K, n] - the log-probabilities of the forced positions, which every beam of a drawing
+        shares; zeros without a prefix.  ``scores`` stay the log-likelihood of the whole sequence."""
         K = self.beam_size
+        table = self._check_prefix(prefix, batch, max_len)
         rows, Tmax = self.begin(batch, max_len)
+        pbuf = self._prefix_begin(table, K, rows, Tmax)
         B = rows // K
         tokens, attach, first_end = self._lanes[0].buffers(rows, Tmax)
         scores, _, finished = self._beam_buffers(rows)
@@ -320,13 +447,17 @@ class BeamDecoder(GreedyDecoder):
             if early_stop and bool((finished != 0).all().cpu()):
                 break
         self.last_steps = done
-        return _ranked("beam", tokens, attach, first_end, scores, finished != 0, B, K, Tmax, self.length_penalty)
+        if pbuf is not None:                                          # the drawing's forced positions were scored on its row b*K
+            pbuf = (pbuf[0].view(B, K)[:, :1].expand(B, K).reshape(rows),
+                    pbuf[1].view(B, K, Tmax)[:, :1].expand(B, K, Tmax).reshape(rows, Tmax))
+        return _ranked("beam", tokens, attach, first_end, scores, finished != 0, B, K, Tmax, self.length_penalty, pbuf)
 
 
-def _ranked(prefix, tokens, attach, first_end, scores, finished, B, K, Tmax, length_penalty):
+def _ranked(prefix, tokens, attach, first_end, scores, finished, B, K, Tmax, length_penalty, pbuf=None):
     """The final ranking shared by beam search and sampling: the K rows b*K + k of every drawing b ordered by score / len^alpha
     descending, stable (len = first END + 1, or Tmax; alpha = 0 ranks by the raw score).  n = max over rows of first END + 1 once
-    every row has finished, else Tmax.  Returns the decoders' result dict, ``<prefix>_tokens`` / ``<prefix>_attach`` [B, K, n]."""
+    every row has finished, else Tmax.  Returns the decoders' result dict, ``<prefix>_tokens`` / ``<prefix>_attach`` [B, K, n];
+    ``pbuf``: the rows' (prefix_score [rows], prefix_lp [rows, Tmax]) of a forced prefix, ranked alike (None: zeros)."""
     fe = first_end.view(B, K).long().cpu()
     fin = finished.view(B, K).cpu()
     n = int(fe.max()) + 1 if bool(fin.all()) else Tmax
@@ -338,8 +469,14 @@ def _ranked(prefix, tokens, attach, first_end, scores, finished, B, K, Tmax, len
     od = order.to(dev)
     bt = tokens.view(B, K, Tmax)[:, :, :n].gather(1, od[:, :, None].expand(B, K, n)).contiguous()
     ba = attach.view(B, K, Tmax)[:, :, :n].gather(1, od[:, :, None].expand(B, K, n)).contiguous()
+    if pbuf is None:
+        ps, pl = torch.zeros(B, K), torch.zeros(B, K, n)
+    else:
+        ps = pbuf[0].view(B, K).cpu().gather(1, order)
+        pl = pbuf[1].view(B, K, Tmax)[:, :, :n].cpu().gather(1, order[:, :, None].expand(B, K, n))
     return {"tokens": bt[:, 0].clone(), "attach": ba[:, 0].clone(), f"{prefix}_tokens": bt, f"{prefix}_attach": ba,
-            "scores": sc.gather(1, order), "finished": fin.gather(1, order), "lengths": lengths.gather(1, order)}
+            "scores": sc.gather(1, order), "finished": fin.gather(1, order), "lengths": lengths.gather(1, order),
+            "prefix_scores": ps, "prefix_logprobs": pl}
 
 
 def sample_params(num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0):
@@ -408,14 +545,21 @@ class SampleDecoder(GreedyDecoder):
         off = p.value - self._sws.data_ptr()
         return self._sws[off: off + rows * 4].view(torch.float32)
 
-    def run(self, batch, max_len=None, early_stop=True, seed=None):
+    def run(self, batch, max_len=None, early_stop=True, seed=None, prefix=None):
         """N samples per drawing.  ``seed``: this call's seed instead of the decoder's (pa_decode_sample_set: the captured step is
         reused).  Returns a dict: ``tokens`` / ``attach`` int64 [B, n] (the best sample), ``sample_tokens`` / ``sample_attach``
         int64 [B, N, n], ``scores`` f32 [B, N] (log-likelihood of each sample), ``finished`` bool [B, N] and ``lengths`` int64
         [B, N], samples in final-ranking order.  n = max over rows of first END + 1 once every sample has finished, else Tmax -
-        the same with and without ``early_stop``."""
+        the same with and without ``early_stop``.
+
+        ``prefix`` (prefix_table, per drawing): the first ``lengths`` positions of every sample of a drawing
+        are forced (no draw; the random numbers of the free steps are those of a run without a prefix).  The dict always has
+        ``prefix_scores`` f32 [B, N] and ``prefix_logprobs`` f32 [B, N, n], zeros without a prefix; ``scores`` stay the
+        log-likelihood of the whole sample."""
         N = self.num_samples
+        table = self._check_prefix(prefix, batch, max_len)
         rows, Tmax = self.begin(batch, max_len)
+        pbuf = self._prefix_begin(table, N, rows, Tmax)
         if seed is not None:
             p = self.params
             q = sample_params(N, p.temperature, p.top_k, p.top_p, seed)
@@ -431,4 +575,4 @@ class SampleDecoder(GreedyDecoder):
             if early_stop and bool((first_end >= 0).all().cpu()):
                 break
         self.last_steps = done
-        return _ranked("sample", tokens, attach, first_end, scores, first_end >= 0, B, N, Tmax, self.length_penalty)
+        return _ranked("sample", tokens, attach, first_end, scores, first_end >= 0, B, N, Tmax, self.length_penalty, pbuf)

@@ -865,21 +865,77 @@ class PlankModel(nn.Module):
         num_plank = len(valid_seq) // self.num_output_dof
         return valid_seq[:num_plank * self.num_output_dof].reshape(-1, self.num_output_dof)
 
-    def eval_step(self, batch):
+    def eval_step(self, batch, prefix=None):
         """reference models.py:267-323: greedy autoregressive sampling (KV-cached HIP decode); beam search instead when the
         model was built with beam_size > 1 (cfg.MODEL.BEAM_SIZE), seeded sampling of num_samples per drawing, best returned,
-        when it was built with num_samples >= 1 (cfg.MODEL.NUM_SAMPLES)."""
+        when it was built with num_samples >= 1 (cfg.MODEL.NUM_SAMPLES).
+
+        ``prefix`` (decode.prefix_table): a dict ``tokens`` [B, P], optional ``attach`` / ``lengths`` - the
+        decode continues these positions instead of starting from the empty sequence; the dict then also carries
+        ``prefix_scores`` / ``prefix_logprobs``, the model's log-probabilities of the forced positions."""
         if self.beam_size > 1:
-            return self.beam_search(batch, self.beam_size, self.length_penalty)
+            return self.beam_search(batch, self.beam_size, self.length_penalty, prefix=prefix)
         if self.num_samples >= 1:
-            return self.sample(batch, self.num_samples, length_penalty=self.length_penalty, **self.sample_cfg)
+            return self.sample(batch, self.num_samples, length_penalty=self.length_penalty, prefix=prefix, **self.sample_cfg)
         from .decode import GreedyDecoder
         self._ensure_handle()
         self._refresh_shadow()
         if self._decoder is None:
             self._decoder = GreedyDecoder(self)
-        output, attach = self._decoder.run(batch)
-        return self._eval_dict(batch, output, attach)
+        output, attach = self._decoder.run(batch, prefix=prefix)
+        out = self._eval_dict(batch, output, attach)
+        if prefix is not None:
+            out["prefix_scores"], out["prefix_logprobs"] = self._decoder.last_prefix_scores, self._decoder.last_prefix_logprobs
+        return out
+
+    def score(self, batch, tokens=None, attach=None, lengths=None):
+        """Log-likelihood of given sequences under the model, on the GPU: the greedy decode step with every position forced
+        (DESIGN.md section 14), one sequence per batch row, max(lengths) steps.
+
+        ``tokens`` int [B, P] defaults to ``batch["output_value"]``; ``lengths`` [B] to each row up to and including its first END
+        (PAD never counts).  ``attach`` int [B, P]: -1 scores position t as the vocab entry ``tokens[t]``, j >= 0 as the pointer to
+        position j.  Not given, the pointers come from ``batch["output_label"]`` when ``tokens`` is not given either and the batch
+        has it (label >= vocab_size means attach = label - vocab_size, the batch contract of data.py); otherwise every position is
+        scored as a vocab entry.  Only what could read out of bounds is refused (ValueError: P above the decode length, a token
+        outside the vocabulary): a pointer the eval branch disallows scores the reference's 1e-6 fill, one that is no candidate
+        at its step (attach >= t, or t < 5) scores -inf.  Returns ``scores`` f32 [B] (sum over the row's positions up to and
+        including its first END), ``logprobs`` f32 [B, n] (per position, n = max(lengths); 0 beyond a row's length) and
+        ``lengths`` int64 [B]."""
+        from .decode import GreedyDecoder
+        self._ensure_handle()
+        self._refresh_shadow()
+        if tokens is None:
+            tokens = batch["output_value"]
+            if attach is None and "output_label" in batch:
+                label = batch["output_label"]
+                attach = torch.where(label >= self.vocab_size, label - self.vocab_size, torch.full_like(label, -1))
+        prefix = {"tokens": tokens}
+        if attach is not None:
+            prefix["attach"] = attach
+        if lengths is not None:
+            prefix["lengths"] = lengths
+        if self._decoder is None:
+            self._decoder = GreedyDecoder(self)
+        dec = self._decoder
+        table = dec._check_prefix(prefix, batch, None, strict=False)
+        n = int(table[0].max()) if table[0].numel() else 0
+        dec.run(batch, early_stop=False, prefix=prefix, max_steps=n, strict_prefix=False)
+        return {"scores": dec.last_prefix_scores, "logprobs": dec.last_prefix_logprobs, "lengths": table[0]}
+
+    def complete(self, batch, num_planks):
+        """eval_step continuing the first ``num_planks`` planks of the ground truth: the first num_planks * num_output_dof
+        positions of ``batch["output_value"]``, clipped before each row's END, with the pointers of ``batch["output_label"]`` when
+        the batch has it, as the forced prefix."""
+        tok = batch["output_value"]
+        P = min(int(num_planks) * self.num_output_dof, tok.shape[1])
+        tok = tok[:, :P].detach().cpu()
+        stop = (tok == self.token.END) | (tok == self.token.PAD)
+        lengths = torch.where(stop.any(1), stop.long().argmax(1), torch.full((tok.shape[0],), P))
+        prefix = {"tokens": tok, "lengths": lengths}
+        if "output_label" in batch:
+            label = batch["output_label"][:, :P].detach().cpu()
+            prefix["attach"] = torch.where(label >= self.vocab_size, label - self.vocab_size, torch.full_like(label, -1))
+        return self.eval_step(batch, prefix=prefix)
 
     def _eval_dict(self, batch, output, attach):
         predicts, groundtruths = [], []
@@ -888,9 +944,9 @@ class PlankModel(nn.Module):
             groundtruths.append(self.parse_sequence(batch["output_value"][i].to(output.device)))
         return {"samples": output, "attach": attach, "predicts": predicts, "groundtruths": groundtruths}
 
-    def beam_search(self, batch, beam_size, length_penalty=0.0):
+    def beam_search(self, batch, beam_size, length_penalty=0.0, prefix=None):
         """Beam-search decode (decode.BeamDecoder): the eval_step dict of the best beam of every drawing plus ``scores``
-        [B, K], the cumulative log-probabilities of all beams in final-ranking order."""
+        [B, K], the cumulative log-probabilities of all beams in final-ranking order.  ``prefix``: as in eval_step, per drawing."""
         from .decode import BeamDecoder
         self._ensure_handle()
         self._refresh_shadow()
@@ -898,15 +954,18 @@ class PlankModel(nn.Module):
         dec = self._beam_decoders.get(key)
         if dec is None:
             dec = self._beam_decoders[key] = BeamDecoder(self, beam_size, length_penalty)
-        r = dec.run(batch)
+        r = dec.run(batch, prefix=prefix)
         out = self._eval_dict(batch, r["tokens"], r["attach"])
         out["scores"] = r["scores"]
+        if prefix is not None:
+            out["prefix_scores"], out["prefix_logprobs"] = r["prefix_scores"], r["prefix_logprobs"]
         return out
 
-    def sample(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0):
+    def sample(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0, prefix=None):
         """Seeded sampling decode (decode.SampleDecoder): the eval_step dict of the best sample of every drawing (by score /
         len^length_penalty) plus ``scores`` [B, N] (log-likelihood of every sample) and ``sample_tokens`` / ``sample_attach``
-        [B, N, n], samples in final-ranking order.  The same seed and batch give the same samples on every call."""
+        [B, N, n], samples in final-ranking order.  The same seed and batch give the same samples on every call.  ``prefix``: as in
+        eval_step, per drawing."""
         from .decode import SampleDecoder
         self._ensure_handle()
         self._refresh_shadow()
@@ -914,9 +973,11 @@ class PlankModel(nn.Module):
         dec = self._sample_decoders.get(key)
         if dec is None:
             dec = self._sample_decoders[key] = SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, length_penalty)
-        r = dec.run(batch, seed=seed)
+        r = dec.run(batch, seed=seed, prefix=prefix)
         out = self._eval_dict(batch, r["tokens"], r["attach"])
         out["scores"] = r["scores"]
+        if prefix is not None:
+            out["prefix_scores"], out["prefix_logprobs"] = r["prefix_scores"], r["prefix_logprobs"]
         out["sample_tokens"], out["sample_attach"] = r["sample_tokens"], r["sample_attach"]
         return out
 
