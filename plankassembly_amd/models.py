@@ -919,8 +919,21 @@ class PlankModel(nn.Module):
         dec = self._decoder
         table = dec._check_prefix(prefix, batch, None, strict=False)
         n = int(table[0].max()) if table[0].numel() else 0
-        dec.run(batch, early_stop=False, prefix=prefix, max_steps=n, strict_prefix=False)
-        return {"scores": dec.last_prefix_scores, "logprobs": dec.last_prefix_logprobs, "lengths": table[0]}
+        written, _ = dec.run(batch, early_stop=False, prefix=prefix, max_steps=n, strict_prefix=False)
+        # The step's own prefix_score is an f32 running sum: at |score| ~ 1 600 (128 positions of the headline model) one addition
+        # rounds by up to 6e-5 and the sum drifted 4e-4 from float64 while every per-token value was within 1.1e-5
+        # (tests/test_decode_logprob_gpu.py case A).  The scorer therefore sums the per-token values itself, in float64, over the
+        # positions the step summed - each row's length, up to and including the first END it wrote - and rounds once.
+        logprobs = dec.last_prefix_logprobs
+        written = written.cpu()
+        pos = torch.arange(n)[None, :]
+        is_end = written == self.token.END
+        stop = torch.full((written.shape[0],), n)
+        if n > 0:                                      # (argmax over an empty dimension raises: every length 0 scores 0)
+            stop = torch.where(is_end.any(1), is_end.long().argmax(1), stop)
+        summed = (pos < table[0][:, None]) & (pos <= stop[:, None])
+        scores = torch.where(summed, logprobs.double(), torch.zeros((), dtype=torch.float64)).sum(1).float()
+        return {"scores": scores, "logprobs": logprobs, "lengths": table[0]}
 
     def complete(self, batch, num_planks):
         """eval_step continuing the first ``num_planks`` planks of the ground truth: the first num_planks * num_output_dof

@@ -10,7 +10,17 @@ path has them:
   'f32_resid'     residual stream, LayerNorm inputs / outputs and the hidden cache stay f32 (rounded only as a GEMM operand)
   'f32_heads'     = f32_resid + vocabulary / pointer / switch heads evaluated in f32 on the f32 hidden rows
 Reported per mode: exact-prefix agreement with the f32 tokens, rows exact to the end, and the oracle's relative top-2 margin
-at every row's first flip.      python tests/bf16_decode_sim.py [batch] [steps]"""
+at every row's first flip.      python tests/bf16_decode_sim.py [batch] [steps]
+
+Teacher-forced mode (``run(..., forced=(tokens, attach))``; tests/decode_logprob_cases.py): every step takes the given candidate
+instead of ``O.sample`` and records ``log dist[candidate]`` in float64 - the yardstick of what bf16 rounding may cost the device's
+per-token log-probabilities (tests/test_decode_logprob_gpu.py).  The two ``step_*`` modes restate the two step forms of
+csrc/decode.hip rounding for rounding; the modes above them stay as profiles/r04 measured them:
+  'step_f32res'   the `f32res` form (bf16, d_model 512, at most 512 rows): the encoder is the bf16 forward (every tensor between
+                  kernels bf16); inside the step the residual stream and the LayerNorms are f32; the vocabulary head is f32 on the
+                  f32 hidden row with the f32 master weight; the pointer head, the hidden cache AND the switch gate read the bf16
+                  copy of the hidden row, and the pointer feature row is itself stored in bf16
+  'step_all_bf16' every other bf16 step: 'all_bf16' plus the pointer feature row stored in bf16"""
 import math
 import os
 import sys
@@ -40,11 +50,17 @@ MODES = {   # name: (encoder, decoder residual path, vocabulary head, pointer he
     "enc_f32+dec_resid+heads": ("f32", "resid", "f32", "f32"),
     "enc_f32+dec_resid+vocab_f32": ("f32", "resid", "f32", "bf16"),
     "dec_resid+vocab_f32": ("bf16", "resid", "f32", "bf16"),
+    # the device's two bf16 step forms as csrc/decode.hip rounds them (fifth entry: the pointer feature row and the row the switch
+    # gate reads are bf16, as dec_sample_kernel<bf16> takes them)
+    "step_f32res": ("bf16", "resid", "f32", "bf16", "bf16"),
+    "step_all_bf16": ("bf16", "bf16", "bf16", "bf16", "bf16"),
 }
 
 
-def run(sd, cfg, batch, mode, steps):
-    enc_mode, dec_mode, vocab_mode, ptr_mode = MODES[mode]
+def run(sd, cfg, batch, mode, steps, forced=None):
+    """Free-running: (tokens, attach).  ``forced`` = (tokens, attach) int64 [B, >= steps]: (tokens, attach, lp float64 [B, steps])."""
+    enc_mode, dec_mode, vocab_mode, ptr_mode = MODES[mode][:4]
+    tail_bf16 = len(MODES[mode]) > 4
     act = rb if enc_mode == "bf16" else (lambda x: x)       # tensors that cross a kernel boundary on the residual path (encoder)
     W = {k: (rb(v) if (v.dim() > 1 and "embedding" not in k) else v) for k, v in sd.items()}   # Linear weights bf16; tables / biases f32
 
@@ -93,6 +109,7 @@ def run(sd, cfg, batch, mode, steps):
     hid = torch.zeros(B, steps, d)
     out = torch.empty(B, 0, dtype=torch.long)
     att = torch.empty(B, 0, dtype=torch.long)
+    lps = []
     x_in = torch.zeros(B, d)
     for t in range(steps):
         x = act(x_in)
@@ -124,18 +141,30 @@ def run(sd, cfg, batch, mode, steps):
             dist = vd
         else:                                               # oracle/plank_oracle.py last_row_dist with the two heads' own precisions
             feat = hp[:, t] @ (sd if ptr_mode == "f32" else W)["pointer_head.weight"].t() + sd["pointer_head.bias"]
+            if tail_bf16:
+                feat = rb(feat)
             ptr = torch.einsum("bd,bjd->bj", feat, hp) / cfg.d_model
-            prob = torch.sigmoid(O.linear(x, sd["switch_head.weight"], sd["switch_head.bias"]))
+            prob = torch.sigmoid(O.linear(rb(x) if tail_bf16 else x, sd["switch_head.weight"], sd["switch_head.bias"]))
             ptr[:, t:] = O.NEG_INF
             pd_ = O.softmax_lastdim(ptr) * prob
             allowed = O.pointer_mask(cfg, t + 1)[t] != 0
             pd_ = torch.where(allowed[None], pd_, torch.full_like(pd_, 1e-6))
             dist = torch.cat((vd * (1 - prob), pd_), dim=-1)
-        tok, ptr_i = O.sample(cfg, dist, out)
+        if forced is None:
+            tok, ptr_i = O.sample(cfg, dist, out)
+        else:                                               # teacher forcing: the given candidate, its log p in float64
+            ptr_i = forced[1][:, t]
+            isp = ptr_i >= 0
+            tok = torch.where(isp, out.gather(1, ptr_i.clamp(min=0)[:, None])[:, 0] if t else forced[0][:, t], forced[0][:, t])
+            idx = torch.where(isp, cfg.vocab + ptr_i, tok)
+            assert int(idx.max()) < dist.shape[1] and not bool((isp & (ptr_i >= t)).any()), "forced candidate does not exist"
+            lps.append(torch.log(dist.gather(1, idx[:, None])[:, 0].double()))
         out = torch.cat((out, tok[:, None]), dim=1)
         att = torch.cat((att, ptr_i[:, None]), dim=1)
         x_in = (sd["input_embeddings.input_value.weight"][tok] + sd["query_coord_embedding.weight"][t % cfg.out_dof]
                 + sd["query_pos_embedding.weight"][t // cfg.out_dof])
+    if forced is not None:
+        return out, att, torch.stack(lps, dim=1)
     return out, att
 
 
@@ -149,7 +178,7 @@ def main():
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else c["max_out"]
     with torch.no_grad():
         s_ref, a_ref, marg = O.greedy_decode_cached(sd, cfg, db, max_steps=steps, early_stop=False, return_margins=True)
-        for mode in (sys.argv[3].split(",") if len(sys.argv) > 3 else list(MODES)):
+        for mode in (sys.argv[3].split(",") if len(sys.argv) > 3 else [m for m in MODES if not m.startswith("step_")]):
             s, a = run(sd, cfg, db, mode, steps)
             first, flips = [], []
             for i in range(Bn):

@@ -463,7 +463,8 @@ def test_greedy_decode_full_size_batch_256_by_1024_properties(dtype):
     must hold for any weights (reference models.py:235-256, 91-101): tokens are vocabulary ids; a pointer at step t points
     at an earlier step the pointer mask allows and the emitted token is the token of that step; steps < 6 never point;
     the device-side END bookkeeping equals the first END of each row.  Rows 0-1 (f32) are also decoded by the CPU oracle
-    and must agree token for token."""
+    and must agree token for token.  The NUMERICAL check of a 256-row batch - per-token log p of 16 rows, f32 and bf16, against
+    float64 - lives in tests/test_decode_logprob_gpu.py (case C)."""
     from oracle import plank_oracle as O
     from plankassembly_amd.data import spec_for, synth_batch
     import plankassembly_amd.decode as D
