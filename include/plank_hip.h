@@ -683,7 +683,7 @@ int pa_decode_sample_buffers(pa_model* m, void** scores);
  * prefix beam 0 carries the hypothesis and beams 1 .. K-1 stay at -inf, as at t = 0 without a prefix; the first free step fans out
  * from beam 0, and prefix_score / prefix_lp of the drawing are those of its row b*K.  Rows with t >= plen[r] behave exactly as without
  * a table, in the same step.  Without pa_decode_prefix_begin every mode launches the kernels it launched before and gives the same
- * bits; a step with a table takes the unfused tail.  Everything is read from device memory: the step captures into one hipGraph and
+ * bits, and a step with a table has the same launches.  Everything is read from device memory: the step captures into one hipGraph and
  * a new table needs no new capture.  pa_decode_begin clears the prefix; pa_decode_step_pair returns PA_EINVAL with a prefix set.
  *   pa_decode_prefix_ws_bytes: bytes of the prefix workspace for `rows` rows and Tmax positions.
  *   pa_decode_prefix_begin: after pa_decode_begin and after any pa_decode_beam_begin / pa_decode_sample_begin.  plen int32 [rows],

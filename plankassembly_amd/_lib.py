@@ -221,6 +221,14 @@ def check(rc: int, what: str):
         raise PlankHipError(f"{what} failed: {msg}")
 
 
+def ws_bytes(name: str, *args) -> int:
+    """The answer of the ``*_ws_bytes`` entry ``name``; a negative one is an error code and raises through check."""
+    need = int(getattr(lib(), name)(*args))
+    if need < 0:
+        check(need, name)
+    return need
+
+
 def dt(t: torch.Tensor) -> int:
     if t.dtype == torch.float32:
         return PA_F32

@@ -84,6 +84,7 @@ struct DecodeLayout {
 namespace {
 
 #define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+#define HIP_RC(x) do { hipError_t he_ = (x); if (he_ != hipSuccess) return (int)he_; } while (0)
 constexpr float LOG2E_F = 1.4426950408889634f;
 #include "split_merge.h"
 }  // namespace
@@ -262,6 +263,26 @@ struct ArgMax { float v; int i; };
 __device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) {   // first-max: larger value, then smaller index
     return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
 }
+// 256-thread block arg-max in better()'s first-max order, valid in every thread on return.  A caller that reduces again puts a barrier
+// of its own before the next call (sha is rewritten).
+__device__ __forceinline__ ArgMax block_argmax(ArgMax best, ArgMax* sha) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ArgMax other{__shfl_xor(best.v, o), __shfl_xor(best.i, o)};
+        best = better(best, other);
+    }
+    if ((threadIdx.x & 63) == 0) sha[threadIdx.x >> 6] = best;
+    __syncthreads();
+    return better(better(sha[0], sha[1]), better(sha[2], sha[3]));
+}
+// Candidate index -> the token and attach to write: vocab entry k < V is itself; pointer j (index V + j) takes the row's own token at j
+// (reference models.py:248-251).  `row` = the row's token history.
+struct TokAtt { int64_t tok, att; };
+__device__ __forceinline__ TokAtt candidate_token(int idx, int V, const int64_t* row) {
+    TokAtt c{idx, -1};
+    if (idx >= V) { c.att = idx - V; c.tok = row[c.att]; }
+    return c;
+}
 __device__ __forceinline__ float block_max(float v, float* sh) {
     v = wave_max(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
@@ -434,18 +455,12 @@ template <typename T>
 __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int ldv, const T* pfeat, const T* h, T* hid_cache,
                                                          const float* sw_w, const float* sw_b, int64_t* tokens,
                                                          int64_t* attach, int32_t* first_end, int32_t* t_dev,
-                                                         int Tmax, int d, int V, int end_tok,
-                                                         // fused tail (PLANK_DECODE_FUSE_TAIL, default on): the NEXT step's input
-                                                         // embedding of this row and the step counter - what dec_embed_kernel and
-                                                         // dec_advance_kernel did as two more launches of the serial chain
-                                                         int fuse, float* x32, T* xT, bf16* x_lp, const float* value,
-                                                         const float* coord, const float* pos, int dof, const PrefixDev px) {
+                                                         int Tmax, int d, int V, int end_tok, const PrefixDev px) {
     __shared__ float plog[MAX_T];
-    __shared__ long long s_tok;
     __shared__ float sh[4];
     __shared__ ArgMax sha[4];
     __shared__ float s_sw;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int t = *t_dev, sz = t + 1;
     const T* hb = h + (int64_t)b * d;
     // hidden-state cache laid out [Tmax][B][d]: the 256 blocks walk the rows j in step, and with a per-sequence
@@ -455,7 +470,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int 
     for (int c = tid; c < d; c += 256) cache[(int64_t)t * nb * d + c] = hb[c];
     const float* vr = vlog + (int64_t)b * ldv;
     const RowDist rd = row_dist_prepare<T>(vr, V, pfeat + (int64_t)b * d, hb, cache, nb, t, d, sw_w, sw_b, plog, sh, &s_sw);
-    if (px.plen && t < px.plen[b]) {                                // forced row (section 14; the host passes fuse = 0 with a table)
+    if (px.plen && t < px.plen[b]) {                                // forced row (section 14)
         if (tid == 0) {
             const Forced f = forced_candidate(px, b, t, Tmax, rd, vr, V, plog, tokens);
             tokens[(int64_t)b * Tmax + t] = f.tok;
@@ -469,41 +484,12 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int 
     }
     ArgMax best{-INFINITY, 0x7fffffff};
     row_dist_visit(rd, vr, V, plog, t, sz, [&](float p, int k) { best = better(best, ArgMax{p, k}); });
-    // block arg-max (first maximum)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ArgMax other{__shfl_xor(best.v, o), __shfl_xor(best.i, o)};
-        best = better(best, other);
-    }
-    if (lane == 0) sha[wave] = best;
-    __syncthreads();
+    best = block_argmax(best, sha);
     if (tid == 0) {
-        best = better(better(sha[0], sha[1]), better(sha[2], sha[3]));
-        int64_t tok = best.i, ptr = -1;
-        if (best.i >= V) { ptr = best.i - V; tok = tokens[(int64_t)b * Tmax + ptr]; }   // models.py:248-251
-        tokens[(int64_t)b * Tmax + t] = tok;
-        attach[(int64_t)b * Tmax + t] = ptr;
-        if (tok == end_tok && first_end[b] < 0) first_end[b] = t;
-        s_tok = tok;
-    }
-    if (!fuse) return;
-    __syncthreads();
-    {   // x(t + 1) = value[token(t)] + coord[t % dof] + pos[t / dof]   (reference models.py:114-123 on the token just sampled)
-        const long long tk = s_tok;
-        for (int c = tid << 2; c < d; c += 1024) {
-            f32x4 acc = *reinterpret_cast<const f32x4*>(value + tk * d + c);
-            acc += *reinterpret_cast<const f32x4*>(coord + (int64_t)(t % dof) * d + c);
-            acc += *reinterpret_cast<const f32x4*>(pos + (int64_t)(t / dof) * d + c);
-            if (x32) { *reinterpret_cast<f32x4*>(x32 + (int64_t)b * d + c) = acc; if (x_lp) st4<bf16>(x_lp + (int64_t)b * d + c, acc); }
-            else st4<T>(xT + (int64_t)b * d + c, acc);
-        }
-    }
-    // the block that finishes last advances the step counter: every block has read *t_dev long before its ticket
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned k = atomicAdd(reinterpret_cast<unsigned*>(t_dev + 1), 1u);
-        if (k == gridDim.x - 1) { t_dev[1] = 0; t_dev[0] = t + 1; }
+        const TokAtt c = candidate_token(best.i, V, tokens + (int64_t)b * Tmax);
+        tokens[(int64_t)b * Tmax + t] = c.tok;
+        attach[(int64_t)b * Tmax + t] = c.att;
+        if (c.tok == end_tok && first_end[b] < 0) first_end[b] = t;
     }
 }
 
@@ -527,7 +513,7 @@ __global__ __launch_bounds__(256) void dec_beam_cand_kernel(const float* vlog, i
     __shared__ float sh[4];
     __shared__ ArgMax sha[4];
     __shared__ float s_sw;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int t = *t_dev;
     const T* hb = h + (int64_t)b * d;
     const int64_t nb = gridDim.x;
@@ -556,21 +542,13 @@ __global__ __launch_bounds__(256) void dec_beam_cand_kernel(const float* vlog, i
         row_dist_visit(rd, vr, V, plog, t, t, [&](float p, int idx) {       // (jend = t: the self pointer is no candidate)
             if (p > 0.f && (p < prev.v || (p == prev.v && idx > prev.i))) best = better(best, ArgMax{p, idx});
         });
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            ArgMax other{__shfl_xor(best.v, o), __shfl_xor(best.i, o)};
-            best = better(best, other);
-        }
-        if (lane == 0) sha[wave] = best;
-        __syncthreads();
-        best = better(better(sha[0], sha[1]), better(sha[2], sha[3]));
+        best = block_argmax(best, sha);
         __syncthreads();                                            // (sha is rewritten by the next round)
         if (tid == 0) {
             if (best.i == 0x7fffffff) { lp[k] = -INFINITY; ct[k] = pad_tok; ca[k] = -1; }
             else {
-                int64_t tok = best.i, ptr = -1;
-                if (best.i >= V) { ptr = best.i - V; tok = tokens[(int64_t)b * Tmax + ptr]; }
-                lp[k] = logf(best.v); ct[k] = (int32_t)tok; ca[k] = (int32_t)ptr;
+                const TokAtt c = candidate_token(best.i, V, tokens + (int64_t)b * Tmax);
+                lp[k] = logf(best.v); ct[k] = (int32_t)c.tok; ca[k] = (int32_t)c.att;
             }
         }
         prev = best;
@@ -856,12 +834,11 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const float* vlog,
     if (pick == 0x7fffffff) pick = -block_min_i(-last, shi);       // rounding left no crossing: the last kept candidate
     if (tid == 0) {
         const int idx = pick < 0 ? 0 : pick;                        // (the top candidate always has w = 1: pick >= 0)
-        int64_t tok = idx, ptr = -1;
-        if (idx >= V) { ptr = idx - V; tok = tokens[(int64_t)r * Tmax + ptr]; }     // models.py:248-251
-        tokens[(int64_t)r * Tmax + t] = tok;
-        attach[(int64_t)r * Tmax + t] = ptr;
+        const TokAtt c = candidate_token(idx, V, tokens + (int64_t)r * Tmax);
+        tokens[(int64_t)r * Tmax + t] = c.tok;
+        attach[(int64_t)r * Tmax + t] = c.att;
         scores[r] += logf(sp[idx]);                                 // the untempered, unfiltered p
-        if (tok == end_tok) first_end[r] = t;
+        if (c.tok == end_tok) first_end[r] = t;
     }
 }
 
@@ -884,50 +861,6 @@ __global__ __launch_bounds__(256) void dec_prefix_init_kernel(int32_t* len, int3
         att[i] = at < 0 ? -1 : (at > 0x7fffffff ? 0x7fffffff : (int32_t)at);
         lp[i] = 0.f;
         if (i < rows) { len[i] = min(max(plen[i], 0), Tmax); score[i] = 0.f; }
-    }
-}
-
-// last decoder layer's norm3 and decoder.norm back to back on the same rows, plus the bf16 copy of the result (f32-residual step):
-// one wave per row, two-pass statistics in registers - three launches (two LayerNorms, dec_cast_kernel) of the serial chain in one
-__global__ __launch_bounds__(256) void dec_tail_norm_kernel(float* hf, bf16* h, const float* z, const float* g3, const float* b3, float eps3,
-                                                            const float* gf, const float* bf, float epsf, int rows, int d) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    constexpr int NV = 2;                                    // d <= 512: two 4-wide vectors per lane
-    f32x4 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (lane + i * 64) << 2;
-        v[i] = c < d ? *reinterpret_cast<const f32x4*>(z + (int64_t)row * d + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-        s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-    }
-    auto norm = [&](const float* g, const float* bb, float eps) {
-        const float mu = wave_sum(s) / d;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = (lane + i * 64) << 2;
-            if (c < d) for (int j = 0; j < 4; ++j) { const float t = v[i][j] - mu; q += t * t; }
-        }
-        const float rs = 1.0f / sqrtf(wave_sum(q) / d + eps);          // (the arithmetic of layernorm_fwd_kernel, term for term)
-        s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = (lane + i * 64) << 2;
-            if (c < d) {
-                const f32x4 gg = *reinterpret_cast<const f32x4*>(g + c), be = *reinterpret_cast<const f32x4*>(bb + c);
-                for (int j = 0; j < 4; ++j) v[i][j] = (v[i][j] - mu) * rs * gg[j] + be[j];
-                s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-            }
-        }
-    };
-    norm(g3, b3, eps3);
-    norm(gf, bf, epsf);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (lane + i * 64) << 2;
-        if (c < d) { *reinterpret_cast<f32x4*>(hf + (int64_t)row * d + c) = v[i]; st4<bf16>(h + (int64_t)row * d + c, v[i]); }
     }
 }
 
@@ -1153,14 +1086,19 @@ int64_t beam_segments(const pa_model_cfg& c, const StepForm& sf, const DecodeLay
 }
 
 // Beam workspace: scores f32 [rows], finished / parent int32 [rows], candidates (f32 log p, int32 token, int32 attach) [rows][K], then
-// the reorder scratch [rows][scr_row].
+// the reorder scratch [rows][scr_row].  The mode layouts (this one, sample_layout, prefix_layout): base NULL is the size query and
+// leaves L alone (L may be NULL).
 size_t beam_layout(DecodeLayout* L, char* base, int rows, int K, int64_t scr_row) {
     Arena a{base, 0};
-    L->bm_score = (float*)a.take((size_t)rows * 4); L->bm_fin = (int32_t*)a.take((size_t)rows * 4);
-    L->bm_parent = (int32_t*)a.take((size_t)rows * 4);
-    L->bm_clp = (float*)a.take((size_t)rows * K * 4); L->bm_ctok = (int32_t*)a.take((size_t)rows * K * 4);
-    L->bm_catt = (int32_t*)a.take((size_t)rows * K * 4);
-    L->bm_copy.scratch = (char*)a.take((size_t)rows * scr_row);
+    const size_t row = (size_t)rows * 4, cand = row * K;
+    void *score = a.take(row), *fin = a.take(row), *parent = a.take(row);
+    void *clp = a.take(cand), *ctok = a.take(cand), *catt = a.take(cand);
+    void* scratch = a.take((size_t)rows * scr_row);
+    if (base) {
+        L->bm_score = (float*)score; L->bm_fin = (int32_t*)fin; L->bm_parent = (int32_t*)parent;
+        L->bm_clp = (float*)clp; L->bm_ctok = (int32_t*)ctok; L->bm_catt = (int32_t*)catt;
+        L->bm_copy.scratch = (char*)scratch;
+    }
     return a.off;
 }
 
@@ -1169,6 +1107,18 @@ PrefixDev prefix_arg(const pa_model* m) {
     const DecodeLayout* L = m->dec;
     if (!L->px_on) return PrefixDev{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     return PrefixDev{L->px_len, L->px_tok, L->px_att, L->px_score, L->px_lp, m->cfg.pad, 0};
+}
+
+// The end of a greedy step: arg-max (or the forced candidate) per row.
+template <typename T>
+int greedy_tail(pa_model* m, int ldv, hipStream_t s) {
+    const pa_model_cfg& c = m->cfg;
+    DecodeLayout* L = m->dec;
+    const int tl = m->tail();
+    PA_LAUNCH(dec_sample_kernel<T>, dim3(L->B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h, (T*)L->hid_cache,
+              (const float*)m->pf[tl + T_SW_W], (const float*)m->pf[tl + T_SW_B], L->tokens, L->attach, L->first_end, L->t_dev, L->Tmax,
+              c.d_model, c.vocab, c.end, prefix_arg(m));
+    return 0;
 }
 
 // The end of a beam step (in place of dec_sample_kernel): candidates, merge, history reorder.  The next step's input embedding is
@@ -1204,6 +1154,20 @@ int sample_tail(pa_model* m, int ldv, hipStream_t s) {
     return 0;
 }
 
+// The end of every step, whatever the mode and the residual-stream form: the mode's choice of a token per row, then the step counter.
+// (The next step's embedding is dec_embed_kernel at its part 0.  A fused tail - embedding and counter inside dec_sample_kernel, norm3 +
+// decoder.norm in one launch, PLANK_DECODE_FUSE_TAIL - was built, MEASURED NULL on MI355X in round 5 (B 256 x 1024 steps under graph
+// replay: bf16 1.0905 ms / step fused against 1.0794, f32 1.9954 against 1.9813) and removed.)
+template <typename T>
+int end_of_step(pa_model* m, int ldv, hipStream_t s) {
+    DecodeLayout* L = m->dec;
+    if (L->beamK > 0) RC(beam_tail<T>(m, ldv, s));
+    else if (L->sampleN > 0) RC(sample_tail<T>(m, ldv, s));
+    else RC(greedy_tail<T>(m, ldv, s));
+    PA_LAUNCH(dec_advance_kernel, dim3(1), dim3(64), 0, s, L->t_dev);
+    return 0;
+}
+
 // One decode step in 2 * n_dec + 1 parts, each ending right after an attention launch (part 2i: self-attention of layer i,
 // part 2i + 1: its cross-attention; the last part is the tail: final norm, heads, sampling).  The attention launches are the
 // HBM-bound third of the step (they stream the K/V caches); everything between them is a chain of latency-bound launches on B
@@ -1224,8 +1188,8 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
     auto gelu_ff = [&]() -> int { return gelu ? pa_gelu_fwd(L->ff, L->ff, B, ff, ff, c.dtype, 0.f, 0, st) : 0; };
     const int n_parts = 2 * c.n_dec + 1;
     if (part < 0 || part >= n_parts) return PA_EINVAL;
-    auto fence_in = [&]() -> int { if (wait_ev) { hipError_t e = hipStreamWaitEvent(s, wait_ev, 0); if (e != hipSuccess) return (int)e; } return 0; };
-    auto fence_out = [&]() -> int { if (rec_ev) { hipError_t e = hipEventRecord(rec_ev, s); if (e != hipSuccess) return (int)e; } return 0; };
+    auto fence_in = [&]() -> int { if (wait_ev) HIP_RC(hipStreamWaitEvent(s, wait_ev, 0)); return 0; };
+    auto fence_out = [&]() -> int { if (rec_ev) HIP_RC(hipEventRecord(rec_ev, s)); return 0; };
     // absorbed cross-attention of layer i (csrc/decode_mq.h): q~_h = scale log2e W_k,h^T q_h for all heads, then attention over the
     // memory rows themselves; the Linear behind it applies W_o,h W_v,h to the context rows (wo_t)
     auto cross_mq = [&](pa_model* mm, int i, hipStream_t ss) -> int {
@@ -1244,17 +1208,8 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
                                  L->mq_sp, L->mq_sp_bytes));
         return fence_out();
     };
-    // PLANK_DECODE_FUSE_TAIL=1 (default 0): the sampling kernel also writes the next step's input embedding and advances the step
-    // counter, and (f32-residual step) norm3 + decoder.norm + the bf16 copy are one launch: 57 -> 52 launches per step, tokens
-    // identical (tests/test_model_gpu.py decode tests pass either way).  MEASURED NULL on MI355X, round 5, B 256 x 1024 steps under
-    // graph replay, A/B in one session: bf16 1.0905 ms / step fused against 1.0794 unfused, f32 1.9954 against 1.9813 - the five
-    // launches it removes cost ~2 us each inside a replayed graph, and the sampling kernel's longer per-block tail (embedding row,
-    // fence, ticket) costs the same again.  Fourth fusion of this decode step that does not pay.  The embedding
-    // of step 0 is all zeros (models.py:114-123 with no token yet): pa_decode_begin clears x.
-    static const int fuse_tail = getenv("PLANK_DECODE_FUSE_TAIL") ? atoi(getenv("PLANK_DECODE_FUSE_TAIL")) : 0;
-    const bool unfused = !fuse_tail || L->beamK > 0 || L->sampleN > 0 || L->px_on;   // (beam, sampling and prefix steps always take the unfused tail)
-    const int fuse_greedy = unfused ? 0 : fuse_tail;
-    if (part == 0 && unfused) {
+    // the step's input embedding from the token of step t - 1 (all zeros at t = 0, reference models.py:114-123 with no token yet)
+    if (part == 0) {
         const int g1 = (B * (d / 4) + 255) / 256;
         if (L->f32res)
             PA_LAUNCH(dec_embed_kernel<float>, dim3(g1), dim3(256), 0, s, (float*)L->x, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
@@ -1299,18 +1254,11 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
                                L->ff, ff, B, ff, d, act, st));
             RC(gelu_ff());
             RC(linear_res32(m, L->ff, PL(pb + D_L2_W), PF(pb + D_L2_B), xf, zf, L->zb, B, d, ff, st));
-            if (part == n_parts - 1 && !(fuse_tail && d <= 512 && (d & 3) == 0))
+            if (part == n_parts - 1)
                 RC(pa_layernorm_fwd(xf, zf, PF(pb + D_N3_W), PF(pb + D_N3_B), L->mean, L->rstd, B, d, c.eps_layer, PA_F32, st));
         }
         if (part == n_parts - 1) {
-            const bool tail_norm = fuse_tail && d <= 512 && (d & 3) == 0;
-            if (tail_norm) {
-                const int pl_ = m->dec_base(c.n_dec - 1);
-                PA_LAUNCH(dec_tail_norm_kernel, dim3((B + 3) / 4), dim3(256), 0, s, L->hf, (bf16*)L->h, (const float*)zf, PF(pl_ + D_N3_W),
-                          PF(pl_ + D_N3_B), c.eps_layer, PF(m->dec_norm()), PF(m->dec_norm() + 1), c.eps_final, B, d);
-            } else {
-                RC(pa_layernorm_fwd(L->hf, xf, PF(m->dec_norm()), PF(m->dec_norm() + 1), L->mean, L->rstd, B, d, c.eps_final, PA_F32, st));
-            }
+            RC(pa_layernorm_fwd(L->hf, xf, PF(m->dec_norm()), PF(m->dec_norm() + 1), L->mean, L->rstd, B, d, c.eps_final, PA_F32, st));
             const int tl = m->tail(), ldv = (c.vocab + 7) / 8 * 8;
             {   // vocabulary head in f32 on the f32 hidden rows (f32 master weight; the f32 skinny kernel)
                 pa_gemm_args g; memset(&g, 0, sizeof(g));
@@ -1320,18 +1268,9 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
                 g.alpha = 1.f; g.aux_scale = 1.f; g.splitk = 1;
                 RC(pa_gemm(&g, st));
             }
-            if (!tail_norm)
-                PA_LAUNCH(dec_cast_kernel, dim3((B * d / 4 + 255) / 256), dim3(256), 0, s, (bf16*)L->h, (const float*)L->hf, (int64_t)B * d / 4);
+            PA_LAUNCH(dec_cast_kernel, dim3((B * d / 4 + 255) / 256), dim3(256), 0, s, (bf16*)L->h, (const float*)L->hf, (int64_t)B * d / 4);
             RC(linear(m, L->h, PL(tl + T_PTR_W), PF(tl + T_PTR_B), L->pfeat, d, B, d, d, 0, nullptr, -1, st));
-            if (L->beamK > 0) RC(beam_tail<T>(m, ldv, s));
-            else if (L->sampleN > 0) RC(sample_tail<T>(m, ldv, s));
-            else
-                PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
-                                   (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
-                                   c.vocab, c.end, fuse_greedy, (float*)L->x, (T*)nullptr, (bf16*)L->xb, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
-                                   c.out_dof, prefix_arg(m));
-            if (unfused) PA_LAUNCH(dec_advance_kernel, dim3(1), dim3(64), 0, s, L->t_dev);
-            return 0;
+            return end_of_step<T>(m, ldv, s);
         }
         const int i = part / 2, pb = m->dec_base(i);
         if ((part & 1) == 0 && L->mq_self_bf) {
@@ -1411,15 +1350,7 @@ int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t re
         const int tl = m->tail(), ldv = (c.vocab + 7) / 8 * 8;
         RC(linear(m, L->h, PL(tl + T_VOCAB_W), PF(tl + T_VOCAB_B), L->vlog, ldv, B, c.vocab, d, 0, nullptr, PA_F32, st));
         RC(linear(m, L->h, PL(tl + T_PTR_W), PF(tl + T_PTR_B), L->pfeat, d, B, d, d, 0, nullptr, -1, st));
-        if (L->beamK > 0) RC(beam_tail<T>(m, ldv, s));
-        else if (L->sampleN > 0) RC(sample_tail<T>(m, ldv, s));
-        else
-            PA_LAUNCH(dec_sample_kernel<T>, dim3(B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h,
-                               (T*)L->hid_cache, PF(tl + T_SW_W), PF(tl + T_SW_B), L->tokens, L->attach, L->first_end, L->t_dev, Tmax, d,
-                               c.vocab, c.end, fuse_greedy, (float*)nullptr, (T*)L->x, (bf16*)nullptr, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
-                               c.out_dof, prefix_arg(m));
-        if (unfused) PA_LAUNCH(dec_advance_kernel, dim3(1), dim3(64), 0, s, L->t_dev);
-        return 0;
+        return end_of_step<T>(m, ldv, s);
     }
     const int i = part / 2;
     const int pb = m->dec_base(i);
@@ -1509,8 +1440,7 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
     L->px_on = false;                                           // and no forced prefix until pa_decode_prefix_begin
     if (L->mq) {
         // absorbed cross-attention: the step reads the encoder output rows themselves - no K / V projection of the memory at all
-        hipError_t hm = hipMemcpyAsync(L->mem, memory, (size_t)m->NE * d * e, hipMemcpyDeviceToDevice, s);
-        if (hm != hipSuccess) return (int)hm;
+        HIP_RC(hipMemcpyAsync(L->mem, memory, (size_t)m->NE * d * e, hipMemcpyDeviceToDevice, s));
     }
     for (int i = 0; i < c.n_dec && !L->mq; ++i) {       // cross-attention K/V of the memory: once per sequence, not per step
         const int pb = m->dec_base(i);
@@ -1561,28 +1491,19 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
     }
     L->cu = nullptr;
     if (m->batch.cu_in) {
-        hipError_t hc = hipMemcpyAsync(L->cu_store, m->batch.cu_in, (size_t)(B + 1) * 4, hipMemcpyDeviceToDevice, s);
-        if (hc != hipSuccess) return (int)hc;
+        HIP_RC(hipMemcpyAsync(L->cu_store, m->batch.cu_in, (size_t)(B + 1) * 4, hipMemcpyDeviceToDevice, s));
         L->cu = L->cu_store;
     }
-    hipError_t he = hipMemcpyAsync(L->kpm, m->batch.input_mask, (size_t)B * S, hipMemcpyDeviceToDevice, s);
-    if (he != hipSuccess) return (int)he;
-    he = hipMemsetAsync(L->first_end, 0xFF, (size_t)B * 4, s);
-    if (he != hipSuccess) return (int)he;
-    he = hipMemsetAsync(L->t_dev, 0, 8, s);                     // step counter and the sampling kernel's ticket
-    if (he != hipSuccess) return (int)he;
-    if (L->mq_sp) {                                             // the range blocks' tickets (every launch leaves them zero again)
-        he = hipMemsetAsync(L->mq_sp, 0, ((size_t)B * 4 + 255) / 256 * 256, s);
-        if (he != hipSuccess) return (int)he;
-    }
-    he = hipMemsetAsync(L->x, 0, (size_t)B * c.d_model * 4, s);  // input embedding of step 0: zeros (later steps: written by the sampling kernel)
-    if (he != hipSuccess) return (int)he;
-    he = hipMemsetAsync(L->xb, 0, (size_t)B * c.d_model * 2, s);
-    if (he != hipSuccess) return (int)he;
-    he = hipMemsetAsync(L->tokens, 0, (size_t)B * Tmax * 8, s);
-    if (he != hipSuccess) return (int)he;
-    he = hipMemsetAsync(L->attach, 0xFF, (size_t)B * Tmax * 8, s);
-    return he == hipSuccess ? 0 : (int)he;
+    HIP_RC(hipMemcpyAsync(L->kpm, m->batch.input_mask, (size_t)B * S, hipMemcpyDeviceToDevice, s));
+    HIP_RC(hipMemsetAsync(L->first_end, 0xFF, (size_t)B * 4, s));
+    HIP_RC(hipMemsetAsync(L->t_dev, 0, 8, s));                  // step counter (and the word beside it, once the removed fused tail's ticket)
+    if (L->mq_sp)                                               // the range blocks' tickets (every launch leaves them zero again)
+        HIP_RC(hipMemsetAsync(L->mq_sp, 0, ((size_t)B * 4 + 255) / 256 * 256, s));
+    HIP_RC(hipMemsetAsync(L->x, 0, (size_t)B * c.d_model * 4, s));
+    HIP_RC(hipMemsetAsync(L->xb, 0, (size_t)B * c.d_model * 2, s));
+    HIP_RC(hipMemsetAsync(L->tokens, 0, (size_t)B * Tmax * 8, s));
+    HIP_RC(hipMemsetAsync(L->attach, 0xFF, (size_t)B * Tmax * 8, s));
+    return 0;
 }
 
 extern "C" int pa_decode_step(pa_model* m, void* stream) {
@@ -1675,8 +1596,7 @@ extern "C" int64_t pa_decode_beam_ws_bytes(pa_model* m, int32_t rows, int32_t S,
     BeamCopy cp;
     const int64_t scr = beam_segments(m->cfg, step_form(m->cfg, rows, S, Tmax), nullptr, rows, Tmax, &cp);
     if (scr < 0) return scr;
-    DecodeLayout tmp;
-    return (int64_t)beam_layout(&tmp, nullptr, rows, K, scr) + 256;
+    return (int64_t)beam_layout(nullptr, nullptr, rows, K, scr) + 256;
 }
 
 extern "C" int pa_decode_beam_begin(pa_model* m, int32_t K, void* ws, int64_t ws_bytes, void* stream) {
@@ -1687,8 +1607,8 @@ extern "C" int pa_decode_beam_begin(pa_model* m, int32_t K, void* ws, int64_t ws
     const StepForm sf{L->mq_contract, L->mq_self, L->mq_self_bf};
     const int64_t scr = beam_segments(m->cfg, sf, L, rows, L->Tmax, &L->bm_copy);
     if (scr < 0) return (int)scr;
-    const size_t need = beam_layout(L, (char*)ws, rows, K, scr);
-    if ((int64_t)need > ws_bytes) { L->beamK = 0; return PA_EINVAL; }
+    if ((int64_t)beam_layout(nullptr, nullptr, rows, K, scr) > ws_bytes) { L->beamK = 0; return PA_EINVAL; }
+    beam_layout(L, (char*)ws, rows, K, scr);
     PA_LAUNCH(dec_beam_init_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, L->bm_score, L->bm_fin, L->bm_parent, rows, K);
     L->beamK = K; L->sampleN = 0;                               // (beam mode replaces sampling mode)
     return 0;
@@ -1710,8 +1630,9 @@ bool sample_params_ok(const pa_sample_params* p, int rows) {
 // sampling workspace: the parameter block, then scores f32 [rows]
 size_t sample_layout(DecodeLayout* L, char* base, int rows) {
     Arena a{base, 0};
-    L->sm_prm = a.take(sizeof(SampleParamsDev));
-    L->sm_score = (float*)a.take((size_t)rows * 4);
+    void* prm = a.take(sizeof(SampleParamsDev));
+    void* score = a.take((size_t)rows * 4);
+    if (base) { L->sm_prm = prm; L->sm_score = (float*)score; }
     return a.off;
 }
 int sample_write_params(DecodeLayout* L, const pa_sample_params* p, float* zero_scores, void* stream) {
@@ -1725,8 +1646,7 @@ int sample_write_params(DecodeLayout* L, const pa_sample_params* p, float* zero_
 
 extern "C" int64_t pa_decode_sample_ws_bytes(pa_model* m, int32_t rows) {
     if (!m || rows <= 0) return PA_EINVAL;
-    DecodeLayout tmp;
-    return (int64_t)sample_layout(&tmp, nullptr, rows) + 256;
+    return (int64_t)sample_layout(nullptr, nullptr, rows) + 256;
 }
 
 extern "C" int pa_decode_sample_begin(pa_model* m, const pa_sample_params* p, void* ws, int64_t ws_bytes, void* stream) {
@@ -1734,8 +1654,7 @@ extern "C" int pa_decode_sample_begin(pa_model* m, const pa_sample_params* p, vo
     if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return PA_EALIGN;
     if (m->cfg.vocab > SAMPLE_MAX_V) return PA_ESHAPE;
     DecodeLayout* L = m->dec;
-    DecodeLayout tmp;
-    if ((int64_t)sample_layout(&tmp, nullptr, L->B) > ws_bytes) return PA_EINVAL;
+    if ((int64_t)sample_layout(nullptr, nullptr, L->B) > ws_bytes) return PA_EINVAL;
     sample_layout(L, (char*)ws, L->B);
     RC(sample_write_params(L, p, L->sm_score, stream));
     L->sampleN = p->n_per_drawing; L->beamK = 0;                // (sampling mode replaces beam mode)
@@ -1758,9 +1677,12 @@ namespace {
 // prefix workspace: plen int32 [rows], ptok / patt int32 [rows][Tmax], prefix_score f32 [rows], prefix_lp f32 [rows][Tmax]
 size_t prefix_layout(DecodeLayout* L, char* base, int rows, int Tmax) {
     Arena a{base, 0};
-    L->px_len = (int32_t*)a.take((size_t)rows * 4);
-    L->px_tok = (int32_t*)a.take((size_t)rows * Tmax * 4); L->px_att = (int32_t*)a.take((size_t)rows * Tmax * 4);
-    L->px_score = (float*)a.take((size_t)rows * 4); L->px_lp = (float*)a.take((size_t)rows * Tmax * 4);
+    const size_t row = (size_t)rows * 4, table = row * Tmax;
+    void *len = a.take(row), *tok = a.take(table), *att = a.take(table), *score = a.take(row), *lp = a.take(table);
+    if (base) {
+        L->px_len = (int32_t*)len; L->px_tok = (int32_t*)tok; L->px_att = (int32_t*)att;
+        L->px_score = (float*)score; L->px_lp = (float*)lp;
+    }
     return a.off;
 }
 int prefix_write(DecodeLayout* L, const int32_t* plen, const int64_t* ptok, const int64_t* patt, void* stream) {
@@ -1773,8 +1695,7 @@ int prefix_write(DecodeLayout* L, const int32_t* plen, const int64_t* ptok, cons
 
 extern "C" int64_t pa_decode_prefix_ws_bytes(pa_model* m, int32_t rows, int32_t Tmax) {
     if (!m || rows <= 0 || Tmax <= 0 || Tmax > MAX_T) return PA_EINVAL;
-    DecodeLayout tmp;
-    return (int64_t)prefix_layout(&tmp, nullptr, rows, Tmax) + 256;
+    return (int64_t)prefix_layout(nullptr, nullptr, rows, Tmax) + 256;
 }
 
 extern "C" int pa_decode_prefix_begin(pa_model* m, const int32_t* plen, const int64_t* ptok, const int64_t* patt, void* ws,
@@ -1782,8 +1703,7 @@ extern "C" int pa_decode_prefix_begin(pa_model* m, const int32_t* plen, const in
     if (!m || !m->dec || m->dec->B <= 0 || !plen || !ptok || !patt || !ws) return PA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return PA_EALIGN;
     DecodeLayout* L = m->dec;
-    DecodeLayout tmp;
-    if ((int64_t)prefix_layout(&tmp, nullptr, L->B, L->Tmax) > ws_bytes) return PA_EINVAL;
+    if ((int64_t)prefix_layout(nullptr, nullptr, L->B, L->Tmax) > ws_bytes) return PA_EINVAL;
     prefix_layout(L, (char*)ws, L->B, L->Tmax);
     RC(prefix_write(L, plen, ptok, patt, stream));
     L->px_on = true;

@@ -5,17 +5,9 @@ One decode step is a fixed kernel sequence that reads its step index from device
 early-stop test (models.py:306, a device->host sync per token) becomes a check of a device flag
 every ``check_every`` replays.
 
-Lanes.  A decode step alternates between HBM-bound kernels (single-query attention over the K/V
-caches: ~60 % of the step) and 38 small Linears that are pure launch latency at M = batch rows
-(~9 us each whatever they compute).  Samples are independent, so the batch is split into two
-halves ("lanes") that run the same step on two streams inside one captured graph (fork / join):
-while one lane sits in its latency-bound Linears the other streams its caches.  Each lane has its
-own runtime handle (same parameter buffers), encoder workspace and decode arena; results are
-concatenated.  ``lanes=1`` (or a batch too small to split) is the plain single-stream step.
-Measured on MI355X (rocprofv3 kernel trace of the replayed graph, tools/overlap_from_db.py): kernels
-of the two lanes are in flight together for only 6.6 % of the busy time - the dispatcher rarely
-co-schedules them - so the gain is 1 % (187 k vs 185 k tokens/s); the fix for the latency-bound
-Linears is fewer launches per step, not a second stream.
+A lane is one runtime handle with its own encoder workspace and decode arena, stepping its share of the batch on its own stream.
+One lane is the default: the single-stream step (1.210 ms at B 256) is ahead of two half-batch lanes in one captured graph (1.239 ms;
+their kernels overlap for only 6.6 % of the busy time), so ``lanes=2`` stays as a measured alternative.  DESIGN.md has the rest.
 """
 from __future__ import annotations
 
@@ -28,15 +20,47 @@ import torch
 from . import _lib as L
 
 
+class _Arena:
+    """One growable uint8 device tensor that the library uses as a 256-byte-aligned workspace."""
+
+    def __init__(self, slack=256):
+        self.buf = None
+        self.slack = slack                             # bytes allocated beyond the library's size (at least the 256 of the alignment)
+        self.grown = 0                                 # allocations so far
+
+    def ensure(self, nbytes, device):
+        """Room for ``nbytes`` behind a 256-byte-aligned base.  Returns (base pointer, bytes usable from it)."""
+        if self.buf is None or self.buf.numel() < nbytes + 256:
+            self.buf = torch.empty(nbytes + self.slack, dtype=torch.uint8, device=device)
+            self.grown += 1
+        base = (self.buf.data_ptr() + 255) // 256 * 256
+        return base, self.buf.numel() - (base - self.buf.data_ptr())
+
+    def view(self, ptr, nbytes, dtype, shape):
+        """The typed view of ``nbytes`` at a device pointer the library handed back."""
+        off = ptr - self.buf.data_ptr()
+        return self.buf[off: off + nbytes].view(dtype).view(shape)
+
+    def data_ptr(self):
+        return None if self.buf is None else self.buf.data_ptr()
+
+
+def _buffers(name, handle, n):
+    """The n device pointers of a ``*_buffers`` entry."""
+    ptrs = [C.c_void_p() for _ in range(n)]
+    L.check(getattr(L.lib(), name)(handle, *[C.byref(p) for p in ptrs]), name)
+    return [p.value for p in ptrs]
+
+
 class _Lane:
     def __init__(self, model, own_handle):
         self.model = model
         self.own = own_handle
         self.handle = model.new_bound_handle() if own_handle else None
-        self.enc_ws = None
-        self.ws = None
+        self.enc_ws = _Arena(slack=512)
+        self.ws = _Arena()
         self.keep = None
-        self.key = None
+        self.key = None                                # what a captured step depends on: (B, S, Tmax, flat, shadow, ws pointer, ws allocation)
         self.stream = None
 
     def h(self):
@@ -52,48 +76,25 @@ class _Lane:
         m, lib = self.model, L.lib()
         b, keep = m._make_batch(batch, with_output=False)
         b.T = 1
-        need = int(lib.pa_model_train_ws_bytes(self.h(), b.B, b.S, 1))
-        if need < 0:
-            L.check(need, "pa_model_train_ws_bytes")
         dev = m.flat_params.device
-        if self.enc_ws is None or self.enc_ws.numel() < need + 256:
-            self.enc_ws = torch.empty(need + 512, dtype=torch.uint8, device=dev)
-        base = (self.enc_ws.data_ptr() + 255) // 256 * 256
+        base, room = self.enc_ws.ensure(L.ws_bytes("pa_model_train_ws_bytes", self.h(), b.B, b.S, 1), dev)
         stats = torch.empty(L.lib().pa_model_stats_floats(), dtype=torch.float32, device=dev)   # include/plank_hip.h: f32[8]
-        L.check(lib.pa_model_train_fwd(self.h(), C.byref(b), C.c_void_p(base),
-                                       C.c_int64(self.enc_ws.numel() - (base - self.enc_ws.data_ptr())), C.c_uint32(0), 0,
+        L.check(lib.pa_model_train_fwd(self.h(), C.byref(b), C.c_void_p(base), C.c_int64(room), C.c_uint32(0), 0,
                                        L.ptr(stats), L.stream()), "pa_model_train_fwd(encoder)")
-        need = int(lib.pa_decode_ws_bytes(self.h(), b.B, b.S, Tmax))
-        if need < 0:
-            L.check(need, "pa_decode_ws_bytes")
-        fresh = False
-        if self.ws is None or self.ws.numel() < need + 256:
-            self.ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-            fresh = True
-        dbase = (self.ws.data_ptr() + 255) // 256 * 256
-        L.check(lib.pa_decode_begin(self.h(), C.c_void_p(dbase), C.c_int64(self.ws.numel() - (dbase - self.ws.data_ptr())),
-                                    Tmax, L.stream()), "pa_decode_begin")
+        base, room = self.ws.ensure(L.ws_bytes("pa_decode_ws_bytes", self.h(), b.B, b.S, Tmax), dev)
+        L.check(lib.pa_decode_begin(self.h(), C.c_void_p(base), C.c_int64(room), Tmax, L.stream()), "pa_decode_begin")
         self.keep = (b, keep, stats)
         shadow = m._shadow.data_ptr() if m._shadow is not None else 0
-        key = (b.B, b.S, Tmax, m._flat.data_ptr(), shadow, self.ws.data_ptr())
-        changed = fresh or key != self.key
-        self.key = key
-        return b.B, changed
+        self.key = (b.B, b.S, Tmax, m._flat.data_ptr(), shadow, self.ws.data_ptr(), self.ws.grown)
+        return b.B
 
     def step(self):
         L.check(L.lib().pa_decode_step(self.h(), L.stream()), "pa_decode_step")
 
     def buffers(self, B, Tmax):
-        ptrs = [C.c_void_p() for _ in range(4)]
-        L.check(L.lib().pa_decode_buffers(self.h(), *[C.byref(p) for p in ptrs]), "pa_decode_buffers")
-        base = self.ws.data_ptr()
-
-        def view(p, nbytes, dtype, shape):
-            off = p.value - base
-            return self.ws[off: off + nbytes].view(dtype).view(shape)
-
-        return (view(ptrs[0], B * Tmax * 8, torch.int64, (B, Tmax)), view(ptrs[1], B * Tmax * 8, torch.int64, (B, Tmax)),
-                view(ptrs[2], B * 4, torch.int32, (B,)))
+        tokens, attach, first_end, _ = _buffers("pa_decode_buffers", self.h(), 4)
+        return (self.ws.view(tokens, B * Tmax * 8, torch.int64, (B, Tmax)), self.ws.view(attach, B * Tmax * 8, torch.int64, (B, Tmax)),
+                self.ws.view(first_end, B * 4, torch.int32, (B,)))
 
 
 def _split_batch(batch, lo, hi):
@@ -159,6 +160,8 @@ def prefix_table(prefix, B, Tmax, vocab_size, end_token, pad_token, strict=True)
 
 
 class GreedyDecoder:
+    _repeat = None                                     # rows per drawing (BeamDecoder: K, SampleDecoder: N; None: the batch as given)
+
     def __init__(self, model, use_graph=None, check_every=16, strict_graph=False, lanes=None):
         """``strict_graph``: a failed hipGraph capture raises instead of falling back to eager launches (benchmarks must
         not silently measure the slow path; PLANK_DECODE_GRAPH=1 has the same effect).  ``lanes``: 1 or 2 (default 1,
@@ -180,8 +183,9 @@ class GreedyDecoder:
         self._side = None
         self._active = 0
         self.last_steps = 0
-        self._pws = None                                   # prefix workspace (pa_decode_prefix_begin) and what the graph captured of it
-        self._pkey = None
+        self._key = {"lanes": None, "mode": None, "prefix": None}     # what the captured step depends on (_rekey)
+        self._mws = _Arena()                               # the mode's workspace (beam / sampling)
+        self._pws = _Arena()                               # prefix workspace (pa_decode_prefix_begin)
         self._pkeep = None
         self.last_prefix_scores = None
         self.last_prefix_logprobs = None
@@ -198,14 +202,29 @@ class GreedyDecoder:
             self._lanes.append(_Lane(self.model, own_handle=len(self._lanes) > 0))
         return self._lanes[i]
 
+    def _rekey(self, **parts):
+        """The one place a captured step is dropped: when a part of what it captured - ``lanes``, ``mode``, ``prefix`` - changed."""
+        key = {**self._key, **parts}
+        if key != self._key:
+            self._graph = None
+        self._key = key
+
+    def _mode_begin(self, lane, rows, Tmax):
+        """The mode's own begin on the begun lane (greedy: nothing).  Returns the mode's part of the graph key."""
+        return None
+
     def begin(self, batch, max_len=None):
-        """Encoder + cross-K/V projection + state reset.  Returns (B, Tmax)."""
+        """Encoder (on the batch with every drawing repeated ``_repeat`` times) + cross-K/V projection + state reset + the mode's
+        begin.  Returns (rows, Tmax)."""
         m = self.model
+        if self._repeat is not None:
+            batch = _repeat_batch(batch, self._repeat)
+            if m.unpad:
+                batch = m.prepare_batch(batch, groups=False)
         Tmax = int(max_len or m.max_output_length)
         B = batch["input_value"].shape[0]
         n = 2 if (self.max_lanes >= 2 and B >= 32) else 1
         self._bounds = [(0, B)] if n == 1 else [(0, B // 2), (B // 2, B)]
-        changed = n != self._active
         self._active = n
         if n == 2 and self._side is None:
             self._side = torch.cuda.Stream()
@@ -214,15 +233,13 @@ class GreedyDecoder:
             ln = self._lane(i)
             sub = batch if n == 1 else m.prepare_batch(_split_batch(batch, lo, hi), groups=False) if m.unpad else _split_batch(batch, lo, hi)
             if i == 0:
-                _, ch = ln.begin(sub, Tmax)
+                ln.begin(sub, Tmax)
             else:
                 self._side.wait_stream(main)
                 with torch.cuda.stream(self._side):
-                    _, ch = ln.begin(sub, Tmax)
+                    ln.begin(sub, Tmax)
                 main.wait_stream(self._side)
-            changed = changed or ch
-        if changed:
-            self._graph = None
+        self._rekey(lanes=tuple(ln.key for ln in self._lanes[:n]), mode=self._mode_begin(self._lanes[0], B, Tmax))
         return B, Tmax
 
     def _step_eager(self):
@@ -282,36 +299,41 @@ class GreedyDecoder:
         """pa_decode_prefix_begin on the begun decode (every drawing's prefix repeated ``repeat`` times, _repeat_batch's layout), or -
         table None - nothing.  A captured step is dropped when the prefix appears, goes away or its workspace moves; a new table on
         the same workspace replays the same graph.  Returns (prefix_score [rows], prefix_lp [rows, Tmax]) device views, or None."""
-        key = None
-        if table is not None:
-            lib, ln = L.lib(), self._lanes[0]
-            dev = self.model.flat_params.device
-            lengths, ptok, patt = table
-            plen = lengths.repeat_interleave(repeat).to(torch.int32).to(dev)
-            ptok = ptok.repeat_interleave(repeat, dim=0).contiguous().to(dev)
-            patt = patt.repeat_interleave(repeat, dim=0).contiguous().to(dev)
-            assert plen.shape[0] == rows and ptok.shape == (rows, Tmax)
-            need = int(lib.pa_decode_prefix_ws_bytes(ln.h(), rows, Tmax))
-            if need < 0:
-                L.check(need, "pa_decode_prefix_ws_bytes")
-            if self._pws is None or self._pws.numel() < need + 256:
-                self._pws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-            base = (self._pws.data_ptr() + 255) // 256 * 256
-            L.check(lib.pa_decode_prefix_begin(ln.h(), L.ptr(plen), L.ptr(ptok), L.ptr(patt), C.c_void_p(base),
-                                               C.c_int64(self._pws.numel() - (base - self._pws.data_ptr())), L.stream()),
-                    "pa_decode_prefix_begin")
-            self._pkeep = (plen, ptok, patt)
-            key = self._pws.data_ptr()
-        if key != self._pkey:
-            self._graph = None
-        self._pkey = key
         if table is None:
+            self._rekey(prefix=None)
             return None
-        ptrs = [C.c_void_p() for _ in range(2)]
-        L.check(L.lib().pa_decode_prefix_buffers(self._lanes[0].h(), *[C.byref(p) for p in ptrs]), "pa_decode_prefix_buffers")
-        o0, o1 = ptrs[0].value - self._pws.data_ptr(), ptrs[1].value - self._pws.data_ptr()
-        return (self._pws[o0: o0 + rows * 4].view(torch.float32),
-                self._pws[o1: o1 + rows * Tmax * 4].view(torch.float32).view(rows, Tmax))
+        ln = self._lanes[0]
+        dev = self.model.flat_params.device
+        lengths, ptok, patt = table
+        plen = lengths.repeat_interleave(repeat).to(torch.int32).to(dev)
+        ptok = ptok.repeat_interleave(repeat, dim=0).contiguous().to(dev)
+        patt = patt.repeat_interleave(repeat, dim=0).contiguous().to(dev)
+        assert plen.shape[0] == rows and ptok.shape == (rows, Tmax)
+        base, room = self._pws.ensure(L.ws_bytes("pa_decode_prefix_ws_bytes", ln.h(), rows, Tmax), dev)
+        L.check(L.lib().pa_decode_prefix_begin(ln.h(), L.ptr(plen), L.ptr(ptok), L.ptr(patt), C.c_void_p(base), C.c_int64(room),
+                                               L.stream()), "pa_decode_prefix_begin")
+        self._pkeep = (plen, ptok, patt)
+        self._rekey(prefix=self._pws.data_ptr())
+        score, lp = _buffers("pa_decode_prefix_buffers", ln.h(), 2)
+        return self._pws.view(score, rows * 4, torch.float32, (rows,)), self._pws.view(lp, rows * Tmax * 4, torch.float32, (rows, Tmax))
+
+    def _loop(self, Tmax, early_stop, all_done, min_steps=0, max_steps=None):
+        """The stepping loop of every mode: ``max_steps`` steps exactly, or up to Tmax with - ``early_stop`` - one look at the device
+        (``all_done()``: has every row finished) after every ``check_every`` replays once ``min_steps`` have run; that look is the
+        loop's only host sync.  Sets ``last_steps`` and returns the number of steps run."""
+        if max_steps is not None:
+            done = max(0, min(int(max_steps), Tmax))
+            self.steps(done)
+        else:
+            done = 0
+            while done < Tmax:
+                k = min(self.check_every, Tmax - done) if early_stop else Tmax - done
+                self.steps(k)
+                done += k
+                if early_stop and done >= min_steps and all_done():
+                    break
+        self.last_steps = done
+        return done
 
     def run(self, batch, max_len=None, early_stop=True, prefix=None, max_steps=None, strict_prefix=True):
         """Full greedy decode.  Returns (samples int64 [B, n], attach int64 [B, n]) with the
@@ -328,22 +350,17 @@ class GreedyDecoder:
         pbuf = self._prefix_begin(table, 1, B, Tmax)
         bufs = [self._lanes[i].buffers(hi - lo, Tmax) for i, (lo, hi) in enumerate(self._bounds)]
         min_steps = int(table[0].max()) if table is not None and B > 0 else 0
-        done = 0
-        n = Tmax
-        if max_steps is not None:
-            n = max(0, min(int(max_steps), Tmax))
-            self.steps(n)
-            done = n
-        while max_steps is None and done < Tmax:
-            k = min(self.check_every, Tmax - done) if early_stop else Tmax - done
-            self.steps(k)
-            done += k
-            if early_stop and done >= min_steps:
-                fe = torch.cat([b[2] for b in bufs]).cpu()
-                if bool((fe >= 0).all()):
-                    n = max(int(fe.max()) + 1, min_steps)
-                    break
-        self.last_steps = done
+        ends = None                                                   # every row's first END, once the host has seen them all
+
+        def all_done():
+            nonlocal ends
+            fe = torch.cat([b[2] for b in bufs]).cpu()
+            ends = fe if bool((fe >= 0).all()) else None
+            return ends is not None
+
+        n = self._loop(Tmax, early_stop, all_done, min_steps, max_steps)
+        if max_steps is None:
+            n = Tmax if ends is None else max(int(ends.max()) + 1, min_steps)
         self.last_prefix_scores = self.last_prefix_logprobs = None
         if pbuf is not None:
             self.last_prefix_scores, self.last_prefix_logprobs = pbuf[0].cpu(), pbuf[1][:, :n].cpu()
@@ -380,47 +397,21 @@ class BeamDecoder(GreedyDecoder):
         super().__init__(model, use_graph=use_graph, check_every=check_every, strict_graph=strict_graph, lanes=1)
         self.beam_size = int(beam_size)
         self.length_penalty = float(length_penalty)
+        self._repeat = self.beam_size
         model._ensure_handle()
         # the library validates K (1 <= K <= PA_BEAM_MAX): PlankHipError here rather than at the first run
-        need = int(L.lib().pa_decode_beam_ws_bytes(model._handle, self.beam_size, 1, 1, self.beam_size))
-        if need < 0:
-            L.check(need, "pa_decode_beam_ws_bytes")
-        self._bws = None
-        self._bkey = None
+        L.ws_bytes("pa_decode_beam_ws_bytes", model._handle, self.beam_size, 1, 1, self.beam_size)
 
-    def begin(self, batch, max_len=None):
-        """Encoder on the repeated batch + pa_decode_begin + pa_decode_beam_begin.  Returns (rows = B*K, Tmax)."""
-        m, K, lib = self.model, self.beam_size, L.lib()
-        rep = _repeat_batch(batch, K)
-        if m.unpad:
-            rep = m.prepare_batch(rep, groups=False)
-        rows, Tmax = super().begin(rep, max_len)
-        ln = self._lanes[0]
-        b = ln.keep[0]
-        need = int(lib.pa_decode_beam_ws_bytes(ln.h(), b.B, b.S, Tmax, K))
-        if need < 0:
-            L.check(need, "pa_decode_beam_ws_bytes")
-        if self._bws is None or self._bws.numel() < need + 256:
-            self._bws = torch.empty(need + 256, dtype=torch.uint8, device=m.flat_params.device)
-        base = (self._bws.data_ptr() + 255) // 256 * 256
-        L.check(lib.pa_decode_beam_begin(ln.h(), K, C.c_void_p(base), C.c_int64(self._bws.numel() - (base - self._bws.data_ptr())),
-                                         L.stream()), "pa_decode_beam_begin")
-        key = (self._bws.data_ptr(), K, ln.key)
-        if key != self._bkey:
-            self._graph = None
-        self._bkey = key
-        return rows, Tmax
+    def _mode_begin(self, lane, rows, Tmax):
+        K = self.beam_size
+        base, room = self._mws.ensure(L.ws_bytes("pa_decode_beam_ws_bytes", lane.h(), rows, lane.keep[0].S, Tmax, K),
+                                      self.model.flat_params.device)
+        L.check(L.lib().pa_decode_beam_begin(lane.h(), K, C.c_void_p(base), C.c_int64(room), L.stream()), "pa_decode_beam_begin")
+        return self._mws.data_ptr(), K
 
     def _beam_buffers(self, rows):
-        ptrs = [C.c_void_p() for _ in range(3)]
-        L.check(L.lib().pa_decode_beam_buffers(self._lanes[0].h(), *[C.byref(p) for p in ptrs]), "pa_decode_beam_buffers")
-        base = self._bws.data_ptr()
-
-        def view(p, dtype):
-            off = p.value - base
-            return self._bws[off: off + rows * 4].view(dtype)
-
-        return view(ptrs[0], torch.float32), view(ptrs[1], torch.int32), view(ptrs[2], torch.int32)
+        return [self._mws.view(p, rows * 4, dt, (rows,))
+                for p, dt in zip(_buffers("pa_decode_beam_buffers", self._lanes[0].h(), 3), (torch.float32, torch.int32, torch.int32))]
 
     def run(self, batch, max_len=None, early_stop=True, prefix=None):
         """Full beam search.  Returns a dict: ``tokens`` / ``attach`` int64 [B, n] (the best beam), ``beam_tokens`` /
@@ -439,14 +430,7 @@ class BeamDecoder(GreedyDecoder):
         B = rows // K
         tokens, attach, first_end = self._lanes[0].buffers(rows, Tmax)
         scores, _, finished = self._beam_buffers(rows)
-        done = 0
-        while done < Tmax:
-            k = min(self.check_every, Tmax - done) if early_stop else Tmax - done
-            self.steps(k)
-            done += k
-            if early_stop and bool((finished != 0).all().cpu()):
-                break
-        self.last_steps = done
+        self._loop(Tmax, early_stop, lambda: bool((finished != 0).all().cpu()))
         if pbuf is not None:                                          # the drawing's forced positions were scored on its row b*K
             pbuf = (pbuf[0].view(B, K)[:, :1].expand(B, K).reshape(rows),
                     pbuf[1].view(B, K, Tmax)[:, :1].expand(B, K, Tmax).reshape(rows, Tmax))
@@ -512,38 +496,17 @@ class SampleDecoder(GreedyDecoder):
         self.params = sample_params(num_samples, temperature, top_k, top_p, seed)
         self.num_samples = int(num_samples)
         self.length_penalty = float(length_penalty)
+        self._repeat = self.num_samples
         model._ensure_handle()
-        self._sws = None
-        self._skey = None
 
-    def begin(self, batch, max_len=None):
-        """Encoder on the repeated batch + pa_decode_begin + pa_decode_sample_begin.  Returns (rows = B*N, Tmax)."""
-        m, N, lib = self.model, self.num_samples, L.lib()
-        rep = _repeat_batch(batch, N)
-        if m.unpad:
-            rep = m.prepare_batch(rep, groups=False)
-        rows, Tmax = super().begin(rep, max_len)
-        ln = self._lanes[0]
-        need = int(lib.pa_decode_sample_ws_bytes(ln.h(), rows))
-        if need < 0:
-            L.check(need, "pa_decode_sample_ws_bytes")
-        if self._sws is None or self._sws.numel() < need + 256:
-            self._sws = torch.empty(need + 256, dtype=torch.uint8, device=m.flat_params.device)
-        base = (self._sws.data_ptr() + 255) // 256 * 256
-        L.check(lib.pa_decode_sample_begin(ln.h(), C.byref(self.params), C.c_void_p(base),
-                                           C.c_int64(self._sws.numel() - (base - self._sws.data_ptr())), L.stream()),
+    def _mode_begin(self, lane, rows, Tmax):
+        base, room = self._mws.ensure(L.ws_bytes("pa_decode_sample_ws_bytes", lane.h(), rows), self.model.flat_params.device)
+        L.check(L.lib().pa_decode_sample_begin(lane.h(), C.byref(self.params), C.c_void_p(base), C.c_int64(room), L.stream()),
                 "pa_decode_sample_begin")
-        key = (self._sws.data_ptr(), N, ln.key)
-        if key != self._skey:
-            self._graph = None
-        self._skey = key
-        return rows, Tmax
+        return self._mws.data_ptr(), self.num_samples
 
     def _scores(self, rows):
-        p = C.c_void_p()
-        L.check(L.lib().pa_decode_sample_buffers(self._lanes[0].h(), C.byref(p)), "pa_decode_sample_buffers")
-        off = p.value - self._sws.data_ptr()
-        return self._sws[off: off + rows * 4].view(torch.float32)
+        return self._mws.view(_buffers("pa_decode_sample_buffers", self._lanes[0].h(), 1)[0], rows * 4, torch.float32, (rows,))
 
     def run(self, batch, max_len=None, early_stop=True, seed=None, prefix=None):
         """N samples per drawing.  ``seed``: this call's seed instead of the decoder's (pa_decode_sample_set: the captured step is
@@ -567,12 +530,5 @@ class SampleDecoder(GreedyDecoder):
         B = rows // N
         tokens, attach, first_end = self._lanes[0].buffers(rows, Tmax)
         scores = self._scores(rows)
-        done = 0
-        while done < Tmax:
-            k = min(self.check_every, Tmax - done) if early_stop else Tmax - done
-            self.steps(k)
-            done += k
-            if early_stop and bool((first_end >= 0).all().cpu()):
-                break
-        self.last_steps = done
+        self._loop(Tmax, early_stop, lambda: bool((first_end >= 0).all().cpu()))
         return _ranked("sample", tokens, attach, first_end, scores, first_end >= 0, B, N, Tmax, self.length_penalty, pbuf)

@@ -151,7 +151,7 @@ class PlankModel(nn.Module):
         if isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= int(beam_size) <= 16:
             raise ValueError(f"BEAM_SIZE must be an integer in [1, 16], got {beam_size!r}")
         self.beam_size, self.length_penalty = int(beam_size), float(length_penalty)
-        self._beam_decoders = {}
+        self._mode_decoders = {}                               # beam / sampling decoders by their settings (_decoder_for)
         # or sampling with this many samples per drawing (decode.SampleDecoder, 1 <= N <= 64; 0 = off)
         from .decode import sample_params
         off = num_samples == 0 and isinstance(num_samples, int) and not isinstance(num_samples, bool)
@@ -160,7 +160,6 @@ class PlankModel(nn.Module):
             raise ValueError(f"NUM_SAMPLES ({num_samples}) and BEAM_SIZE ({beam_size}) > 1 exclude each other")
         self.num_samples = int(num_samples)
         self.sample_cfg = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(sample_seed))
-        self._sample_decoders = {}
         self.compute_mode = compute_dtype                      # what the caller asked for
         self.split3 = compute_dtype == "x3"
         self.compute_dtype = "f32" if self.split3 else compute_dtype     # storage / kernel dtype: 'x3' is f32 with split products
@@ -319,8 +318,7 @@ class PlankModel(nn.Module):
             self._handle = None
         self._ws = None
         self._decoder = None
-        self._beam_decoders = {}
-        self._sample_decoders = {}
+        self._mode_decoders = {}
         self._drop_x3_cache()
 
     def _drop_x3_cache(self):
@@ -877,16 +875,10 @@ class PlankModel(nn.Module):
             return self.beam_search(batch, self.beam_size, self.length_penalty, prefix=prefix)
         if self.num_samples >= 1:
             return self.sample(batch, self.num_samples, length_penalty=self.length_penalty, prefix=prefix, **self.sample_cfg)
-        from .decode import GreedyDecoder
-        self._ensure_handle()
-        self._refresh_shadow()
-        if self._decoder is None:
-            self._decoder = GreedyDecoder(self)
-        output, attach = self._decoder.run(batch, prefix=prefix)
-        out = self._eval_dict(batch, output, attach)
-        if prefix is not None:
-            out["prefix_scores"], out["prefix_logprobs"] = self._decoder.last_prefix_scores, self._decoder.last_prefix_logprobs
-        return out
+        dec = self._decoder_for()
+        output, attach = dec.run(batch, prefix=prefix)
+        return self._decode_dict(batch, {"tokens": output, "attach": attach, "prefix_scores": dec.last_prefix_scores,
+                                         "prefix_logprobs": dec.last_prefix_logprobs}, prefix)
 
     def score(self, batch, tokens=None, attach=None, lengths=None):
         """Log-likelihood of given sequences under the model, on the GPU: the greedy decode step with every position forced
@@ -901,9 +893,7 @@ class PlankModel(nn.Module):
         at its step (attach >= t, or t < 5) scores -inf.  Returns ``scores`` f32 [B] (sum over the row's positions up to and
         including its first END), ``logprobs`` f32 [B, n] (per position, n = max(lengths); 0 beyond a row's length) and
         ``lengths`` int64 [B]."""
-        from .decode import GreedyDecoder
-        self._ensure_handle()
-        self._refresh_shadow()
+        dec = self._decoder_for()
         if tokens is None:
             tokens = batch["output_value"]
             if attach is None and "output_label" in batch:
@@ -914,9 +904,6 @@ class PlankModel(nn.Module):
             prefix["attach"] = attach
         if lengths is not None:
             prefix["lengths"] = lengths
-        if self._decoder is None:
-            self._decoder = GreedyDecoder(self)
-        dec = self._decoder
         table = dec._check_prefix(prefix, batch, None, strict=False)
         n = int(table[0].max()) if table[0].numel() else 0
         written, _ = dec.run(batch, early_stop=False, prefix=prefix, max_steps=n, strict_prefix=False)
@@ -950,6 +937,29 @@ class PlankModel(nn.Module):
             prefix["attach"] = torch.where(label >= self.vocab_size, label - self.vocab_size, torch.full_like(label, -1))
         return self.eval_step(batch, prefix=prefix)
 
+    def _decoder_for(self, key=None, build=None):
+        """The way into a decoder: a bound handle, fresh bf16 shadows, and the cached decoder - the greedy one (``_decoder``; None
+        = build one on next use) or the beam / sampling decoder of the settings ``key``, from ``build()`` on first use."""
+        from .decode import GreedyDecoder
+        self._ensure_handle()
+        self._refresh_shadow()
+        if key is None:
+            if self._decoder is None:
+                self._decoder = GreedyDecoder(self)
+            return self._decoder
+        dec = self._mode_decoders.get(key)
+        if dec is None:
+            dec = self._mode_decoders[key] = build()
+        return dec
+
+    def _decode_dict(self, batch, r, prefix):
+        """The eval_step dict of a decoder's result ``r``: the best row's parse, then what the mode adds - ``scores``, the prefix
+        keys when a prefix was given, ``sample_*``."""
+        out = self._eval_dict(batch, r["tokens"], r["attach"])
+        keys = ["scores"] + (["prefix_scores", "prefix_logprobs"] if prefix is not None else []) + ["sample_tokens", "sample_attach"]
+        out.update((k, r[k]) for k in keys if k in r)
+        return out
+
     def _eval_dict(self, batch, output, attach):
         predicts, groundtruths = [], []
         for i in range(output.shape[0]):
@@ -961,18 +971,8 @@ class PlankModel(nn.Module):
         """Beam-search decode (decode.BeamDecoder): the eval_step dict of the best beam of every drawing plus ``scores``
         [B, K], the cumulative log-probabilities of all beams in final-ranking order.  ``prefix``: as in eval_step, per drawing."""
         from .decode import BeamDecoder
-        self._ensure_handle()
-        self._refresh_shadow()
-        key = (int(beam_size), float(length_penalty))
-        dec = self._beam_decoders.get(key)
-        if dec is None:
-            dec = self._beam_decoders[key] = BeamDecoder(self, beam_size, length_penalty)
-        r = dec.run(batch, prefix=prefix)
-        out = self._eval_dict(batch, r["tokens"], r["attach"])
-        out["scores"] = r["scores"]
-        if prefix is not None:
-            out["prefix_scores"], out["prefix_logprobs"] = r["prefix_scores"], r["prefix_logprobs"]
-        return out
+        dec = self._decoder_for(("beam", int(beam_size), float(length_penalty)), lambda: BeamDecoder(self, beam_size, length_penalty))
+        return self._decode_dict(batch, dec.run(batch, prefix=prefix), prefix)
 
     def sample(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0, prefix=None):
         """Seeded sampling decode (decode.SampleDecoder): the eval_step dict of the best sample of every drawing (by score /
@@ -980,19 +980,9 @@ class PlankModel(nn.Module):
         [B, N, n], samples in final-ranking order.  The same seed and batch give the same samples on every call.  ``prefix``: as in
         eval_step, per drawing."""
         from .decode import SampleDecoder
-        self._ensure_handle()
-        self._refresh_shadow()
-        key = (int(num_samples), float(temperature), int(top_k), float(top_p), float(length_penalty))
-        dec = self._sample_decoders.get(key)
-        if dec is None:
-            dec = self._sample_decoders[key] = SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, length_penalty)
-        r = dec.run(batch, seed=seed, prefix=prefix)
-        out = self._eval_dict(batch, r["tokens"], r["attach"])
-        out["scores"] = r["scores"]
-        if prefix is not None:
-            out["prefix_scores"], out["prefix_logprobs"] = r["prefix_scores"], r["prefix_logprobs"]
-        out["sample_tokens"], out["sample_attach"] = r["sample_tokens"], r["sample_attach"]
-        return out
+        key = ("sample", int(num_samples), float(temperature), int(top_k), float(top_p), float(length_penalty))
+        dec = self._decoder_for(key, lambda: SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, length_penalty))
+        return self._decode_dict(batch, dec.run(batch, seed=seed, prefix=prefix), prefix)
 
     def forward(self, batch):
         """reference models.py:325-330."""

@@ -1,7 +1,7 @@
 """Greedy step without a prefix table, with an all-free table, and fully forced (the scorer), in one process.
 
 For each row count (B rows, Tmax 128, bf16, the bench decode model) under graph replay: greedy without a table (the step as it was
-before prefixes existed), greedy with a table of plen = 0 (what carrying the table and the unfused tail cost) and every position
+before prefixes existed), greedy with a table of plen = 0 (what carrying the table costs) and every position
 forced to the table-less run's own output (what PlankModel.score runs); the time is that of the Tmax steps alone (encoder,
 pa_decode_begin and pa_decode_prefix_begin excluded), best of `REPS` runs, the three alternating.
 `python tools/prefix_time.py [B ...]` (default: 16 64 256).  One row count under
