@@ -153,6 +153,20 @@ int pa_gemm_recorded(pa_gemm_args* out, int32_t cap);
 int pa_gemm_recorded_kinds(int32_t* out, int32_t cap);
 /* -1 for launches made by pa_gemm; members of one pa_gemm_group launch share an id >= 0 (consecutive entries). */
 int pa_gemm_recorded_groups(int32_t* out, int32_t cap);
+/* Dry run of the dispatch: the status pa_gemm(args) - or, with `ext`, pa_gemm_norm_a(args, ext) - would return before its launch
+ * (0 where the real call launches; a launch error or the check of a deferred split-K epilogue, which follow the launch, are not
+ * predicted) and, when that is 0, the kernel family (PA_GEMM_KIND_*), tile, grid, block size and effective split-K it would use.
+ * Made by the same selection function the real calls run, under the same PA_GEMM_* switches and reserved CUs.  It launches nothing,
+ * needs no GPU and never dereferences the operand pointers: only their values count, for the alignment rules.  It plans the plain
+ * path and ignores the bf16x3 mode (where an f32 product is re-planned as a bf16 one over 3 K).  pa_gemm_group has no dry run. */
+typedef struct {
+    int32_t kind;               /* PA_GEMM_KIND_* ("tall" tiles report PA_GEMM_KIND_WIDE, as the recorder does) */
+    int32_t tile_h, tile_w;
+    int32_t grid, block;
+    int32_t splitk;             /* non-empty contraction slices */
+    int32_t units;              /* slots of the unit enumeration the grid strides over (padding of the XCD interleave included) */
+    int32_t pad_;
+} pa_gemm_plan_info;
 
 /* Linear + bias (+ dropout) + residual + LayerNorm in one launch, for the post-norm sublayer tails of the reference's
  * encoder / decoder layers (torch nn/modules/transformer.py `x = norm(x + dropout(sublayer(x)))`, used by
@@ -191,6 +205,8 @@ typedef struct {
 int pa_ln_fold_weights(void* Wf, float* u, float* v, const float* W, const float* bias, const float* gamma, const float* beta,
                        int32_t N, int32_t K, void* stream);
 int pa_gemm_norm_a(const pa_gemm_args* args, const pa_gemm_norm_ext* ext, void* stream);
+/* the dry run of pa_gemm (ext NULL) / pa_gemm_norm_a: see pa_gemm_plan_info above */
+int pa_gemm_plan(const pa_gemm_args* args, const pa_gemm_norm_ext* ext, pa_gemm_plan_info* out);
 /* The same fold in exact f32 (the f32 greedy-decode step, round 4): pa_ln_fold_weights_f32 writes Wf = W gamma as f32; pa_gemm_norm_a
  * with in_dtype = out_dtype = PA_F32 takes f32 rows A (ext->zf = the same rows: the statistics source), Wf, u, v and writes f32.
  * At most 512 rows, K = 512 (PA_ESHAPE otherwise). */

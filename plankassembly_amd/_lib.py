@@ -42,6 +42,12 @@ class GemmNormExt(C.Structure):
                 ("zf", C.c_void_p), ("ldzf", C.c_int32), ("y_f32", C.c_int32)]
 
 
+class GemmPlanInfo(C.Structure):
+    """include/plank_hip.h pa_gemm_plan_info: what pa_gemm_plan (the dry run of the GEMM dispatch) reports."""
+    _fields_ = [("kind", C.c_int32), ("tile_h", C.c_int32), ("tile_w", C.c_int32), ("grid", C.c_int32),
+                ("block", C.c_int32), ("splitk", C.c_int32), ("units", C.c_int32), ("pad_", C.c_int32)]
+
+
 class GemmLnArgs(C.Structure):
     _fields_ = [("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("R", C.c_void_p),
                 ("Z", C.c_void_p), ("Y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
@@ -102,6 +108,7 @@ def lib():
         sig = {
             "pa_version": (I, []),
             "pa_gemm": (I, [P, P]),
+            "pa_gemm_plan": (I, [P, P, P]),
             "pa_gemm_ln": (I, [P, P]),
             "pa_gemm_ln_max_rows": (I, []),
             "pa_set_reserved_cus": (I, [I]),

@@ -18,6 +18,7 @@
 //    and writes whole 128/256-byte row segments with 8/16-byte vector stores (bias / ReLU / ReLU-backward gate /
 //    dropout / residual applied on the way).
 #include <stdlib.h>
+#include <climits>
 #include <atomic>
 #include <new>
 #include <mutex>
@@ -502,9 +503,6 @@ __global__ __launch_bounds__(NT, OCC) void gemm_kernel(GemmP p) {
                     }
                 }
                 TR(23);
-#ifdef PA_PAIR_ABL_NOSTORE                 // timing ablation (wrong results): the fast path's output stores removed
-                if (p.alpha == 123.f)
-#endif
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
                     const int m = mp + it * 4;
@@ -696,9 +694,7 @@ __global__ __launch_bounds__(NT, OCC) void gemm_kernel(GemmP p) {
                 else fetch(cur, t + 1, buf ^ 1);
             }
             TR(2);
-#ifndef PA_PAIR_NO_EPI_PREFETCH
             if (last_k) prefetch_epi(cur);
-#endif
             compute(buf);
             TR(3);
             if (last_k) {
@@ -1006,21 +1002,12 @@ __global__ __launch_bounds__(NT, 1) void gemm3_kernel(PT prm) {
     };
     using NoQ = std::integral_constant<int, -1>;
 
-    // Residual / gate tiles of the block's FIRST unit, requested before its first K tile (see the prefetch below): in a
-    // single-round launch - most launches of the training step - every block would otherwise start these loads only after
-    // its K loop, with nothing left to hide their latency behind (measured in round 2: 5.9 k of a 15.5 k-cycle epilogue at K = 512).
-    // OFF since round 4 (-DPA_RING_PREFETCH_RES restores it): the 64 registers held across the K loop pushed the kernel to 256
-    // VGPRs + 203 AGPRs used as spill space - every item outside the hot loop carried 60-130 v_accvgpr copies (+600 cycles per
-    // item, the "last four items of a unit" of profiles/r02_gemm_block_timeline.txt).  Without it: 208 VGPRs + 128 AGPRs, and
-    // 12.15 / 15.66 / 19.12 us against 12.51 / 16.10 / 19.95 us per launch WITH a residual (7 940 x 512, K 512 / 1 024 / 1 536),
-    // 10.83 against 11.28 us without; train step -0.02 ms (three interleaved A/B runs).
-    u32x2 pre_res[2][8], pre_aux[2][8];
-    bool pre_live = false;
+    // (No prefetch of the first unit's residual / gate tiles before the K loop here: it was measured and removed in round 4 - the 64
+    //  registers held across the K loop pushed the kernel to 256 VGPRs + 203 AGPRs used as spill space; without it 208 VGPRs + 128
+    //  AGPRs and 12.15 / 15.66 / 19.12 us against 12.51 / 16.10 / 19.95 us per launch with a residual, 7 940 x 512, K 512 / 1 024 / 1 536.)
     // ---- epilogue ------------------------------------------------------------------------------------------------
     auto epilogue = [&](const Unit& un) {
         char* stage = smem + NSTG * STAGE + wave * EPI;
-        const bool pre = pre_live;
-        pre_live = false;
         const bool slab = pc.splitk > 1;
         const size_t cbase = slab ? (size_t)un.z * pc.M * pc.ldc : (size_t)un.b * pc.sC;
         const int mw = un.tile_m * BM + wm * 64, nw = un.tile_n * BN + wn * 64;
@@ -1060,12 +1047,8 @@ __global__ __launch_bounds__(NT, 1) void gemm3_kernel(PT prm) {
             }
             if (fast) {
                 f32x4 res[NIT], gate[NIT];
-                auto widen = [](const u32x2& u) { f32x4 r; r[0] = bf16_lo(u[0]); r[1] = bf16_hi(u[0]); r[2] = bf16_lo(u[1]); r[3] = bf16_hi(u[1]); return r; };
                 if (has_res) {
-                    if (pre) {
-#pragma unroll
-                        for (int it = 0; it < NIT; ++it) res[it] = widen(pre_res[pass][it]);
-                    } else if (out_f32) {
+                    if (out_f32) {
 #pragma unroll
                         for (int it = 0; it < NIT; ++it) {
                             const size_t ro = (size_t)un.b * pc.sR + (size_t)min(mp + it * 4, pc.M - 1) * pc.ldr + n;
@@ -1080,15 +1063,10 @@ __global__ __launch_bounds__(NT, 1) void gemm3_kernel(PT prm) {
                     }
                 }
                 if (has_aux) {
-                    if (pre) {
 #pragma unroll
-                        for (int it = 0; it < NIT; ++it) gate[it] = widen(pre_aux[pass][it]);
-                    } else {
-#pragma unroll
-                        for (int it = 0; it < NIT; ++it) {
-                            const size_t ao = (size_t)un.b * pc.sAux + (size_t)min(mp + it * 4, pc.M - 1) * pc.ldaux + n;
-                            gate[it] = ld4<T>(reinterpret_cast<const T*>(pc.aux) + ao);
-                        }
+                    for (int it = 0; it < NIT; ++it) {
+                        const size_t ao = (size_t)un.b * pc.sAux + (size_t)min(mp + it * 4, pc.M - 1) * pc.ldaux + n;
+                        gate[it] = ld4<T>(reinterpret_cast<const T*>(pc.aux) + ao);
                     }
                 }
                 if (!slab) {
@@ -1240,26 +1218,6 @@ __global__ __launch_bounds__(NT, 1) void gemm3_kernel(PT prm) {
     cmp_enter(blockIdx.x);
     if (cc_u >= total_units) return;
     dma_enter(cc_u, &cun);
-    // Prefetch of the first unit's residual / gate tiles (bf16, vector path).  Issued BEFORE the first DMA instruction: loads
-    // return in order, so the hand-counted `vmcnt` waits of the K loop (which count DMA instructions only) stay exact - these
-    // loads are older than every DMA and are retired by the first of those waits, together with the first K tile.
-#ifdef PA_RING_PREFETCH_RES
-    if constexpr (!GROUP) {
-        const int nw0 = cun.tile_n * BN + wn * 64;
-        if (pc.splitk <= 1 && pc.vec_ok && nw0 + 64 <= pc.N && pc.out_dtype != PA_F32 && (pc.R != nullptr || pc.aux != nullptr)) {
-            pre_live = true;
-            const int mw0 = cun.tile_m * BM + wm * 64, n0 = nw0 + (lane & 15) * 4, rs = lane >> 4;
-#pragma unroll
-            for (int pass = 0; pass < 2; ++pass)
-#pragma unroll
-                for (int it = 0; it < 8; ++it) {
-                    const int m = min(mw0 + pass * 32 + rs + it * 4, pc.M - 1);
-                    if (pc.R) pre_res[pass][it] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16*>(pc.R) + (size_t)cun.b * pc.sR + (size_t)m * pc.ldr + n0);
-                    if (pc.aux) pre_aux[pass][it] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16*>(pc.aux) + (size_t)cun.b * pc.sAux + (size_t)m * pc.ldaux + n0);
-                }
-        }
-    }
-#endif
     int pending = 0;                            // items issued and not yet finished by the MFMAs
     auto issue = [&]() {
         DMA(fetch(sd));
@@ -1418,11 +1376,6 @@ __global__ __launch_bounds__(NT, 2) void gemm3s_kernel(GemmP p) {
     for (int s_ = 0; s_ < 4; ++s_) xs[s_] = (uint32_t)((((2 * s_ + half) ^ sw) & 7) << 4);
     const uint32_t fa_off = (wm * 32 + (lane & 31)) * RB, fb_off = (wn * 32 + (lane & 31)) * RB + TILE_BYTES;
 #define PA_RD128(dst, addr) asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr))
-    auto frag = [&](u32x4 (&f)[2], uint32_t st, int s_) {
-        const uint32_t a0 = st + fa_off + xs[s_], b0 = st + fb_off + xs[s_];
-        PA_RD128(f[0], a0); PA_RD128(f[1], b0);
-    };
-    auto wait_frag = [&](u32x4 (&f)[2]) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1])); };
 
     // residual / gate tile of the block's first unit, requested before its first K tile (as in gemm3_kernel)
     u32x2 pre_res[4], pre_aux[4];
@@ -1580,12 +1533,10 @@ __global__ __launch_bounds__(NT, 2) void gemm3s_kernel(GemmP p) {
                 }
             }
         }
-#ifndef PA_G3S_OLD
         // every path "uses" the bias: a path that loaded it and stored nothing (a wave past the last row) would leave the load
         // pending in the COMPILER's scoreboard, and it would guard the K loop's first temporary with `s_waitcnt vmcnt(0)` - the
         // whole ring - on every item
         asm volatile("" :: "v"(bias[0]), "v"(bias[1]), "v"(bias[2]), "v"(bias[3]));
-#endif
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     };
@@ -1693,18 +1644,15 @@ __global__ __launch_bounds__(NT, 2) void gemm3s_kernel(GemmP p) {
                 }
             }
         }
-#ifndef PA_G3S_OLD
         // a wait the COMPILER sees (vmcnt 0, other counters untouched): without it its scoreboard carries this block's loads into
         // the K loop (the hand-counted waits there are inline assembly) and it puts its own `s_waitcnt vmcnt(0)` in front of every
         // item's DMA - every item then waited for the whole ring, one memory round trip per item
         __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
     }
     wait_items(pending - 1);
     __builtin_amdgcn_s_barrier();
     PA_TR3(2);
     int sc = 0;
-#ifndef PA_G3S_OLD
     // One item = one 64-deep K tile = four MFMAs per wave.  With ONE wave per SIMD nothing else hides an LDS round trip, so the
     // fragments are requested a WHOLE item ahead: behind the item's barrier (the next item has landed) the pair of reads of the
     // next item's k-step s goes out right after the MFMA of this item's k-step s, into the registers that MFMA has just read -
@@ -1749,54 +1697,6 @@ __global__ __launch_bounds__(NT, 2) void gemm3s_kernel(GemmP p) {
         if (!has_next) break;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(F[0]), "+v"(F[1]), "+v"(F[2]), "+v"(F[3]), "+v"(F[4]), "+v"(F[5]), "+v"(F[6]), "+v"(F[7]));
-#else
-    u32x4 F0[2], F1[2];
-    frag(F0, lds0, 0);
-    auto item = [&](auto HOT_) -> bool {
-        constexpr bool HOT = decltype(HOT_)::value;
-        const uint32_t st = lds0 + sc * STAGE;
-        __builtin_amdgcn_s_barrier();           // barrier A: previous item's stage may be refilled
-        if constexpr (!HOT) { if (cd_u < p.units) issue(); }
-        wait_frag(F0); acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&F0[1]), *reinterpret_cast<const bf16x8*>(&F0[0]), acc, 0, 0, 0);
-        frag(F1, st, 1); if constexpr (HOT) { fetch_q(sd, Q0{}); fetch_q(sd, Q1{}); }
-        wait_frag(F1); acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&F1[1]), *reinterpret_cast<const bf16x8*>(&F1[0]), acc, 0, 0, 0);
-        frag(F0, st, 2); if constexpr (HOT) { fetch_q(sd, Q2{}); fetch_q(sd, Q3{}); fetch_done(); sd = (sd + 1) & (NSTG - 1); ++cd_t; }
-        wait_frag(F0); acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&F0[1]), *reinterpret_cast<const bf16x8*>(&F0[0]), acc, 0, 0, 0);
-        frag(F1, st, 3);
-        const bool has_next = HOT || pending >= 2;
-        wait_frag(F1);
-        if (has_next) {
-            if constexpr (HOT) wait_items(2); else wait_items(pending - 2);
-            __builtin_amdgcn_s_barrier();       // barrier B: the next item has landed for every wave
-            frag(F0, lds0 + ((sc + 1) & (NSTG - 1)) * STAGE, 0);
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&F1[1]), *reinterpret_cast<const bf16x8*>(&F1[0]), acc, 0, 0, 0);
-        sc = (sc + 1) & (NSTG - 1);
-        if constexpr (HOT) { ++cc_t; return true; }
-        else {
-            if (++cc_t >= nt) {
-                PA_TR3(3);
-                epilogue(cun);
-#ifdef PA_GEMM_TRACE3
-                PA_TR3(5);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-                PA_TR3(4);
-                cc_u += ustride; cc_t = 0;
-                if (cc_u < p.units) unit_of(cc_u, cun);
-            }
-            --pending;
-            return has_next;
-        }
-    };
-#pragma unroll 1
-    while (true) {
-        int hot = (pending == 3 && cd_u == cc_u) ? (nt - cd_t - 1) : 0;
-#pragma unroll 1
-        for (; hot > 0; --hot) item(std::true_type{});
-        if (!item(std::false_type{})) break;
-    }
-#endif
 #undef PA_RD128
 }
 
@@ -2406,18 +2306,112 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmP p, const float
     }
 }
 
+// ---- host side: runtime switches and the helpers every launch site shares ---------------------------------------------------
+// Every runtime switch of the GEMM dispatch: environment, read once per process, the defaults are the measured choices (the
+// comments at the kernels and in plan_gemm say what was measured).  PA_RESERVE_CUS is not here: pa_set_reserved_cus changes it.
+struct GemmSwitches {
+    int nst;                       // PA_GEMM_NST: stages of the pair kernel, 0 auto, 1 / 3 forced
+    int epre;                      // PA_GEMM_EPRE: 0 turns the pair kernel's epilogue-prefetch variant off
+    int bk;                        // PA_GEMM_BK: bf16 K tile of the pair kernel, 64 or 32
+    int noglds;                    // PA_GEMM_NOGLDS: 1 = no direct-to-LDS loads (pair kernel only then)
+    int grid;                      // PA_GEMM_GRID: blocks of a pair launch per 256 CUs (0 = one block per unit)
+    int dbg;                       // PA_GEMM_DBG: timing-ablation bits of -DPA_GEMM_ABLATE builds (wrong results)
+    int v3;                        // PA_GEMM_V3: ring kernels 0 never, 1 single-round launches, 2 every eligible launch
+    int small_on, small_max, small_max_k512;        // PA_GEMM_SMALL, PA_GEMM_SMALL_MAX, PA_GEMM_SMALL_MAX_K512
+    int wide, tall;                // PA_GEMM_WIDE: 0 never, 1 every eligible launch, 2 single round; PA_GEMM_TALL: opt-in
+    int skinny, skinny_rows, skinny_rows_f32;       // PA_GEMM_SKINNY: 0 never, 1 f32 only, 2 bf16 too; PA_GEMM_SKINNY_ROWS[_F32]
+    int big, big_minm, big_minn, big_tn;            // PA_GEMM_BIG: 0 never, 1 / 2 tile-width rule; PA_GEMM_BIG_MINM / _MINN / _TN
+    int dw_xcd;                    // PA_DW_XCD: 0 = plain slot order in the grouped weight-gradient launch
+};
+const GemmSwitches& gemm_switches() {
+    static const GemmSwitches sw = [] {
+        auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+        GemmSwitches s;
+        s.nst = env("PA_GEMM_NST", 0);
+        s.epre = env("PA_GEMM_EPRE", 1);
+        s.bk = env("PA_GEMM_BK", 64);
+        s.noglds = env("PA_GEMM_NOGLDS", 0);
+        s.grid = env("PA_GEMM_GRID", s.nst == 1 ? 1024 : s.bk == 32 ? 768 : 512);      // (two blocks per CU by default)
+        s.dbg = env("PA_GEMM_DBG", 0);
+        s.v3 = env("PA_GEMM_V3", 1);
+        s.small_on = env("PA_GEMM_SMALL", 1);
+        s.small_max = env("PA_GEMM_SMALL_MAX", 128);
+        s.small_max_k512 = env("PA_GEMM_SMALL_MAX_K512", 192);
+        s.wide = env("PA_GEMM_WIDE", 2);
+        s.tall = env("PA_GEMM_TALL", 0);
+        s.skinny = env("PA_GEMM_SKINNY", 2);
+        s.skinny_rows = env("PA_GEMM_SKINNY_ROWS", 512);
+        s.skinny_rows_f32 = env("PA_GEMM_SKINNY_ROWS_F32", env("PA_GEMM_SKINNY_ROWS", 2048));
+        s.big = env("PA_GEMM_BIG", 0);
+        s.big_minm = env("PA_GEMM_BIG_MINM", 4096);
+        s.big_minn = env("PA_GEMM_BIG_MINN", 256);
+        s.big_tn = env("PA_GEMM_BIG_TN", 0);
+        s.dw_xcd = env("PA_DW_XCD", 1);
+        return s;
+    }();
+    return sw;
+}
+
+// Number of NON-EMPTY contraction slices for a requested split of `nt` K tiles: slices are whole tiles, and rounding the slice
+// length up can leave trailing slices empty - those must not exist, their slabs would never be written.
+inline int eff_splitk(int nt, int sk) {
+    if (sk > nt) sk = nt;
+    if (sk < 1) sk = 1;
+    const int per = (nt + sk - 1) / sk;
+    return (nt + per - 1) / per;
+}
+
+// Tile counts and unit order of one launch.  UNITS_XCD: units interleave the row tiles over the eight XCDs (rows padded to a multiple
+// of 8) unless there are fewer than 8 row tiles - the interleave would leave most units empty; UNITS_XCD_ALWAYS: even then.
+enum UnitOrder { UNITS_PLAIN, UNITS_XCD, UNITS_XCD_ALWAYS };
+struct Tiling { int tiles_m, tiles_n, tiles_m_pad, plain_order, units; };
+inline Tiling tiling_of(int M, int N, int tile_h, int tile_w, int batch_times_splitk, UnitOrder order) {
+    Tiling t;
+    t.tiles_m = (M + tile_h - 1) / tile_h;
+    t.tiles_n = (N + tile_w - 1) / tile_w;
+    t.plain_order = order == UNITS_PLAIN || (order == UNITS_XCD && t.tiles_m < 8);
+    t.tiles_m_pad = t.plain_order ? t.tiles_m : (t.tiles_m + 7) / 8 * 8;
+    t.units = t.tiles_m_pad * t.tiles_n * batch_times_splitk;
+    return t;
+}
+inline void set_tiling(GemmP& p, const Tiling& t) {
+    p.tiles_m = t.tiles_m; p.tiles_n = t.tiles_n; p.tiles_m_pad = t.tiles_m_pad; p.plain_order = t.plain_order; p.units = t.units;
+}
+inline void set_tiling(GemmP& p, int tile_h, int tile_w, int batch_times_splitk, UnitOrder order) {
+    set_tiling(p, tiling_of(p.M, p.N, tile_h, tile_w, batch_times_splitk, order));
+}
+
+// 4-element vector accesses of an epilogue on `q` (element size esz, row stride ld, batch stride sb) are naturally aligned
+inline bool vec_ok(const void* q, long long ld, long long sb, int esz) {
+    return !q || ((reinterpret_cast<uintptr_t>(q) % (4 * esz) == 0) && (ld % 4 == 0) && (sb % 4 == 0));
+}
+
+// operands, shapes, strides and epilogue scalars of an argument block (everything a kernel reads that no launch site decides)
+inline void fill_operands(GemmP& p, const pa_gemm_args& a) {
+    p.A = a.A; p.B = a.B; p.C = a.C; p.bias = a.bias; p.R = a.R; p.aux = a.aux;
+    p.M = a.M; p.N = a.N; p.K = a.K;
+    p.lda = a.lda; p.ldb = a.ldb; p.ldc = a.ldc; p.ldr = a.ldr; p.ldaux = a.ldaux;
+    p.sA = a.sA; p.sB = a.sB; p.sC = a.sC; p.sR = a.sR; p.sAux = a.sAux; p.sBias = a.sBias;
+    p.batch = a.batch;
+    p.alpha = a.alpha; p.relu = a.relu; p.aux_scale = a.aux_scale;
+    p.drop_thr = a.drop_p > 0.f ? (uint32_t)((double)a.drop_p * 4294967296.0) : 0u;    // keep <=> 32-bit product >= thr (pa_device.h drop_keep_rc)
+    p.drop_scale = (float)(1.0 / (1.0 - (double)p.drop_thr / 4294967296.0));
+    p.drop_seed = a.drop_seed;
+    p.out_dtype = a.out_dtype;
+}
+
 template <typename T, int BK_, int OCC, bool A_KC, bool B_KC>
 int launch_t(const GemmP& p, bool aligned, bool glds, dim3 grid, hipStream_t st) {
     constexpr bool CAN_TR = sizeof(T) == 2 && BK_ == 64 && !(A_KC && B_KC);
     constexpr bool ALLD = (A_KC && B_KC) || CAN_TR;        // both operands DMA'd when glds is usable
-    static const int dbg_nst = getenv("PA_GEMM_NST") ? atoi(getenv("PA_GEMM_NST")) : 0;   // 0 auto, 2 / 3 forced
-    const bool deep = ALLD && sizeof(T) == 2 && BK_ == 64 && dbg_nst == 3;
-    const bool flat = ALLD && sizeof(T) == 2 && BK_ == 64 && dbg_nst == 1;
+    const GemmSwitches& sw = gemm_switches();
+    const bool deep = ALLD && sizeof(T) == 2 && BK_ == 64 && sw.nst == 3;
+    const bool flat = ALLD && sizeof(T) == 2 && BK_ == 64 && sw.nst == 1;
     if (aligned && glds) {
         if constexpr (ALLD && sizeof(T) == 4 && BK_ == 16) {
             // f32, both operands k-contiguous: a 3-stage ring (PA_GEMM_NST=3) was measured and LOSES - 33.9 vs 31.3 ms per f32
             // train step (round 4): these launches are not waiting for their K tiles.  Opt-in only.
-            if (dbg_nst == 3) {
+            if (sw.nst == 3) {
                 PA_LAUNCH((gemm_kernel<T, BK_, 2, A_KC, B_KC, true, true, false, 3>), grid, dim3(NT), 0, st, p);
                 return 0;
             }
@@ -2436,8 +2430,7 @@ int launch_t(const GemmP& p, bool aligned, bool glds, dim3 grid, hipStream_t st)
             // bf16 residual / gate rows, bf16 output: the variant that fetches them under the last K tile.  Back-to-back launches at
             // 8704 rows, with a residual: 512 x 512 16.4 -> 15.5 us, 512 x 1024 24.4 -> 21.5, 512 x 1536 31.0 -> 27.6, 1024 x 512
             // 31.1 -> 24.4, 1536 x 512 35.8 -> 28.9; strided weight 512 x 1536 38.2 -> 36.4.  PA_GEMM_EPRE=0 turns it off.
-            static const bool epre_on = !(getenv("PA_GEMM_EPRE") && atoi(getenv("PA_GEMM_EPRE")) == 0);
-            if (epre_on && (p.R || p.aux) && p.splitk == 1 && p.out_dtype != PA_F32 && p.vec_ok) {
+            if (sw.epre && (p.R || p.aux) && p.splitk == 1 && p.out_dtype != PA_F32 && p.vec_ok) {
                 PA_LAUNCH((gemm_kernel<T, BK_, OCC, A_KC, B_KC, true, true, CAN_TR, 2, true>), grid, dim3(NT), 0, st, p);
                 return 0;
             }
@@ -2471,6 +2464,159 @@ template <typename T> bool is_aligned(const pa_gemm_args* a) {
     return ok;
 }
 
+// ---- which kernel, which grid ----------------------------------------------------------------------------------------------------
+// plan_gemm / plan_norm_a are the whole rule, as pure functions of the argument block, the switches and the CUs a launch may use:
+// they call no HIP function and dereference nothing (pa_gemm_plan runs them on a machine without a GPU).
+enum GemmKernel { GK_PAIR, GK_RING, GK_SMALL, GK_WIDE, GK_TALL, GK_BIG, GK_SKINNY };
+struct GemmPlan {
+    int status;                    // what the call returns before it launches (0: it launches)
+    int kind;                      // PA_GEMM_KIND_* the recorder reports
+    GemmKernel kernel;             // what the launcher switches on
+    int tile_h, tile_w;
+    Tiling t;
+    int splitk, tiles_per_slice;   // effective split-K
+    int grid, block;
+    int vec_ok;                    // the epilogue may use 4-element vector accesses
+    int bk; bool aligned, glds;    // pair kernel: K tile depth, 16-byte operand loads, direct-to-LDS loads
+};
+inline GemmPlan plan_fail(int status) { GemmPlan pl = GemmPlan(); pl.status = status; return pl; }
+inline void plan_kernel(GemmPlan& pl, int kind, GemmKernel kernel, const pa_gemm_args& a, int tile_h, int tile_w, int batch_times_splitk,
+                        UnitOrder order, int max_blocks, int block) {
+    pl.kind = kind; pl.kernel = kernel; pl.tile_h = tile_h; pl.tile_w = tile_w;
+    pl.t = tiling_of(a.M, a.N, tile_h, tile_w, batch_times_splitk, order);
+    pl.grid = pl.t.units < max_blocks ? pl.t.units : max_blocks;
+    pl.block = block;
+}
+
+// Precedence: big -> (a C_lp nobody but the skinny kernel writes is rejected) -> skinny -> wide -> tall -> small -> ring -> pair.
+GemmPlan plan_gemm(const pa_gemm_args& a, const GemmSwitches& sw, int cus) {
+    if (!a.A || !a.B || !a.C || a.M <= 0 || a.N <= 0 || a.K <= 0 || a.batch <= 0) return plan_fail(PA_EINVAL);
+    if (a.in_dtype != PA_F32 && a.in_dtype != PA_BF16) return plan_fail(PA_EINVAL);
+    if (a.out_dtype != PA_F32 && a.out_dtype != PA_BF16) return plan_fail(PA_EINVAL);
+    if (a.drop_p < 0.f || a.drop_p >= 1.f) return plan_fail(PA_EINVAL);
+    if (a.C_lp && (a.out_dtype != PA_F32 || a.ldc_lp < a.N || a.ldc_lp % 4 || (reinterpret_cast<uintptr_t>(a.C_lp) & 7))) return plan_fail(PA_EINVAL);
+    GemmPlan pl = GemmPlan();
+    const bool bf = a.in_dtype == PA_BF16, bk32 = bf && sw.bk == 32;
+    pl.bk = bf ? (bk32 ? 32 : 64) : 16;
+    const int nt = (a.K + pl.bk - 1) / pl.bk;
+    const int splitk = eff_splitk(nt, a.splitk);
+    if (splitk > 1 && !a.ws) return plan_fail(PA_EINVAL);
+    pl.splitk = splitk;
+    pl.tiles_per_slice = (nt + splitk - 1) / splitk;
+    // vector epilogue: 4-element accesses on C (the slab workspace under split-K) / R / aux / bias must be naturally aligned
+    const int osz = (splitk > 1 || a.out_dtype == PA_F32) ? 4 : 2, isz = bf ? 2 : 4;
+    pl.vec_ok = (splitk > 1 ? vec_ok(a.ws, a.N, (long long)a.M * a.N, osz) : vec_ok(a.C, a.ldc, a.sC, osz)) && vec_ok(a.R, a.ldr, a.sR, osz) &&
+                vec_ok(a.aux, a.ldaux, a.sAux, isz) && vec_ok(a.bias, 4, a.sBias, 4);
+    pl.aligned = bf ? is_aligned<bf16>(&a) : is_aligned<float>(&a);
+    pl.glds = ((a.K % pl.bk) == 0 || (!a.a_kcontig && !a.b_kcontig && bf && !bk32)) && !sw.noglds;
+
+    const Tiling base = tiling_of(a.M, a.N, BM, BN, a.batch * splitk, UNITS_XCD);
+    const int valid_units = base.tiles_m * base.tiles_n * a.batch * splitk;
+    const bool ring_ok = bf && !bk32 && !sw.noglds && pl.aligned;                                  // the ring kernels' operands
+    const bool linear = a.a_kcontig && a.b_kcontig && splitk == 1 && a.K % 64 == 0;             // a plain Linear of whole 64-deep K tiles
+    // ring (one block per CU, 4-stage ring) wins while the launch is a single round of units (latency-bound shapes); with more
+    // rounds the two-blocks-per-CU pair kernel overlaps better.  PA_GEMM_V3=2 forces the ring for every eligible launch.
+    const bool go_v3 = sw.v3 && (valid_units <= 256 || sw.v3 == 2) && ring_ok && ((!a.a_kcontig && !a.b_kcontig) || a.K % 64 == 0);
+    // small (64 x 64 tiles): plain Linears whose 128 x 128 tiling covers at most half of the CUs (measured: <= 128 units 7.05 ms/step,
+    // <= 64 7.11, <= 256 7.53).  Round 6, after the small kernel's K loop was repaired: up to 192 units too while K <= 512 - 2 048 x
+    // 1 536 x 512: 12.0 -> 10.8 us; from K = 1 024 on the 128 x 128 ring is ahead there, 15.6 vs 16.5 us (profiles/r06_gemm_small_tile.txt)
+    const bool go_small = go_v3 && sw.small_on && linear && (valid_units <= sw.small_max || (valid_units <= sw.small_max_k512 && a.K <= 512));
+    // wide (128 x 256 tiles): by default when that tiling is a single round of blocks (7 940 x 1 024: 248 tiles - measured 15.5 us
+    // against 16.8 for the pair kernel once the epilogues were restructured; at N = 1 536 the 378 tiles are a round and a half and the
+    // pair kernel stays ahead).  PA_GEMM_WIDE=1, every eligible launch: 0.73 us per K tile (the best of the four kernels) but 14.8 us
+    // fixed cost against 11.9 us, so at the model's K = 512 it loses (20.4 vs 18.5 us at 7 940 x 1 024) and only wins from K ~ 2 048 on.
+    const long long wide_tiles = (long long)((a.M + 127) / 128) * ((a.N + 255) / 256) * a.batch;
+    const bool go_wide = sw.v3 && sw.wide && (sw.wide == 1 || wide_tiles <= cus) && ring_ok && linear && a.N >= 1024 && valid_units > 256;
+    // tall (192 x 128 tiles, the wide kernel with 3 x 2 MFMA tiles per wave), opt-in: a Linear whose 128 x 128 tiling is a few units
+    // past one round of the CUs (N = 512 at 8.2 k - 12 k packed encoder rows: 260 - 384 units) becomes ONE round of at most 256
+    // bigger units (round 6).  Measured LEVEL with the pair kernel - 8 704 x 512 x 512: 16.5 vs 16.2 us, x 1 024: 22.0 vs 22.2; train
+    // step 4.56-4.64 either way (profiles/r06_gemm_tile_choice.txt) - 184 units of 1.5 x the work cost what 272 units on 512 slots do.
+    const int tall_units = ((a.M + 191) / 192) * ((a.N + 127) / 128) * a.batch;
+    const bool go_tall = sw.v3 && sw.tall && !go_wide && ring_ok && linear && valid_units > 256 && tall_units <= cus;
+    // skinny (a few hundred rows against a whole weight: the greedy-decode Linears).  Measured, greedy decode B 256 x 1024 steps: f32
+    // 3.65 -> 2.03 ms/step (the f32 Linears were 43 ... 98 us each on 8 blocks), bf16 1.224 -> 1.112 ms/step (32 blocks of the small
+    // kernel before).  f32 has no 64 x 64-tile kernel: a 2048-row f32 Linear (the decoder side of the f32 train step) is 64 blocks of
+    // the pair kernel on 256 CUs, the K-resident 32 x 32 kernel puts it on 1024 blocks: f32 train step 31.29 -> 29.84 ms (batch 16);
+    // at 8704 rows it loses (30.2 ms with the limit at 16384) - hence the f32 row limit of its own.
+    const bool go_skinny = sw.skinny && (!bf || sw.skinny >= 2) && a.a_kcontig && a.b_kcontig && splitk == 1 && a.batch == 1 &&
+                           a.M <= (bf ? sw.skinny_rows : sw.skinny_rows_f32) && a.K % (bf ? 512 : 256) == 0 && !a.aux && a.drop_p == 0.f &&
+                           !sw.noglds && pl.aligned;
+    // big (eight waves, gemm8.h), opt-in: plain bf16 Linears of at least PA_GEMM_BIG_MINM rows.  Level with the kernels below at this
+    // model's shapes, never ahead (profiles/r04_step_floor_probes.txt section 8).
+    const bool go_big = sw.big && !go_skinny && bf && !sw.noglds && pl.aligned && linear && a.M >= sw.big_minm && a.N >= sw.big_minn;
+    if (go_big) {
+        // tile width: PA_GEMM_BIG=1 (round 4): 256 from N = 1024 on, else 128.  PA_GEMM_BIG=2 (round 6): the width in {256, 192, 128}
+        // that needs the fewest ROUNDS of one block per CU (ties: the wider tile) - 256 x 192 makes N = 1536 one round of 31 x 8 blocks
+        // at 7.9 k rows where 256 x 256 leaves 70 CUs idle and 128-wide tiles take two rounds; PA_GEMM_BIG_TN=<n> forces.
+        int tn = a.N >= 1024 ? 256 : 128;
+        if (sw.big >= 2) {
+            long best = -1;
+            for (int w : {256, 192, 128}) {
+                const long blocks = (long)((a.M + 255) / 256) * ((a.N + w - 1) / w) * a.batch;
+                const long rounds = (blocks + cus - 1) / cus;
+                const long cost = rounds * w * 1000 + ((a.N + w - 1) / w * w - a.N);       // time ~ rounds x tile width; then least padding
+                if (best < 0 || cost < best) { best = cost; tn = w; }
+            }
+        }
+        if (sw.big_tn == 256 || sw.big_tn == 192 || sw.big_tn == 128) tn = sw.big_tn;
+        plan_kernel(pl, PA_GEMM_KIND_BIG, GK_BIG, a, 256, tn, a.batch, UNITS_XCD, cus, 512);
+        return pl;
+    }
+    if (a.C_lp && !go_skinny) return plan_fail(PA_EINVAL);          // the bf16 copy of an f32 output exists in the skinny kernel only
+    if (go_skinny) plan_kernel(pl, PA_GEMM_KIND_SKINNY, GK_SKINNY, a, SK_T, SK_T, 1, UNITS_PLAIN, INT_MAX, 256);      // one block per tile
+    else if (go_wide) plan_kernel(pl, PA_GEMM_KIND_WIDE, GK_WIDE, a, 128, 256, a.batch, UNITS_XCD_ALWAYS, cus, NT);
+    else if (go_tall) plan_kernel(pl, PA_GEMM_KIND_WIDE, GK_TALL, a, 192, 128, a.batch, UNITS_XCD, cus, NT);
+    else if (go_small) plan_kernel(pl, PA_GEMM_KIND_SMALL, GK_SMALL, a, 64, 64, a.batch, UNITS_PLAIN, 2 * cus, NT);   // two 80 KB blocks fit a CU
+    else if (go_v3) plan_kernel(pl, PA_GEMM_KIND_RING, GK_RING, a, BM, BN, a.batch * splitk, UNITS_XCD, cus, NT);
+    else {
+        const int pair_cap = sw.grid > 0 ? (sw.grid / 256) * cus + sw.grid % 256 : INT_MAX;
+        plan_kernel(pl, PA_GEMM_KIND_PAIR, GK_PAIR, a, BM, BN, a.batch * splitk, UNITS_XCD, pair_cap, NT);
+    }
+    return pl;
+}
+
+// pa_gemm_norm_a: the f32 skinny form, the bf16 skinny form, or the 64 x 64 form of the small kernel
+GemmPlan plan_norm_a(const pa_gemm_args& a, const pa_gemm_norm_ext& x, const GemmSwitches& sw, int cus) {
+    if (!a.A || !a.B || !a.C || !a.bias || !x.u || a.M <= 0 || a.N <= 0 || a.K <= 0) return plan_fail(PA_EINVAL);
+    if ((a.in_dtype != PA_BF16 && a.in_dtype != PA_F32) || (a.out_dtype != PA_BF16 && a.out_dtype != PA_F32) || !a.a_kcontig || !a.b_kcontig) return plan_fail(PA_EINVAL);
+    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    GemmPlan pl = GemmPlan();
+    pl.splitk = 1;
+    // C / bias / u as 4-element vectors
+    const bool cbu_ok = vec_ok(a.C, a.ldc, 0, a.out_dtype == PA_F32 ? 4 : 2) && al16(a.bias) && al16(x.u);
+    if (a.in_dtype == PA_F32) {
+        // exact-f32 form (the f32 greedy-decode step): f32 rows, f32 folded weight (pa_ln_fold_weights_f32), f32 output; the statistics
+        // come from the rows themselves (ext->zf, normally == args->A).  Skinny kernel only: <= 512 rows, K = 512.
+        if (a.batch != 1 || a.splitk > 1 || a.R || a.aux || a.drop_p != 0.f || a.N % 32) return plan_fail(PA_ESHAPE);
+        if (!x.zf || a.K != 512 || a.M > sw.skinny_rows || a.out_dtype != PA_F32 || (x.y && (!x.y_f32 || a.N < a.K))) return plan_fail(PA_ESHAPE);
+        if (x.y && (!x.gamma || !x.beta || x.ldy < a.K || x.ldy % 4 || !al16(x.y))) return plan_fail(PA_EINVAL);
+        if (!is_aligned<float>(&a) || x.ldzf < a.K || x.ldzf % 4 || !al16(x.zf)) return plan_fail(PA_EALIGN);
+        pl.vec_ok = cbu_ok && (!x.y || (al16(x.gamma) && al16(x.beta)));
+        if (!pl.vec_ok) return plan_fail(PA_EALIGN);
+        plan_kernel(pl, PA_GEMM_KIND_SKINNY, GK_SKINNY, a, SK_T, SK_T, 1, UNITS_PLAIN, INT_MAX, 256);
+        return pl;
+    }
+    if (a.batch != 1 || a.splitk > 1 || a.R || a.aux || a.drop_p != 0.f || a.K % 64 || a.N % 32) return plan_fail(PA_ESHAPE);
+    if (x.y && (!x.gamma || !x.beta || x.ldy < a.K || x.ldy % 4)) return plan_fail(PA_EINVAL);
+    if (x.y && (a.N + 63) / 64 * 64 < a.K) return plan_fail(PA_ESHAPE);      // column tile j materialises columns 64 j .. 64 j + 63 of LayerNorm(Z)
+    if (!is_aligned<bf16>(&a)) return plan_fail(PA_EALIGN);
+    if (x.zf && (x.ldzf < a.K || x.ldzf % 4 || !al16(x.zf))) return plan_fail(PA_EINVAL);
+    if (x.y && x.y_f32 && !al16(x.y)) return plan_fail(PA_EALIGN);
+    pl.vec_ok = cbu_ok;
+    // <= 512 rows and K = 512: the skinny kernel's form (the Z tile is resident in LDS, the statistics cost no memory round trip)
+    if (sw.skinny >= 2 && a.M <= sw.skinny_rows && a.K == 512 &&
+        (!x.y || (a.N >= a.K && x.ldy % 8 == 0 && al16(x.y) && al16(x.gamma) && al16(x.beta)))) {
+        plan_kernel(pl, PA_GEMM_KIND_SKINNY, GK_SKINNY, a, SK_T, SK_T, 1, UNITS_PLAIN, INT_MAX, 256);
+        return pl;
+    }
+    if (x.zf || x.y_f32) return plan_fail(PA_ESHAPE);               // the f32-residual form exists in the skinny kernel only
+    plan_kernel(pl, PA_GEMM_KIND_SMALL, GK_SMALL, a, 64, 64, 1, UNITS_PLAIN, INT_MAX, NT);
+    if (pl.t.units > 2 * cus) return plan_fail(PA_ESHAPE);         // the row statistics live in registers: one unit per block
+    if (!pl.vec_ok) return plan_fail(PA_EALIGN);
+    pl.tiles_per_slice = a.K / 64;
+    return pl;
+}
+
 }  // namespace
 
 // Measurement hook: while recording, every pa_gemm() call's argument block is appended to a host-side list so that
@@ -2481,6 +2627,16 @@ std::vector<int32_t>* g_rec_kind = nullptr;      // kernel each recorded launch 
 std::vector<int32_t>* g_rec_group = nullptr;     // -1: launched by pa_gemm; >= 0: member of that pa_gemm_group launch
 int g_rec_ngroups = 0;
 std::mutex g_rec_mu;
+void record_args(const pa_gemm_args& a) {
+    if (g_rec) { std::lock_guard<std::mutex> lk(g_rec_mu); if (g_rec) g_rec->push_back(a); }
+}
+// the kernel family of the launch just recorded and the pa_gemm_group launch it belongs to (-1: pa_gemm's own)
+void record_kind(int kind, int group) {
+    if (!g_rec) return;
+    std::lock_guard<std::mutex> lk(g_rec_mu);
+    if (g_rec && g_rec_kind) g_rec_kind->push_back(kind);
+    if (g_rec && g_rec_group) g_rec_group->push_back(group);
+}
 }
 extern "C" int pa_gemm_record(int32_t enable) {
     std::lock_guard<std::mutex> lk(g_rec_mu);
@@ -2515,9 +2671,6 @@ extern "C" int pa_gemm_recorded_kinds(int32_t* out, int32_t cap) {
     return n;
 }
 
-// number of NON-EMPTY contraction slices pa_gemm uses for a requested split (slices are whole K tiles of 64 bf16 / 16 f32
-// elements; rounding the slice length up can leave trailing slices empty - those must not exist, their slabs would
-// never be written)
 namespace {
 // bf16x3 mode state (see "bf16x3 (split) products" below)
 struct SplitKeep { const void* src; int rows, cols, ld, pat; bf16* dst; int made; };     // pat 0: (hi, hi, lo) parts, 1: (hi, lo, hi);
@@ -2580,15 +2733,12 @@ extern "C" int pa_split_ctx_enter(void* ctx) { t_split = static_cast<SplitState*
 extern "C" void* pa_split_ctx_current(void) { return t_split; }
 extern "C" int pa_split_attn_set(int32_t on) { g_split.attn.store(on ? 1 : 0, std::memory_order_relaxed); return 0; }
 extern "C" int pa_split_attn_active(void) { return g_split.attn.load(std::memory_order_relaxed); }
+// number of non-empty contraction slices pa_gemm uses for a requested split (whole K tiles of 64 bf16 / 16 f32 elements)
 extern "C" int pa_gemm_effective_splitk(int32_t K, int32_t in_dtype, int32_t splitk) {
     // (bf16x3 mode: an f32 GEMM runs on the bf16 kernels over a 3 K long contraction - its slices are whole 64-wide tiles of THAT)
     const bool x3 = in_dtype == PA_F32 && split_on();
     const int BK = (in_dtype == PA_BF16 || x3) ? 64 : 16;
-    const int nt = ((x3 ? 3 * K : K) + BK - 1) / BK;
-    int sk = splitk > 1 ? splitk : 1;
-    if (sk > nt) sk = nt;
-    const int per = (nt + sk - 1) / sk;
-    return (nt + per - 1) / per;
+    return eff_splitk(((x3 ? 3 * K : K) + BK - 1) / BK, splitk);
 }
 extern "C" int pa_gemm_split_active(void) { return split_on() ? 1 : 0; }
 
@@ -2676,7 +2826,6 @@ __global__ __launch_bounds__(256) void split_many_kernel(const SplitJob* jobs, c
     const SplitJob J = jobs[lo];
     split_job(J, blockIdx.x - begin[lo], begin[lo + 1] - begin[lo]);
 }
-inline int eff_split(int nt, int sk) { if (sk > nt) sk = nt; if (sk < 1) sk = 1; const int per = (nt + sk - 1) / sk; return (nt + per - 1) / per; }
 }  // namespace
 extern "C" int pa_gemm_split_config(int32_t on, void* ws, int64_t bytes) {
     if (on && (!ws || bytes <= 0 || (reinterpret_cast<uintptr_t>(ws) & 255))) return PA_EINVAL;
@@ -2771,7 +2920,6 @@ extern "C" int pa_gemm_split_stats(int64_t* out2, int32_t reset) {
     if (reset) { g_cnt.taken.store(0); g_cnt.declined.store(0); g_cnt.reused.store(0); g_cnt.made_hits.store(0); g_cnt.cache_hits.store(0); }
     return 0;
 }
-// returns 1 when the GEMM was enqueued as bf16x3, 0 when the caller must run it exact, < 0 on error
 // Returns 0 and *taken = true when the product ran as bf16x3, 0 and *taken = false when the caller must run it exact, or an error
 // (a negative PA_E* or a positive hipError_t of the cut / inner launch - ADVICE r5: the status used to share the return value
 // with the 'taken' flag, so hipErrorInvalidValue = 1 read as success).
@@ -2849,15 +2997,13 @@ static int gemm_split3(const pa_gemm_args* a, void* stream, bool* taken) {
         }
         keep_a = g_split.retain == 1 && akc && nb == 1 && g_split.nkeep < 16;
     }
-    // split-K: the caller sized its slabs with the f32 tiling (pa_gemm_effective_splitk(K, PA_F32, .)); ask the bf16 tiling for
-    // exactly as many non-empty slices, or decline
     // split-K: callers size their slabs with pa_gemm_effective_splitk(K, PA_F32, .), which in this mode already counts whole
     // 64-wide tiles of the 3 K long bf16 contraction - the request passes through unchanged
-    const int sk_req = a->splitk > 1 ? a->splitk : 1, zero_from = 0, zero_to = 0;
+    const int sk_req = a->splitk > 1 ? a->splitk : 1;
     if (sk_req > 1 && !a->ws) return 0;
     static const bool dbg_split = getenv("PA_SPLIT_DEBUG") && atoi(getenv("PA_SPLIT_DEBUG")) >= 2;
-    if (dbg_split) fprintf(stderr, "[pa_gemm x3] M %d N %d K %d batch %d akc %d bkc %d splitk %d -> %d (zero-fill %d..%d) defer %d\n",
-                           M, N, K, nb, (int)akc, (int)bkc, a->splitk, sk_req, zero_from, zero_to, a->splitk_defer);
+    if (dbg_split) fprintf(stderr, "[pa_gemm x3] M %d N %d K %d batch %d akc %d bkc %d splitk %d -> %d defer %d\n",
+                           M, N, K, nb, (int)akc, (int)bkc, a->splitk, sk_req, a->splitk_defer);
     char* w0 = g_split.ws + g_split.keep_off;
     bf16* A3 = reinterpret_cast<bf16*>(w0);
     bf16* B3 = reinterpret_cast<bf16*>(w0 + a_bytes);
@@ -2901,11 +3047,6 @@ static int gemm_split3(const pa_gemm_args* a, void* stream, bool* taken) {
     const int rc = pa_gemm(&b, stream);
     g_split.on.store(1, std::memory_order_relaxed);
     if (rc) return rc;
-    if (zero_to > zero_from) {
-        const size_t slab = (size_t)M * N * sizeof(float);
-        if (hipMemsetAsync(static_cast<char*>(a->ws) + (size_t)zero_from * slab, 0, (size_t)(zero_to - zero_from) * slab,
-                           reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return PA_EINVAL;
-    }
     *taken = true;
     return 0;
 }
@@ -2923,11 +3064,10 @@ extern "C" int pa_gemm(const pa_gemm_args* a, void* stream) {
             // the caller's reduction descriptor counts pa_gemm_effective_splitk(K, PA_F32, splitk) slabs in THIS mode's (bf16)
             // tiling; the exact kernel below writes the f32 tiling's count: run it with a request that yields no more than that
             // and hand the reducer zeros for the rest
-            auto eff = [](int nt, int sk) { if (sk > nt) sk = nt; if (sk < 1) sk = 1; const int per = (nt + sk - 1) / sk; return (nt + per - 1) / per; };
-            const int want = eff((3 * a->K + 63) / 64, a->splitk), nt32 = (a->K + 15) / 16;
+            const int want = eff_splitk((3 * a->K + 63) / 64, a->splitk), nt32 = (a->K + 15) / 16;
             int req = want;
-            while (req > 1 && eff(nt32, req) > want) --req;
-            const int got = eff(nt32, req);
+            while (req > 1 && eff_splitk(nt32, req) > want) --req;
+            const int got = eff_splitk(nt32, req);
             pa_gemm_args e = *a; e.splitk = req;
             g_split.on.store(0, std::memory_order_relaxed);
             const int rc = pa_gemm(&e, stream);
@@ -2944,208 +3084,58 @@ extern "C" int pa_gemm(const pa_gemm_args* a, void* stream) {
         if (dbg_split) fprintf(stderr, "[pa_gemm x3 declined] M %d N %d K %d batch %d akc %d bkc %d lda %d ldb %d sA %lld sB %lld splitk %d aux %d ldaux %d\n",
                                a->M, a->N, a->K, a->batch, a->a_kcontig, a->b_kcontig, a->lda, a->ldb, (long long)a->sA, (long long)a->sB, a->splitk, a->aux ? 1 : 0, a->ldaux);
     }
-    if (g_rec) { std::lock_guard<std::mutex> lk(g_rec_mu); if (g_rec) g_rec->push_back(*a); }
-    if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch <= 0) return PA_EINVAL;
-    if (a->in_dtype != PA_F32 && a->in_dtype != PA_BF16) return PA_EINVAL;
-    if (a->out_dtype != PA_F32 && a->out_dtype != PA_BF16) return PA_EINVAL;
-    if (a->drop_p < 0.f || a->drop_p >= 1.f) return PA_EINVAL;
+    record_args(*a);
+    const GemmSwitches& sw = gemm_switches();
+    const GemmPlan pl = plan_gemm(*a, sw, cus_for_gemm());      // (256 CUs minus those left to RCCL's kernels: pa_set_reserved_cus)
+    if (pl.status) return pl.status;
+    record_kind(pl.kind, -1);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    GemmP p;
-    p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias; p.R = a->R; p.aux = a->aux;
-    p.M = a->M; p.N = a->N; p.K = a->K;
-    p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldr = a->ldr; p.ldaux = a->ldaux;
-    p.sA = a->sA; p.sB = a->sB; p.sC = a->sC; p.sR = a->sR; p.sAux = a->sAux; p.sBias = a->sBias;
-    p.batch = a->batch;
-    p.alpha = a->alpha; p.relu = a->relu; p.aux_scale = a->aux_scale;
-    p.drop_thr = (uint32_t)((double)a->drop_p * 4294967296.0);           // keep <=> 32-bit product >= thr (pa_device.h drop_keep_rc)
-    p.drop_scale = (float)(1.0 / (1.0 - (double)p.drop_thr / 4294967296.0));
-    p.drop_seed = a->drop_seed;
-    p.out_dtype = a->out_dtype;
-    p.ln_u = nullptr; p.ln_gamma = nullptr; p.ln_beta = nullptr; p.ln_y = nullptr; p.ldy = 0; p.ln_eps = 0.f;
-    p.c_lp = a->C_lp; p.ldc_lp = a->ldc_lp; p.ln_zf = nullptr; p.ldzf = 0; p.ln_y_f32 = 0;
-    if (a->C_lp && (a->out_dtype != PA_F32 || a->ldc_lp < a->N || a->ldc_lp % 4 || (reinterpret_cast<uintptr_t>(a->C_lp) & 7))) return PA_EINVAL;
-    static const int dbg_bk = getenv("PA_GEMM_BK") ? atoi(getenv("PA_GEMM_BK")) : 64;     // bf16 K tile: 64 or 32
-    const bool bk32 = a->in_dtype == PA_BF16 && dbg_bk == 32;
-    const int BK = a->in_dtype == PA_BF16 ? (bk32 ? 32 : 64) : 16;
-    const int nt = (a->K + BK - 1) / BK;
-    int splitk = a->splitk > 1 ? a->splitk : 1;
-    if (splitk > nt) splitk = nt;
-    splitk = (nt + (nt + splitk - 1) / splitk - 1) / ((nt + splitk - 1) / splitk);   // drop slices that would be empty (pa_gemm_effective_splitk)
-    if (splitk > 1 && !a->ws) return PA_EINVAL;
-    p.splitk = splitk;
-    p.tiles_per_slice = (nt + splitk - 1) / splitk;
-    p.tiles_m = (a->M + BM - 1) / BM;
-    p.tiles_n = (a->N + BN - 1) / BN;
-    p.plain_order = p.tiles_m < 8;                                        // < 8 row tiles: the XCD interleave would leave most units empty
-    p.tiles_m_pad = p.plain_order ? p.tiles_m : (p.tiles_m + 7) / 8 * 8;
-    p.units = p.tiles_m_pad * p.tiles_n * a->batch * splitk;
-    GemmP pk = p;
-    if (splitk > 1) { pk.C = a->ws; pk.ldc = a->N; }
-    // vector epilogue: 4-element accesses on C / R / aux / bias must be naturally aligned
-    {
-        const int osz = (splitk > 1 || a->out_dtype == PA_F32) ? 4 : 2, isz = a->in_dtype == PA_BF16 ? 2 : 4;
-        auto ok = [](const void* q, long long ld, long long sb, int esz) {
-            return !q || (((reinterpret_cast<uintptr_t>(q) * 1) % (4 * esz) == 0) && (ld % 4 == 0) && (sb % 4 == 0));
-        };
-        pk.vec_ok = ok(pk.C, pk.ldc, splitk > 1 ? (long long)a->M * a->N : a->sC, osz) && ok(a->R, a->ldr, a->sR, osz) &&
-                    ok(a->aux, a->ldaux, a->sAux, isz) && ok(a->bias, 4, a->sBias, 4);
+    GemmP p = GemmP();                                           // (value-initialised: the LayerNorm-fold pointers stay null)
+    fill_operands(p, *a);
+    p.c_lp = a->C_lp; p.ldc_lp = a->ldc_lp;
+    p.splitk = pl.splitk; p.tiles_per_slice = pl.tiles_per_slice;
+    p.dbg = sw.dbg;
+    GemmP pk = p;                                                // the product kernel's view: under split-K it writes the f32 slabs
+    if (pl.splitk > 1) { pk.C = a->ws; pk.ldc = a->N; }
+    pk.vec_ok = pl.vec_ok;
+    set_tiling(pk, pl.t);
+    const dim3 grid(pl.grid), block(pl.block);
+    const bool akc = a->a_kcontig != 0, bkc = a->b_kcontig != 0;
+    switch (pl.kernel) {
+    case GK_BIG:
+        if (pl.tile_w == 256) PA_LAUNCH((gemm8_kernel<4, 2, 2, 4, 64, 2>), grid, block, 0, st, pk);
+        else if (pl.tile_w == 192) PA_LAUNCH((gemm8_kernel<4, 2, 2, 3, 64, 2>), grid, block, 0, st, pk);
+        else PA_LAUNCH((gemm8_kernel<4, 2, 2, 2, 64, 2>), grid, block, 0, st, pk);
+        break;
+    case GK_SKINNY:
+        if (a->in_dtype == PA_BF16) PA_LAUNCH((gemm_skinny_kernel<bf16, false>), grid, block, 0, st, pk);
+        else PA_LAUNCH((gemm_skinny_kernel<float, false>), grid, block, 0, st, pk);
+        break;
+    case GK_WIDE: PA_LAUNCH((gemm3w_kernel<2, 4>), grid, block, 0, st, pk); break;
+    case GK_TALL: PA_LAUNCH((gemm3w_kernel<3, 2>), grid, block, 0, st, pk); break;
+    case GK_SMALL: PA_LAUNCH(gemm3s_kernel, grid, block, 0, st, pk); break;
+    case GK_RING:
+        if (akc && bkc) PA_LAUNCH((gemm3_kernel<true, true, GemmP>), grid, block, 0, st, pk);
+        else if (akc) PA_LAUNCH((gemm3_kernel<true, false, GemmP>), grid, block, 0, st, pk);
+        else if (bkc) PA_LAUNCH((gemm3_kernel<false, true, GemmP>), grid, block, 0, st, pk);
+        else PA_LAUNCH((gemm3_kernel<false, false, GemmP>), grid, block, 0, st, pk);
+        break;
+    case GK_PAIR: {
+        int rc;
+        if (a->in_dtype != PA_BF16) rc = launch_layout<float, 16, 2>(pk, akc, bkc, pl.aligned, pl.glds, grid, st);
+        else if (pl.bk == 32) rc = launch_layout<bf16, 32, 3>(pk, akc, bkc, pl.aligned, pl.glds, grid, st);
+        else rc = launch_layout<bf16, 64, 2>(pk, akc, bkc, pl.aligned, pl.glds, grid, st);
+        if (rc) return rc;
+        break;
     }
-    const int cus = cus_for_gemm();                 // 256 minus the CUs left to RCCL's kernels (pa_set_reserved_cus)
-    // debug/ablation toggles (environment, read once): PA_GEMM_NOGLDS=1, PA_GEMM_GRID=<blocks> (0 = one block per unit)
-    static const int dbg_noglds = getenv("PA_GEMM_NOGLDS") ? atoi(getenv("PA_GEMM_NOGLDS")) : 0;
-    static const int dbg_grid = getenv("PA_GEMM_GRID") ? atoi(getenv("PA_GEMM_GRID")) :
-                                (getenv("PA_GEMM_NST") && atoi(getenv("PA_GEMM_NST")) == 1 ? 1024 : (bk32 ? 768 : 512));
-    static const int dbg_bits = getenv("PA_GEMM_DBG") ? atoi(getenv("PA_GEMM_DBG")) : 0;   // v3 timing ablations (wrong results)
-    pk.dbg = dbg_bits; p.dbg = dbg_bits;
-    const int pair_cap = dbg_grid > 0 ? (dbg_grid / 256) * cus + dbg_grid % 256 : 0;      // (two blocks per CU by default)
-    int grid_x = (pair_cap > 0 && pk.units > pair_cap) ? pair_cap : pk.units;
-    dim3 grid(grid_x);
-    const bool glds = ((a->K % BK) == 0 || (!a->a_kcontig && !a->b_kcontig && a->in_dtype == PA_BF16 && !bk32)) && !dbg_noglds;
-    int rc;
-    static const int use_v3 = getenv("PA_GEMM_V3") ? atoi(getenv("PA_GEMM_V3")) : 1;
-    const bool v3_layout_ok = (a->a_kcontig && a->b_kcontig) ? (a->K % 64 == 0) : ((!a->a_kcontig || a->K % 64 == 0) && (!a->b_kcontig || a->K % 64 == 0));
-    // v3 (one block per CU, 4-stage ring) wins while the launch is a single round of units (latency-bound shapes);
-    // with more rounds the two-blocks-per-CU kernel overlaps better.  PA_GEMM_V3=2 forces v3 for every eligible launch.
-    const int valid_units = p.tiles_m * p.tiles_n * a->batch * splitk;
-    const bool go_v3 = use_v3 && (valid_units <= 256 || use_v3 == 2) && a->in_dtype == PA_BF16 && !bk32 && !dbg_noglds && is_aligned<bf16>(a) && v3_layout_ok;
-    // 128 x 256 kernel: opt-in (PA_GEMM_WIDE=1).  Measured on MI355X: 0.73 us per K tile (0.37 per 128 x 128 equivalent, the best
-    // of the four kernels) but 14.8 us fixed cost against 11.9 us (eight staged 32 x 32 epilogue passes), so at the model's
-    // K = 512 it loses to the two-blocks-per-CU kernel (20.4 vs 18.5 us at 7 940 x 1 024) and only wins from K ~ 2 048 on.
-    static const int use_small = getenv("PA_GEMM_SMALL") ? atoi(getenv("PA_GEMM_SMALL")) : 1;
-    static const int small_max = getenv("PA_GEMM_SMALL_MAX") ? atoi(getenv("PA_GEMM_SMALL_MAX")) : 128;
-    // (round 6, after the small kernel's K loop was repaired: up to 192 units too while K <= 512 - 2 048 x 1 536 x 512: 12.0 -> 10.8 us;
-    //  from K = 1 024 on the 128 x 128 ring is ahead there, 15.6 vs 16.5 us - profiles/r06_gemm_small_tile.txt)
-    static const int small_max_k512 = getenv("PA_GEMM_SMALL_MAX_K512") ? atoi(getenv("PA_GEMM_SMALL_MAX_K512")) : 192;
-    const bool go_small = go_v3 && use_small && a->a_kcontig && a->b_kcontig && splitk == 1 && a->K % 64 == 0 &&
-                          (valid_units <= small_max || (valid_units <= small_max_k512 && a->K <= 512));
-    // PA_GEMM_WIDE: 0 never, 1 every eligible launch, 2 (default) when the 128 x 256 tiling is a single round of blocks
-    // (7 940 x 1 024: 248 tiles - measured 15.5 us against 16.8 for the two-blocks-per-CU kernel once the epilogues were
-    // restructured; at N = 1 536 the 378 tiles are a round and a half and the two-blocks-per-CU kernel stays ahead)
-    static const int use_wide = getenv("PA_GEMM_WIDE") ? atoi(getenv("PA_GEMM_WIDE")) : 2;
-    const long long wide_tiles = (long long)((a->M + 127) / 128) * ((a->N + 255) / 256) * a->batch;
-    const bool go_wide = use_v3 && use_wide && (use_wide == 1 || wide_tiles <= cus) && a->in_dtype == PA_BF16 && !bk32 && !dbg_noglds &&
-                         is_aligned<bf16>(a) && a->a_kcontig && a->b_kcontig && splitk == 1 && a->K % 64 == 0 && a->N >= 1024 && valid_units > 256;
-    static const int use_tall = getenv("PA_GEMM_TALL") ? atoi(getenv("PA_GEMM_TALL")) : 0;
-    const int tall_units = ((a->M + 191) / 192) * ((a->N + 127) / 128) * a->batch;
-    const bool go_tall = use_v3 && use_tall && !go_wide && a->in_dtype == PA_BF16 && !bk32 && !dbg_noglds && is_aligned<bf16>(a) && a->a_kcontig &&
-                         a->b_kcontig && splitk == 1 && a->K % 64 == 0 && valid_units > 256 && tall_units <= cus;
-    // skinny kernel (a few hundred rows against a whole weight: the greedy-decode Linears).  PA_GEMM_SKINNY: 0 never, 1 f32 only,
-    // 2 (default) bf16 too.  Measured on MI355X, greedy decode B 256 x 1024 steps: f32 3.65 -> 2.03 ms/step (the f32 Linears were
-    // 43 ... 98 us each on 8 blocks), bf16 1.224 -> 1.112 ms/step (32 blocks of the 64 x 64-tile ring kernel before).
-    static const int use_skinny = getenv("PA_GEMM_SKINNY") ? atoi(getenv("PA_GEMM_SKINNY")) : 2;
-    static const int skinny_rows = getenv("PA_GEMM_SKINNY_ROWS") ? atoi(getenv("PA_GEMM_SKINNY_ROWS")) : 512;
-    // f32 has no 64 x 64-tile kernel: a 2048-row f32 Linear (the decoder side of the f32 train step) is 64 blocks of the 128 x 128
-    // pair kernel on 256 CUs.  The K-resident 32 x 32 kernel puts it on 1024 blocks: f32 train step 31.29 -> 29.84 ms (MI355X,
-    // batch 16); at 8704 rows it loses (30.2 ms with the limit at 16384).  PA_GEMM_SKINNY_ROWS_F32 overrides.
-    static const int skinny_rows32 = getenv("PA_GEMM_SKINNY_ROWS_F32") ? atoi(getenv("PA_GEMM_SKINNY_ROWS_F32"))
-                                     : getenv("PA_GEMM_SKINNY_ROWS") ? atoi(getenv("PA_GEMM_SKINNY_ROWS")) : 2048;
-    const int sk_ch = a->in_dtype == PA_BF16 ? 512 : 256;
-    const bool go_skinny = use_skinny && (a->in_dtype == PA_F32 || use_skinny >= 2) && a->a_kcontig && a->b_kcontig && splitk == 1 &&
-                           a->batch == 1 && a->M <= (a->in_dtype == PA_F32 ? skinny_rows32 : skinny_rows) && a->K % sk_ch == 0 && !a->aux && a->drop_p == 0.f && !dbg_noglds &&
-                           (a->in_dtype == PA_BF16 ? is_aligned<bf16>(a) : is_aligned<float>(a));
-    // eight-wave big-tile kernel (gemm8.h): PA_GEMM_BIG 0 (default) never, 1 plain k-contiguous bf16 Linears of at least
-    // PA_GEMM_BIG_MINM rows - 256 x 256 tiles from N = 1024 on, 256 x 128 tiles below.  Opt-in: level with the kernels below at this
-    // model's shapes, never ahead (profiles/r04_step_floor_probes.txt section 8).
-    static const int use_big = getenv("PA_GEMM_BIG") ? atoi(getenv("PA_GEMM_BIG")) : 0;
-    static const int big_minm = getenv("PA_GEMM_BIG_MINM") ? atoi(getenv("PA_GEMM_BIG_MINM")) : 4096;
-    static const int big_minn = getenv("PA_GEMM_BIG_MINN") ? atoi(getenv("PA_GEMM_BIG_MINN")) : 256;
-    const bool go_big = use_big && !go_skinny && a->in_dtype == PA_BF16 && !dbg_noglds && is_aligned<bf16>(a) && a->a_kcontig && a->b_kcontig &&
-                        splitk == 1 && a->K % 64 == 0 && a->M >= big_minm && a->N >= big_minn;
-    if (go_big) {
-        if (g_rec) { std::lock_guard<std::mutex> lk(g_rec_mu); if (g_rec && g_rec_kind) g_rec_kind->push_back(PA_GEMM_KIND_BIG); if (g_rec && g_rec_group) g_rec_group->push_back(-1); }
-        // tile width: PA_GEMM_BIG=1 (round 4): 256 from N = 1024 on, else 128.  PA_GEMM_BIG=2 (round 6): the width in {256, 192, 128}
-        // that needs the fewest ROUNDS of one block per CU (ties: the wider tile) - 256 x 192 makes N = 1536 one round of 31 x 8 blocks
-        // at 7.9 k rows where 256 x 256 leaves 70 CUs idle and 128-wide tiles take two rounds; PA_GEMM_BIG_TN=<n> forces.
-        static const int force_tn = getenv("PA_GEMM_BIG_TN") ? atoi(getenv("PA_GEMM_BIG_TN")) : 0;
-        int tn = a->N >= 1024 ? 256 : 128;
-        const int tm8 = (a->M + 255) / 256;
-        if (use_big >= 2) {
-            long best = -1;
-            for (int w : {256, 192, 128}) {
-                const long blocks = (long)tm8 * ((a->N + w - 1) / w) * a->batch;
-                const long rounds = (blocks + cus - 1) / cus;
-                const long cost = rounds * w * 1000 + ((a->N + w - 1) / w * w - a->N);       // time ~ rounds x tile width; then least padding
-                if (best < 0 || cost < best) { best = cost; tn = w; }
-            }
-        }
-        if (force_tn == 256 || force_tn == 192 || force_tn == 128) tn = force_tn;
-        GemmP pb = pk;
-        pb.tiles_m = tm8; pb.tiles_n = (a->N + tn - 1) / tn;
-        pb.plain_order = pb.tiles_m < 8;
-        pb.tiles_m_pad = pb.plain_order ? pb.tiles_m : (pb.tiles_m + 7) / 8 * 8;
-        pb.units = pb.tiles_m_pad * pb.tiles_n * a->batch;
-        const int gb = pb.units < cus ? pb.units : cus;
-        if (tn == 256) PA_LAUNCH((gemm8_kernel<4, 2, 2, 4, 64, 2>), dim3(gb), dim3(512), 0, st, pb);
-        else if (tn == 192) PA_LAUNCH((gemm8_kernel<4, 2, 2, 3, 64, 2>), dim3(gb), dim3(512), 0, st, pb);
-        else PA_LAUNCH((gemm8_kernel<4, 2, 2, 2, 64, 2>), dim3(gb), dim3(512), 0, st, pb);
-        return 0;
     }
-    if (a->C_lp && !go_skinny) return PA_EINVAL;          // the bf16 copy of an f32 output exists in the skinny kernel only
-    if (go_skinny) {
-        if (g_rec) { std::lock_guard<std::mutex> lk(g_rec_mu); if (g_rec && g_rec_kind) g_rec_kind->push_back(PA_GEMM_KIND_SKINNY); if (g_rec && g_rec_group) g_rec_group->push_back(-1); }
-        GemmP ps = pk;
-        ps.tiles_m = (a->M + SK_T - 1) / SK_T; ps.tiles_n = (a->N + SK_T - 1) / SK_T;
-        const dim3 gsk(ps.tiles_m * ps.tiles_n);
-        if (a->in_dtype == PA_BF16) PA_LAUNCH((gemm_skinny_kernel<bf16, false>), gsk, dim3(256), 0, st, ps);
-        else PA_LAUNCH((gemm_skinny_kernel<float, false>), gsk, dim3(256), 0, st, ps);
-        return 0;
-    }
-    if (g_rec) { std::lock_guard<std::mutex> lk(g_rec_mu); if (g_rec && g_rec_kind) g_rec_kind->push_back((go_wide || go_tall) ? PA_GEMM_KIND_WIDE : (go_small ? PA_GEMM_KIND_SMALL : (go_v3 ? PA_GEMM_KIND_RING : PA_GEMM_KIND_PAIR))); if (g_rec && g_rec_group) g_rec_group->push_back(-1); }
-    // wide-tile ring kernel: large multi-round k-contiguous Linears (N >= 1024): 128 x 256 tiles
-    if (go_wide) {
-        GemmP pw = pk;
-        pw.tiles_m = (a->M + 127) / 128; pw.tiles_n = (a->N + 255) / 256;
-        pw.tiles_m_pad = (pw.tiles_m + 7) / 8 * 8; pw.plain_order = 0;
-        pw.units = pw.tiles_m_pad * pw.tiles_n * a->batch;
-        const int gw = pw.units < cus ? pw.units : cus;
-        PA_LAUNCH((gemm3w_kernel<2, 4>), dim3(gw), dim3(NT), 0, st, pw);
-        return 0;
-    }
-    // "tall" tiles (192 x 128, the same kernel with 3 x 2 MFMA tiles per wave), opt-in (PA_GEMM_TALL=1): a Linear whose 128 x 128
-    // tiling is a few units past one round of the CUs (N = 512 at 8.2 k - 12 k packed encoder rows: 260 - 384 units) becomes ONE
-    // round of at most 256 bigger units (round 6).  Measured LEVEL with the two-blocks-per-CU kernel - 8 704 x
-    // 512 x 512: 16.5 vs 16.2 us, x 1 024: 22.0 vs 22.2; train step 4.56-4.64 either way (profiles/r06_gemm_tile_choice.txt) -
-    // 184 units of 1.5 x the work cost what 272 units on 512 slots do.
-    if (go_tall) {
-        GemmP pw = pk;
-        pw.tiles_m = (a->M + 191) / 192; pw.tiles_n = (a->N + 127) / 128;
-        pw.plain_order = pw.tiles_m < 8;
-        pw.tiles_m_pad = pw.plain_order ? pw.tiles_m : (pw.tiles_m + 7) / 8 * 8;
-        pw.units = pw.tiles_m_pad * pw.tiles_n * a->batch;
-        const int gw = pw.units < cus ? pw.units : cus;
-        PA_LAUNCH((gemm3w_kernel<3, 2>), dim3(gw), dim3(NT), 0, st, pw);
-        return 0;
-    }
-    // small-tile ring kernel: plain k-contiguous Linears whose 128 x 128 tiling covers at most half of the CUs (measured: <= 128 units 7.05 ms/step, <= 64 7.11, <= 256 7.53)
-    if (go_small) {
-        GemmP ps = pk;
-        ps.tiles_m = (a->M + 63) / 64; ps.tiles_n = (a->N + 63) / 64; ps.tiles_m_pad = ps.tiles_m; ps.plain_order = 1;
-        ps.units = ps.tiles_m * ps.tiles_n * a->batch;
-        const int gs = ps.units < 2 * cus ? ps.units : 2 * cus;       // two 80 KB blocks fit a CU
-        PA_LAUNCH(gemm3s_kernel, dim3(gs), dim3(NT), 0, st, ps);
-        rc = 0;
-    } else
-    if (go_v3) {
-        const int g3 = pk.units < cus ? pk.units : cus;
-        if (a->a_kcontig && a->b_kcontig) PA_LAUNCH((gemm3_kernel<true, true, GemmP>), dim3(g3), dim3(NT), 0, st, pk);
-        else if (a->a_kcontig) PA_LAUNCH((gemm3_kernel<true, false, GemmP>), dim3(g3), dim3(NT), 0, st, pk);
-        else if (a->b_kcontig) PA_LAUNCH((gemm3_kernel<false, true, GemmP>), dim3(g3), dim3(NT), 0, st, pk);
-        else PA_LAUNCH((gemm3_kernel<false, false, GemmP>), dim3(g3), dim3(NT), 0, st, pk);
-        rc = 0;
-    } else
-    if (a->in_dtype == PA_BF16) {
-        if (bk32) rc = launch_layout<bf16, 32, 3>(pk, a->a_kcontig, a->b_kcontig, is_aligned<bf16>(a), glds, grid, st);
-        else rc = launch_layout<bf16, 64, 2>(pk, a->a_kcontig, a->b_kcontig, is_aligned<bf16>(a), glds, grid, st);
-    } else {
-        rc = launch_layout<float, 16, 2>(pk, a->a_kcontig, a->b_kcontig, is_aligned<float>(a), glds, grid, st);
-    }
-    if (rc) return rc;
-    if (splitk > 1 && a->splitk_defer) {
+    // (only the ring and pair kernels take split-K: every other family is planned for splitk == 1)
+    if (pl.splitk > 1 && a->splitk_defer) {
         // the caller reduces the slabs later: only plain f32 outputs qualify (no epilogue would be applied)
         if (a->out_dtype != PA_F32 || a->bias || a->R || a->aux || a->relu || a->drop_p > 0.f || a->alpha != 1.f || a->batch != 1) return PA_EINVAL;
         return 0;
     }
-    if (splitk > 1) {
+    if (pl.splitk > 1) {
         size_t total = (size_t)a->batch * a->M * a->N;
         int blocks = (int)((total + 255) / 256);
         if (blocks > 2048) blocks = 2048;
@@ -3154,6 +3144,17 @@ extern "C" int pa_gemm(const pa_gemm_args* a, void* stream) {
         else
             PA_LAUNCH(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, st, p, (const float*)a->ws);
     }
+    return 0;
+}
+
+// Dry run (include/plank_hip.h): the status, family and grid pa_gemm / pa_gemm_norm_a would use, from the same plan functions.
+extern "C" int pa_gemm_plan(const pa_gemm_args* a, const pa_gemm_norm_ext* x, pa_gemm_plan_info* out) {
+    if (!a || !out) return PA_EINVAL;
+    const GemmPlan pl = x ? plan_norm_a(*a, *x, gemm_switches(), cus_for_gemm()) : plan_gemm(*a, gemm_switches(), cus_for_gemm());
+    *out = pa_gemm_plan_info();
+    if (pl.status) return pl.status;
+    out->kind = pl.kind; out->tile_h = pl.tile_h; out->tile_w = pl.tile_w;
+    out->grid = pl.grid; out->block = pl.block; out->splitk = pl.splitk; out->units = pl.t.units;
     return 0;
 }
 
@@ -3199,72 +3200,21 @@ extern "C" int pa_ln_fold_weights_f32(float* Wf, float* u, float* v, const float
     return 0;
 }
 extern "C" int pa_gemm_norm_a(const pa_gemm_args* a, const pa_gemm_norm_ext* x, void* stream) {
-    if (!a || !x || !a->A || !a->B || !a->C || !a->bias || !x->u || a->M <= 0 || a->N <= 0 || a->K <= 0) return PA_EINVAL;
-    if ((a->in_dtype != PA_BF16 && a->in_dtype != PA_F32) || (a->out_dtype != PA_BF16 && a->out_dtype != PA_F32) || !a->a_kcontig || !a->b_kcontig) return PA_EINVAL;
-    if (a->in_dtype == PA_F32) {
-        // exact-f32 form (the f32 greedy-decode step): f32 rows, f32 folded weight (pa_ln_fold_weights_f32), f32 output; the statistics
-        // come from the rows themselves (ext->zf, normally == args->A).  Skinny kernel only: <= 512 rows, K = 512.
-        static const int sk_rows32 = getenv("PA_GEMM_SKINNY_ROWS") ? atoi(getenv("PA_GEMM_SKINNY_ROWS")) : 512;
-        if (a->batch != 1 || a->splitk > 1 || a->R || a->aux || a->drop_p != 0.f || a->N % 32) return PA_ESHAPE;
-        if (!x->zf || a->K != 512 || a->M > sk_rows32 || a->out_dtype != PA_F32 || (x->y && (!x->y_f32 || a->N < a->K))) return PA_ESHAPE;
-        if (x->y && (!x->gamma || !x->beta || x->ldy < a->K || x->ldy % 4 || (reinterpret_cast<uintptr_t>(x->y) & 15))) return PA_EINVAL;
-        if (!is_aligned<float>(a) || x->ldzf < a->K || x->ldzf % 4 || (reinterpret_cast<uintptr_t>(x->zf) & 15)) return PA_EALIGN;
-        GemmP p = GemmP();
-        p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias;
-        p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc;
-        p.batch = 1; p.alpha = a->alpha; p.relu = a->relu; p.aux_scale = 1.f; p.drop_scale = 1.f; p.out_dtype = PA_F32; p.splitk = 1;
-        p.tiles_m = (a->M + SK_T - 1) / SK_T; p.tiles_n = (a->N + SK_T - 1) / SK_T;
-        p.vec_ok = ((reinterpret_cast<uintptr_t>(a->C) & 15) == 0 && a->ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(a->bias) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(x->u) & 15) == 0 && (!x->y || ((reinterpret_cast<uintptr_t>(x->gamma) & 15) == 0 &&
-                                                                          (reinterpret_cast<uintptr_t>(x->beta) & 15) == 0))) ? 1 : 0;
-        if (!p.vec_ok) return PA_EALIGN;
-        p.ln_u = x->u; p.ln_gamma = x->gamma; p.ln_beta = x->beta; p.ln_y = x->y; p.ldy = x->ldy; p.ln_eps = x->eps;
-        p.ln_zf = x->zf; p.ldzf = x->ldzf; p.ln_y_f32 = 1;
-        PA_LAUNCH((gemm_skinny_kernel<float, true>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-        return 0;
-    }
-    if (a->batch != 1 || a->splitk > 1 || a->R || a->aux || a->drop_p != 0.f || a->K % 64 || a->N % 32) return PA_ESHAPE;
-    if (x->y && (!x->gamma || !x->beta || x->ldy < a->K || x->ldy % 4)) return PA_EINVAL;
-    if (x->y && (a->N + 63) / 64 * 64 < a->K) return PA_ESHAPE;      // column tile j materialises columns 64 j .. 64 j + 63 of LayerNorm(Z)
-    if (!is_aligned<bf16>(a)) return PA_EALIGN;
-    if (x->zf && (x->ldzf < a->K || x->ldzf % 4 || (reinterpret_cast<uintptr_t>(x->zf) & 15))) return PA_EINVAL;
-    if (x->y && x->y_f32 && (reinterpret_cast<uintptr_t>(x->y) & 15)) return PA_EALIGN;
-    // <= 512 rows and K = 512: the skinny kernel's form (the Z tile is resident in LDS, the statistics cost no memory round trip)
-    static const int sk_on = getenv("PA_GEMM_SKINNY") ? atoi(getenv("PA_GEMM_SKINNY")) : 2;
-    static const int sk_rows = getenv("PA_GEMM_SKINNY_ROWS") ? atoi(getenv("PA_GEMM_SKINNY_ROWS")) : 512;
-    if (sk_on >= 2 && a->M <= sk_rows && a->K == 512 && (!x->y || (a->N >= a->K && x->ldy % 8 == 0 && (reinterpret_cast<uintptr_t>(x->y) & 15) == 0 &&
-                                                                  (reinterpret_cast<uintptr_t>(x->gamma) & 15) == 0 &&
-                                                                  (reinterpret_cast<uintptr_t>(x->beta) & 15) == 0))) {
-        GemmP p = GemmP();
-        p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias;
-        p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc;
-        p.batch = 1; p.alpha = a->alpha; p.relu = a->relu; p.aux_scale = 1.f; p.drop_scale = 1.f; p.out_dtype = a->out_dtype;
-        p.splitk = 1;
-        p.tiles_m = (a->M + SK_T - 1) / SK_T; p.tiles_n = (a->N + SK_T - 1) / SK_T;
-        const int osz = a->out_dtype == PA_F32 ? 4 : 2;
-        p.vec_ok = ((reinterpret_cast<uintptr_t>(a->C) % (4 * osz)) == 0 && a->ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(a->bias) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(x->u) & 15) == 0) ? 1 : 0;
-        p.ln_u = x->u; p.ln_gamma = x->gamma; p.ln_beta = x->beta; p.ln_y = x->y; p.ldy = x->ldy; p.ln_eps = x->eps;
-        p.ln_zf = x->zf; p.ldzf = x->ldzf; p.ln_y_f32 = x->y_f32;
-        PA_LAUNCH((gemm_skinny_kernel<bf16, true>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-        return 0;
-    }
-    if (x->zf || x->y_f32) return PA_ESHAPE;               // the f32-residual form exists in the skinny kernel only
-    const int tiles = ((a->M + 63) / 64) * ((a->N + 63) / 64);
-    const int cus = cus_for_gemm();
-    if (tiles > 2 * cus) return PA_ESHAPE;                 // the row statistics live in registers: one unit per block
+    if (!a || !x) return PA_EINVAL;
+    const GemmPlan pl = plan_norm_a(*a, *x, gemm_switches(), cus_for_gemm());
+    if (pl.status) return pl.status;
     GemmP p = GemmP();                                     // (value-initialised: every optional pointer null)
-    p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias;
-    p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc;
-    p.batch = 1; p.alpha = a->alpha; p.relu = a->relu; p.aux_scale = 1.f; p.drop_scale = 1.f; p.out_dtype = a->out_dtype;
-    p.splitk = 1; p.tiles_per_slice = a->K / 64;
-    p.tiles_m = (a->M + 63) / 64; p.tiles_n = (a->N + 63) / 64; p.tiles_m_pad = p.tiles_m; p.plain_order = 1; p.units = tiles;
-    const int osz = a->out_dtype == PA_F32 ? 4 : 2;
-    p.vec_ok = ((reinterpret_cast<uintptr_t>(a->C) % (4 * osz)) == 0 && a->ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(a->bias) & 15) == 0 &&
-                (reinterpret_cast<uintptr_t>(x->u) & 15) == 0) ? 1 : 0;
-    if (!p.vec_ok) return PA_EALIGN;
+    fill_operands(p, *a);
+    p.splitk = 1; p.tiles_per_slice = pl.tiles_per_slice;
+    p.vec_ok = pl.vec_ok;
+    set_tiling(p, pl.t);
     p.ln_u = x->u; p.ln_gamma = x->gamma; p.ln_beta = x->beta; p.ln_y = x->y; p.ldy = x->ldy; p.ln_eps = x->eps;
-    PA_LAUNCH(gemm3s_kernel, dim3(tiles), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), p);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (pl.kernel == GK_SMALL) { PA_LAUNCH(gemm3s_kernel, dim3(pl.grid), dim3(pl.block), 0, st, p); return 0; }
+    // the skinny forms read the f32 rows behind A; the exact-f32 form always writes its LayerNorm(Z) as f32
+    p.ln_zf = x->zf; p.ldzf = x->ldzf; p.ln_y_f32 = a->in_dtype == PA_F32 ? 1 : x->y_f32;
+    if (a->in_dtype == PA_F32) PA_LAUNCH((gemm_skinny_kernel<float, true>), dim3(pl.grid), dim3(pl.block), 0, st, p);
+    else PA_LAUNCH((gemm_skinny_kernel<bf16, true>), dim3(pl.grid), dim3(pl.block), 0, st, p);
     return 0;
 }
 
@@ -3343,33 +3293,25 @@ extern "C" int pa_gemm_group(const pa_gemm_args* args, int32_t n, void* stream) 
         if (a->in_dtype != PA_BF16 || a->out_dtype != PA_F32 || a->a_kcontig || a->b_kcontig || a->batch != 1) return PA_EINVAL;
         if (a->bias || a->R || a->aux || a->relu || a->drop_p > 0.f || a->alpha != 1.f) return PA_EINVAL;
         if (!is_aligned<bf16>(a)) return PA_EINVAL;
-        const int nt = (a->K + 63) / 64;
-        int splitk = a->splitk > 1 ? a->splitk : 1;
-        if (splitk > nt) splitk = nt;
-        splitk = (nt + (nt + splitk - 1) / splitk - 1) / ((nt + splitk - 1) / splitk);
+        const int nt = (a->K + 63) / 64, splitk = eff_splitk(nt, a->splitk);
         if (splitk > 1 && (!a->ws || !a->splitk_defer)) return PA_EINVAL;
         GemmP& p = g.p[i];
         p = GemmP{};
-        p.A = a->A; p.B = a->B; p.M = a->M; p.N = a->N; p.K = a->K;
-        p.lda = a->lda; p.ldb = a->ldb; p.batch = 1;
-        p.alpha = 1.f; p.aux_scale = 1.f; p.drop_scale = 1.f; p.out_dtype = PA_F32;
+        fill_operands(p, *a);
         p.splitk = splitk; p.tiles_per_slice = (nt + splitk - 1) / splitk;
-        p.tiles_m = (a->M + BM - 1) / BM; p.tiles_n = (a->N + BN - 1) / BN;
-        p.tiles_m_pad = p.tiles_m; p.plain_order = 1;                    // plain unit order: every unit valid
-        p.units = p.tiles_m * p.tiles_n * splitk;
+        set_tiling(p, BM, BN, splitk, UNITS_PLAIN);                      // plain unit order: every unit valid
         if (splitk > 1) { p.C = a->ws; p.ldc = a->N; }
-        else { p.C = a->C; p.ldc = a->ldc; }
-        p.vec_ok = ((reinterpret_cast<uintptr_t>(p.C) & 15) == 0 && (p.ldc & 3) == 0) ? 1 : 0;
+        p.vec_ok = vec_ok(p.C, p.ldc, 0, 4);
         g.begin[i + 1] = g.begin[i] + p.units;
         valid += p.units;
-        if (g_rec) { std::lock_guard<std::mutex> lk(g_rec_mu); if (g_rec) { g_rec->push_back(*a); if (g_rec_kind) g_rec_kind->push_back(PA_GEMM_KIND_RING); if (g_rec_group) g_rec_group->push_back(g_rec_ngroups); } }
+        record_args(*a);
+        record_kind(PA_GEMM_KIND_RING, g_rec_ngroups);
     }
     if (g_rec) { std::lock_guard<std::mutex> lk(g_rec_mu); if (g_rec) ++g_rec_ngroups; }
     const int cus = cus_for_gemm();
     int grid = valid < cus ? valid : cus;
-    static const int xcd_order = [] { const char* e = getenv("PA_DW_XCD"); return e ? atoi(e) : 1; }();
     g.xcd_chunk = 0;
-    if (xcd_order && valid >= 64) {                 // (a handful of units: nothing to share)
+    if (gemm_switches().dw_xcd && valid >= 64) {                 // (a handful of units: nothing to share)
         g.xcd_chunk = (valid + 7) / 8;
         grid = (grid + 7) / 8 * 8;                  // slots of a block stay on its XCD
         if (grid > 8 * g.xcd_chunk) grid = 8 * g.xcd_chunk;
