@@ -416,6 +416,25 @@ int pa_attn_bwd(const pa_attn_args* a, void* stream);
  * shape would use it: split not enabled - PA_ATTN_SPLIT=1 -, H != 8, or L_max short enough for one block per tile) */
 int64_t pa_attn_ws_bytes(int32_t rows_total, int32_t B, int32_t H, int32_t L_max);
 int64_t pa_attn_ws_ticket_bytes(int64_t ws_bytes);
+/* Dry run of the dispatch: the status pa_attn_fwd(a) (bwd = 0) / pa_attn_bwd(a) (bwd != 0) would return before its first launch and,
+ * when that is 0, the launches it would make, in order, and the fields of the kernel argument block the dispatch decides.  Made by the
+ * same selection function the real calls run, under the same PA_ATTN_* / PA_X3_* switches and the caller's bf16x3 mode
+ * (pa_attn_split_config).  It launches nothing, needs no GPU, counts nothing in pa_attn_split_taken and never dereferences the
+ * operand pointers: only their values count (NULL tests, alignment, cu_q == cu_k). */
+typedef struct {
+    int32_t n_launches;         /* 1 (forward) .. 3 */
+    int32_t balanced;           /* 0, 1 = packed self-attention in length-balanced block order, 2 = the same cut into range blocks */
+    int32_t ks_min;             /* in-block key split: elements with fewer 64-key tiles run unsplit */
+    int32_t parts_q, parts_kv;  /* bf16x3 backward: blocks per owned tile of the dQ resp. dK/dV launch */
+    int32_t sp_slots;           /* range blocks: (owned tile, head) slots the scratch buffer `ws` holds */
+    struct {
+        char kernel[56];        /* the kernel's template-id as a demangler prints it, e.g. "attn4_fwd_kernel<true, 2>" */
+        uint32_t grid[3];
+        int32_t block, lds_bytes;
+        int32_t extra;          /* second kernel argument of attn4_bwd_merged_kernel (its dQ blocks); 0 elsewhere */
+    } launch[3];
+} pa_attn_plan_info;
+int pa_attn_plan(const pa_attn_args* a, int32_t bwd, pa_attn_plan_info* out);
 /* bf16x3 ("split") attention, the companion of pa_gemm_split_config: while `on`, f32 launches with dh = 64 compute every matrix
  * product of torch's F.multi_head_attention_forward (reference plankassembly/models.py:60-69: S = Q K^T, O = P V) and of its
  * backward as hi*hi + hi*lo + lo*hi of the operands' bf16 hi / lo parts with f32 accumulation (csrc/attention_x3.h); inputs,

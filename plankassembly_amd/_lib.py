@@ -71,6 +71,17 @@ class AttnArgs(C.Structure):
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+class AttnPlanLaunch(C.Structure):
+    _fields_ = [("kernel", C.c_char * 56), ("grid", C.c_uint32 * 3), ("block", C.c_int32), ("lds_bytes", C.c_int32),
+                ("extra", C.c_int32)]
+
+
+class AttnPlanInfo(C.Structure):
+    """include/plank_hip.h pa_attn_plan_info: what pa_attn_plan (the dry run of the attention dispatch) reports."""
+    _fields_ = [("n_launches", C.c_int32), ("balanced", C.c_int32), ("ks_min", C.c_int32), ("parts_q", C.c_int32),
+                ("parts_kv", C.c_int32), ("sp_slots", C.c_int32), ("launch", AttnPlanLaunch * 3)]
+
+
 class GroupDesc(C.Structure):
     _fields_ = [("idx", C.c_void_p), ("rowmap", C.c_void_p),
                 ("n", C.c_int32), ("rows", C.c_int32), ("kind", C.c_int32), ("T", C.c_int32), ("dof", C.c_int32),
@@ -157,6 +168,7 @@ def lib():
             "pa_layernorm_finish_many": (I, [P, I, I, P]),
             "pa_attn_fwd": (I, [P, P]),
             "pa_attn_bwd": (I, [P, P]),
+            "pa_attn_plan": (I, [P, I, P]),
             "pa_attn_ws_bytes": (I64, [I, I, I, I]),
             "pa_attn_ws_ticket_bytes": (I64, [I64]),
             "pa_attn_split_config": (I, [I]),

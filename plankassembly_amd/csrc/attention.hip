@@ -166,23 +166,6 @@ template <int DH> struct StoreTr<float, DH> {
         }
     }
 };
-template <int DH> struct StoreTr<bf16, DH> {
-    static __device__ __forceinline__ void run(const u32x4* regs, char* lds, int sb) {
-        using A = AT<bf16, DH>;
-        const int cb = sb % A::NCHR, rb = sb / A::NCHR;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            u32x2 o;
-#pragma unroll
-            for (int qd = 0; qd < 2; ++qd) {
-                const uint32_t lo = regs[2 * qd][e >> 1], hi = regs[2 * qd + 1][e >> 1];
-                o[qd] = (e & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-            }
-            // row d = cb*8+e, columns rb*4..+3 = 8 bytes at byte rb*8: chunk rb>>1, sub (rb&1)*8
-            *reinterpret_cast<u32x2*>(lds + swz_off<A::RBT>(cb * 8 + e, rb >> 1) + (rb & 1) * 8) = o;
-        }
-    }
-};
 
 // ---- MFMA helpers ------------------------------------------------------------------------------------
 // acc(32 x 32) += NAT[row0 + (lane&31)][:] (A operand, contraction over dh) x regs (B operand)
@@ -215,33 +198,6 @@ template <int DH> struct MmaTr<float, DH> {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     acc[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a[e]), pv[4 * g + e], acc[dt], 0, 0, 0);
-            }
-        }
-    }
-};
-template <int DH> struct MmaTr<bf16, DH> {
-    static __device__ __forceinline__ void run(f32x16* acc, const char* tr, int col0, const f32x16& pv, int lane) {
-        using A = AT<bf16, DH>;
-        const int half = lane >> 5;
-        u32x4 pb[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) pb[u][w] = pack_bf16(pv[8 * u + 2 * w], pv[8 * u + 2 * w + 1]);
-#pragma unroll
-        for (int dt = 0; dt < A::NDT; ++dt) {
-            const int d = dt * 32 + (lane & 31);
-            const bool ok = d < DH;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int col = col0 + 16 * u + 4 * half;           // bytes col*2: chunk (col>>3), sub (col&7)*2
-                u32x4 a = {0u, 0u, 0u, 0u};
-                if (ok) {
-                    const u32x2 a0 = *reinterpret_cast<const u32x2*>(tr + swz_off<A::RBT>(d, col >> 3) + (col & 7) * 2);
-                    const u32x2 a1 = *reinterpret_cast<const u32x2*>(tr + swz_off<A::RBT>(d, (col + 8) >> 3) + (col & 7) * 2);
-                    a[0] = a0[0]; a[1] = a0[1]; a[2] = a1[0]; a[3] = a1[1];
-                }
-                mma16B<bf16>(acc[dt], a, pb[u]);
             }
         }
     }
@@ -840,26 +796,8 @@ template <int DH> struct BT {
     static constexpr int NDT = (DH + 31) / 32;
 };
 
-// DMA one 64-row natural tile (rows row0.. of a [nrows][ld] bf16 matrix, DH columns at column offset 0 of `base`)
-template <int DH>
-__device__ __forceinline__ void glds_nat(char* lds, const bf16* base, int ld, int row0, int nrows, int tid, int wave) {
-    using B = BT<DH>;
-    constexpr int RPB = (B::RBN >= 256) ? 1 : 256 / B::RBN;
-#pragma unroll
-    for (int i = 0; i < B::NLD; ++i) {
-        const int p = tid + i * NTH;
-        if (B::NCHUNK % NTH == 0 || p < B::NCHUNK) {
-            const int row = p / B::NCHR;
-            const int ch = ((p % B::NCHR) ^ tile_key<B::RBN>(row)) & (B::NCHR - 1);       // source chunk that belongs at position p
-            const int r = min(row0 + row, nrows - 1);                            // clamp: masked rows still read finite data
-            const bf16* src = base + (size_t)r * ld + ch * 8;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                (__attribute__((address_space(3))) void*)(lds + (i * NTH + wave * 64) * 16), 16, 0, 0);
-        }
-    }
-}
-
-// The same tile DMA through a buffer resource (v3 kernels): `voff` is the per-thread byte offset of its first chunk inside a
+// DMA of one 64-row natural tile (DH columns at column offset 0 of the base) through a buffer resource (v3 kernels): `voff` is
+// the per-thread byte offset of its first chunk inside a
 // tile (tile_voff, loop invariant: ONE VGPR for every tile of a matrix), and every round of a tile gets its own resource
 // descriptor (four SGPRs, scalar arithmetic only) whose base is the round's first row and whose size ends at the sample's
 // last row: rows past the end read as ZEROS through the hardware range check - no clamp, no 64-bit vector address
@@ -882,7 +820,6 @@ __device__ __forceinline__ TileSrc tile_src(const bf16* base, int ld, int nrows,
 }
 template <int DH> __device__ __forceinline__ int tile_voff(int ld, int tid) {
     using B = BT<DH>;
-    constexpr int RPB = (B::RBN >= 256) ? 1 : 256 / B::RBN;
     const int row = tid / B::NCHR;
     const int ch = ((tid % B::NCHR) ^ tile_key<B::RBN>(row)) & (B::NCHR - 1);           // source chunk that belongs at position tid
     return (row * ld + ch * 8) * 2;
@@ -2278,274 +2215,110 @@ __global__ __launch_bounds__(NT4, 4) void attn4_bwd_merged_kernel(AttnP pin, int
 #include "attention_x3.h"
 
 // =====================================================================================================
-static int split_kmax() { static const int v = getenv("PA_ATTN_SPLIT_KMAX") ? atoi(getenv("PA_ATTN_SPLIT_KMAX")) : 8; return v < 1 ? 1 : v; }
-static int split_pmax() { static const int v = getenv("PA_ATTN_SPLIT_PMAX") ? atoi(getenv("PA_ATTN_SPLIT_PMAX")) : 2; return v < 1 ? 1 : v > 8 ? 8 : v; }
-AttnP make_params(const pa_attn_args* a) {
-    AttnP p;
-    p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o; p.lse = a->lse; p.kpm = a->kpm;
-    p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk;
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.causal = a->causal; p.scale = a->scale;
-    p.drop_thr = (uint32_t)((double)a->drop_p * 4294967296.0);     // keep <=> 32-bit product >= thr (pa_device.h drop_keep2)
-    p.drop_scale = (float)(1.0 / (1.0 - (double)p.drop_thr / 4294967296.0));
-    p.drop_seed = a->drop_seed;
-    p.dout = a->dout; p.dq = a->dq; p.dk = a->dk; p.dv = a->dv; p.delta = a->delta;
-    p.lddo = a->lddo; p.lddq = a->lddq; p.lddk = a->lddk; p.lddv = a->lddv;
-    p.cu_q = a->cu_q; p.cu_k = a->cu_k; p.order = a->order;
-    static const bool bal_env = !(getenv("PA_ATTN_BALANCED") && atoi(getenv("PA_ATTN_BALANCED")) == 0);
-    p.ks_min = 4; p.parts_q = 1; p.parts_kv = 1;
-    p.balanced = (bal_env && a->order && a->cu_q && a->cu_k && a->H == 8 && a->B <= 64) ? 1 : 0;
-    // range blocks (balanced == 2, set by the launchers whose kernels know it): packed self-attention with scratch from the caller.
-    // PA_ATTN_SPLIT=1 enables (default off); PA_ATTN_SPLIT_KMAX (8) longest unsplit chain in 64-row tiles; PA_ATTN_SPLIT_PMAX (2) most ranges.
-    p.sp_tick = nullptr; p.sp_part = nullptr; p.sp_slots = 0; p.sp_pmax = split_pmax(); p.sp_kmax = split_kmax();
-    static const bool sp_env = getenv("PA_ATTN_SPLIT") && atoi(getenv("PA_ATTN_SPLIT")) != 0;     // opt-in: measured slower (profiles/r06_attention_launch_shape.txt)
-    if (sp_env && p.balanced && a->ws && a->cu_q == a->cu_k && !a->kpm && !a->causal && a->dtype == PA_BF16 && a->dh == 64 &&
-        (reinterpret_cast<uintptr_t>(a->ws) & 255) == 0 && p.sp_pmax > 1) {
-        const int64_t per = (int64_t)p.sp_pmax * SP_BYTES + 64;          // one (owned tile, head): its range blocks' partials + ticket
-        const int64_t total = a->ws_bytes / per;
-        p.sp_slots = (int)(total / 8 < (1 << 20) ? total / 8 : (1 << 20));
-        p.sp_tick = static_cast<int*>(a->ws);
-        p.sp_part = static_cast<char*>(a->ws) + ((int64_t)p.sp_slots * 8 * 4 + 255) / 256 * 256;
-        if ((int64_t)p.sp_slots * 8 * per > a->ws_bytes || p.sp_slots < 1) { p.sp_slots = 0; p.sp_tick = nullptr; }
-    }
-    return p;
-}
-// blocks of a balanced == 2 launch: an upper bound of the units (the host does not know the elements' lengths; surplus blocks exit)
-static unsigned split_grid(const AttnP& p, int owned_max, int streamed_max) {
-    const int ks = (streamed_max + BSTR - 1) / BSTR;
-    const int np = ks > p.sp_kmax ? std::min(p.sp_pmax, (ks + p.sp_kmax - 1) / p.sp_kmax) : 1;
-    return (unsigned)(8 * p.B * ((owned_max + BOWN - 1) / BOWN) * np);
-}
-
-template <typename K> int set_lds(K kern, int bytes) {
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
-// 16-row waves (v4, dh = 64) for launches that cannot fill the SIMDs with 32-row waves: variable-length (packed) batches and
-// launches with fewer than four 32-row waves per SIMD.  Measured (tools/attn_bench.py): packed self-attention forward 35.9 ->
-// 32.9 us, cross-attention forward / backward 28.9 -> 23.5 / 57.1 -> 52.9 us, but the dense padded S = 1024 launch (4 096
-// 32-row waves, VALU-bound) 67.9 -> 75.0 us - twice the LDS operand reads and barriers for no extra occupancy.
-// PA_ATTN_V4=0 never, 2 always.
-static bool use_v4(const AttnP& p, int rows_owned) {
-    static const int mode = getenv("PA_ATTN_V4") ? atoi(getenv("PA_ATTN_V4")) : 1;
-    if (mode == 0) return false;
-    if (mode >= 2) return true;
-    const long long waves32 = (long long)p.B * p.H * ((rows_owned + 31) / 32);
-    return p.cu_q != nullptr || p.cu_k != nullptr || waves32 < 4 * 1024;
-}
-// In-block key split of the 16-row-wave forward / dQ kernels (attn4_fwd_kernel): for launches whose duration is one block's
-// serial chain of key steps - few blocks, many keys.  PA_ATTN_KSPLIT: 0 never, 1 (default) cross-attention-like launches (at
-// most one block per CU and at least 4 key tiles), 2 every eligible launch (no key-padding mask, not causal).
-static bool use_ksplit(AttnP& p, unsigned blocks) {
-    static const int mode = getenv("PA_ATTN_KSPLIT") ? atoi(getenv("PA_ATTN_KSPLIT")) : 1;
-    static const int min_few = getenv("PA_ATTN_KSPLIT_MIN") ? atoi(getenv("PA_ATTN_KSPLIT_MIN")) : 4;
-    static const int min_many = getenv("PA_ATTN_KSPLIT_MIN2") ? atoi(getenv("PA_ATTN_KSPLIT_MIN2")) : 10;
-    if (mode == 0 || p.kpm || p.causal || p.Lk < 4 * BSTR) return false;
-    // at most one block per CU (cross-attention): every element with >= 4 key tiles; more blocks than CUs (packed
-    // self-attention, mode 2): only the long elements, whose chain of key steps sets the duration of the launch
-    p.ks_min = blocks <= 256 ? min_few : min_many;
-    return mode >= 2 || blocks <= 256;
-}
-// v5 forward (attention5.h): PA_ATTN_V5 = 0 never, 1 (default) self-attention-like launches (not causal, at least two 128-row
-// query tiles per element), 2 every non-causal dh = 64 launch.
-static bool use_v5(const AttnP& p) {
-    static const int mode = getenv("PA_ATTN_V5") ? atoi(getenv("PA_ATTN_V5")) : 1;
-    if (mode == 0 || p.causal) return false;
-    return mode >= 2 || p.Lq > BOWN;
-}
-template <int DH> int run_fwd_bf16(AttnP p, hipStream_t st) {
-    const int shm = BL<DH>::SHM;
-    dim3 grid(((p.Lq + BOWN - 1) / BOWN) * p.H * p.B);
-    if constexpr (DH == 64) {
-        if (use_v5(p)) {
-            // PA_ATTN_V5_OCC: 3 (default) three blocks per CU with a 3-stage K/V ring, 2: two blocks per CU, 4 stages
-            static const int occ = getenv("PA_ATTN_V5_OCC") ? atoi(getenv("PA_ATTN_V5_OCC")) : 3;
-            static const int rc4 = set_lds(attn5_fwd_kernel<true, 4, 2>, L5<4>::SHM) | set_lds(attn5_fwd_kernel<false, 4, 2>, L5<4>::SHM);
-            if (rc4) return rc4;
-            if (p.balanced && p.sp_tick) { p.balanced = 2; grid = dim3(split_grid(p, p.Lq, p.Lk)); }
-            if (occ == 2) {
-                if (p.drop_thr) PA_LAUNCH((attn5_fwd_kernel<true, 4, 2>), grid, dim3(NTH), L5<4>::SHM, st, p);
-                else PA_LAUNCH((attn5_fwd_kernel<false, 4, 2>), grid, dim3(NTH), L5<4>::SHM, st, p);
-            } else {
-                if (p.drop_thr) PA_LAUNCH((attn5_fwd_kernel<true, 3, 3>), grid, dim3(NTH), L5<3>::SHM, st, p);
-                else PA_LAUNCH((attn5_fwd_kernel<false, 3, 3>), grid, dim3(NTH), L5<3>::SHM, st, p);
-            }
-            return 0;
-        }
-        if (use_v4(p, p.Lq)) {
-            if (use_ksplit(p, grid.x)) {
-                constexpr int shm2 = 4 * BL<DH>::BUF + 64;                 // two pairs of stages: > 64 KiB, opt in once
-                static const int rc_d = set_lds(attn4_fwd_kernel<true, 2>, shm2), rc_n = set_lds(attn4_fwd_kernel<false, 2>, shm2);
-                if (rc_d || rc_n) return rc_d ? rc_d : rc_n;
-                if (p.drop_thr) PA_LAUNCH((attn4_fwd_kernel<true, 2>), grid, dim3(2 * NT4), shm2, st, p);
-                else PA_LAUNCH((attn4_fwd_kernel<false, 2>), grid, dim3(2 * NT4), shm2, st, p);
-                return 0;
-            }
-            if (p.drop_thr) PA_LAUNCH((attn4_fwd_kernel<true, 1>), grid, dim3(NT4), shm, st, p);
-            else PA_LAUNCH((attn4_fwd_kernel<false, 1>), grid, dim3(NT4), shm, st, p);
-            return 0;
-        }
-    }
-    if (p.drop_thr) PA_LAUNCH((attn_fwd_bf16_kernel<DH, true>), grid, dim3(NTH), shm, st, p);
-    else PA_LAUNCH((attn_fwd_bf16_kernel<DH, false>), grid, dim3(NTH), shm, st, p);
-    return 0;
-}
-template <int DH> int run_bwd_bf16(AttnP p, hipStream_t st) {
-    const int shm = BL<DH>::SHM;
-    const dim3 gq0(((p.Lq + BOWN - 1) / BOWN) * p.H * p.B), gk0(((p.Lk + BOWN - 1) / BOWN) * p.H * p.B);
-    if constexpr (DH == 64) {
-        if (use_v4(p, p.Lq > p.Lk ? p.Lq : p.Lk)) {
-            dim3 gq = gq0, gk = gk0;
-            // single query tile per (sample, head): dQ and dK/dV blocks in one launch (PA_ATTN_BWD_MERGE=0: two launches)
-            static const bool merge_env = !(getenv("PA_ATTN_BWD_MERGE") && atoi(getenv("PA_ATTN_BWD_MERGE")) == 0);
-            static const int merge_max = getenv("PA_ATTN_BWD_MERGE_MAX") ? atoi(getenv("PA_ATTN_BWD_MERGE_MAX")) : 128;
-            if (merge_env && p.Lq <= merge_max && p.Lq <= 2048 && (gq.x & 7) == 0) {
-                const int shm3 = shm + (p.Lq + 15) / 16 * 64 + 64;
-                const dim3 gm(gq.x + gk.x);
-                if (p.drop_thr) {
-                    if (p.causal) PA_LAUNCH((attn4_bwd_merged_kernel<true, true>), gm, dim3(NT4), shm3, st, p, (int)gq.x);
-                    else PA_LAUNCH((attn4_bwd_merged_kernel<true, false>), gm, dim3(NT4), shm3, st, p, (int)gq.x);
-                } else {
-                    if (p.causal) PA_LAUNCH((attn4_bwd_merged_kernel<false, true>), gm, dim3(NT4), shm3, st, p, (int)gq.x);
-                    else PA_LAUNCH((attn4_bwd_merged_kernel<false, false>), gm, dim3(NT4), shm3, st, p, (int)gq.x);
-                }
-                return 0;
-            }
-            bool ks = use_ksplit(p, gq.x);
-            constexpr int shm2 = 4 * BL<DH>::BUF + 64;
-            if (p.balanced && p.sp_tick && !ks) { p.balanced = 2; gq = dim3(split_grid(p, p.Lq, p.Lk)); gk = dim3(split_grid(p, p.Lk, p.Lq)); }
-            if (ks) {
-                static const int rc_d = set_lds(attn4_bwd_dq_kernel<true, 2>, shm2), rc_n = set_lds(attn4_bwd_dq_kernel<false, 2>, shm2);
-                if (rc_d || rc_n) return rc_d ? rc_d : rc_n;
-            }
-            if (p.drop_thr) {
-                if (ks) PA_LAUNCH((attn4_bwd_dq_kernel<true, 2>), gq, dim3(2 * NT4), shm2, st, p);
-                else PA_LAUNCH((attn4_bwd_dq_kernel<true, 1>), gq, dim3(NT4), shm, st, p);
-                if (p.causal) PA_LAUNCH((attn4_bwd_dkv_kernel<true, true>), gk, dim3(NT4), shm, st, p);
-                else PA_LAUNCH((attn4_bwd_dkv_kernel<true, false>), gk, dim3(NT4), shm, st, p);
-            } else {
-                if (ks) PA_LAUNCH((attn4_bwd_dq_kernel<false, 2>), gq, dim3(2 * NT4), shm2, st, p);
-                else PA_LAUNCH((attn4_bwd_dq_kernel<false, 1>), gq, dim3(NT4), shm, st, p);
-                if (p.causal) PA_LAUNCH((attn4_bwd_dkv_kernel<false, true>), gk, dim3(NT4), shm, st, p);
-                else PA_LAUNCH((attn4_bwd_dkv_kernel<false, false>), gk, dim3(NT4), shm, st, p);
-            }
-            return 0;
-        }
-    }
-    const dim3 gq = gq0, gk = gk0;
-    // blocks per CU the register allocation is made for (experiment knob PA_ATTN_OCC="<dq><dkv>", e.g. "43")
-    static const int occ_env = getenv("PA_ATTN_OCC") ? atoi(getenv("PA_ATTN_OCC")) : 0;
-    const int oq = occ_env ? occ_env / 10 : 3, ok = occ_env ? occ_env % 10 : 2;
-    if (p.drop_thr) {
-        if (oq >= 4) PA_LAUNCH((attn_bwd_dq_bf16_kernel<DH, true, 4>), gq, dim3(NTH), shm, st, p);      // also writes delta
-        else PA_LAUNCH((attn_bwd_dq_bf16_kernel<DH, true, 3>), gq, dim3(NTH), shm, st, p);
-        if (ok >= 3) { if (p.causal) PA_LAUNCH((attn_bwd_dkv_bf16_kernel<DH, true, 3, true>), gk, dim3(NTH), shm, st, p); else PA_LAUNCH((attn_bwd_dkv_bf16_kernel<DH, true, 3, false>), gk, dim3(NTH), shm, st, p); }
-        else { if (p.causal) PA_LAUNCH((attn_bwd_dkv_bf16_kernel<DH, true, 2, true>), gk, dim3(NTH), shm, st, p); else PA_LAUNCH((attn_bwd_dkv_bf16_kernel<DH, true, 2, false>), gk, dim3(NTH), shm, st, p); }
-    } else {
-        if (oq >= 4) PA_LAUNCH((attn_bwd_dq_bf16_kernel<DH, false, 4>), gq, dim3(NTH), shm, st, p);
-        else PA_LAUNCH((attn_bwd_dq_bf16_kernel<DH, false, 3>), gq, dim3(NTH), shm, st, p);
-        if (ok >= 3) { if (p.causal) PA_LAUNCH((attn_bwd_dkv_bf16_kernel<DH, false, 3, true>), gk, dim3(NTH), shm, st, p); else PA_LAUNCH((attn_bwd_dkv_bf16_kernel<DH, false, 3, false>), gk, dim3(NTH), shm, st, p); }
-        else { if (p.causal) PA_LAUNCH((attn_bwd_dkv_bf16_kernel<DH, false, 2, true>), gk, dim3(NTH), shm, st, p); else PA_LAUNCH((attn_bwd_dkv_bf16_kernel<DH, false, 2, false>), gk, dim3(NTH), shm, st, p); }
-    }
-    return 0;
+// Host side: attn_switches() reads every switch once, plan_attn() - a pure function - turns an argument block into the status, the
+// finished AttnP and the 1 to 3 launches of a call, launch_plan() walks that over KERNELS, the table of every kernel of this object.
+// pa_attn_plan reports the same plan without launching (tests/test_attn_plan_cpu.py pins it on machines without a GPU).
+struct AttnSwitches {
+    // packed self-attention
+    int balanced;          // PA_ATTN_BALANCED (1): 0 = no length-balanced block order for packed self-attention with `order`
+    int split;             // PA_ATTN_SPLIT (0): 1 = range blocks (balanced == 2) for packed bf16 self-attention with scratch from the
+                           //   caller - opt-in: measured slower (profiles/r06_attention_launch_shape.txt)
+    int split_kmax;        // PA_ATTN_SPLIT_KMAX (8, >= 1): longest unsplit chain in 64-row tiles
+    int split_pmax;        // PA_ATTN_SPLIT_PMAX (2, 1 .. 8): most ranges
+    // kernel family, bf16 dh = 64
+    int v4;                // PA_ATTN_V4 (1): 16-row waves for launches that cannot fill the SIMDs with 32-row waves; 0 never, 2 always
+    int v5;                // PA_ATTN_V5 (1): v5 forward (attention5.h) for self-attention-like launches; 0 never, 2 every non-causal one
+    int v5_occ;            // PA_ATTN_V5_OCC (3): three blocks per CU with a 3-stage K/V ring; 2: two blocks per CU, 4 stages
+    int occ;               // PA_ATTN_OCC ("<dq><dkv>", unset = 3 / 2): blocks per CU the 32-row-wave backward is allocated for
+    // in-block key split of the 16-row-wave forward / dQ kernels
+    int ksplit;            // PA_ATTN_KSPLIT (1): cross-attention-like launches; 0 never, 2 every eligible launch
+    int ksplit_min;        // PA_ATTN_KSPLIT_MIN (4): fewest key tiles of a split element, launches of at most one block per CU
+    int ksplit_min2;       // PA_ATTN_KSPLIT_MIN2 (10): the same for launches of more blocks than CUs
+    // 16-row-wave backward
+    int bwd_merge;         // PA_ATTN_BWD_MERGE (1): dQ and dK/dV blocks of a single-query-tile backward in one launch; 0: two
+    int bwd_merge_max;     // PA_ATTN_BWD_MERGE_MAX (128): most query rows of a merged launch (never above 2048)
+    // bf16x3 backward (attention_x3.h)
+    int x3_parts;          // PA_X3_PARTS (0): n >= 2 = n range blocks per owned tile adding partial dQ / dK / dV with f32 atomics.  OFF:
+                           //   measured on MI355X, x3 train step 13.0 ms unsplit, 16.4 ms with 2 parts, 20.2 ms with 4
+    int x3_parts_min;      // PA_X3_PARTS_MIN (512): fewest streamed rows of a launch that is cut
+    int x3_dkv_occ;        // PA_X3_DKV_OCC (1): dK/dV allocated for one block per CU (no spills; 12.72 against 12.82 ms per x3 step); 2: two
+};
+const AttnSwitches& attn_switches() {
+    static const AttnSwitches sw = [] {
+        auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+        AttnSwitches s;
+        s.balanced = env("PA_ATTN_BALANCED", 1);
+        s.split = env("PA_ATTN_SPLIT", 0);
+        s.split_kmax = std::max(env("PA_ATTN_SPLIT_KMAX", 8), 1);
+        s.split_pmax = std::min(std::max(env("PA_ATTN_SPLIT_PMAX", 2), 1), 8);
+        s.v4 = env("PA_ATTN_V4", 1);
+        s.v5 = env("PA_ATTN_V5", 1);
+        s.v5_occ = env("PA_ATTN_V5_OCC", 3);
+        s.occ = env("PA_ATTN_OCC", 0);
+        s.ksplit = env("PA_ATTN_KSPLIT", 1);
+        s.ksplit_min = env("PA_ATTN_KSPLIT_MIN", 4);
+        s.ksplit_min2 = env("PA_ATTN_KSPLIT_MIN2", 10);
+        s.bwd_merge = env("PA_ATTN_BWD_MERGE", 1);
+        s.bwd_merge_max = env("PA_ATTN_BWD_MERGE_MAX", 128);
+        s.x3_parts = env("PA_X3_PARTS", 0);
+        s.x3_parts_min = env("PA_X3_PARTS_MIN", 512);
+        s.x3_dkv_occ = env("PA_X3_DKV_OCC", 1);
+        return s;
+    }();
+    return sw;
 }
 
-// bf16x3 attention (attention_x3.h) for f32 launches with dh = 64 while pa_attn_split_config(1) is in force
-extern "C" int pa_split_attn_set(int32_t on);       // gemm.hip: the flag lives in the current bf16x3 context (pa_split_ctx_*)
-extern "C" int pa_split_attn_active(void);
-std::atomic<long long> g_attn_x3_taken{0};
-template <typename T, int DH> int run_fwd(const AttnP& p, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) return run_fwd_bf16<DH>(p, st);
-    if constexpr (sizeof(T) == 4 && DH == 64) {
-        if (pa_split_attn_active()) {
-            const int shm = X3L<DH>::SHM;
-            static const int rc_ = set_lds(attnx_fwd_kernel<DH, true>, shm) | set_lds(attnx_fwd_kernel<DH, false>, shm);
-            if (rc_) return rc_;
-            const dim3 gq((p.Lq + BOWN - 1) / BOWN, p.H, p.B);
-            if (p.drop_thr) PA_LAUNCH((attnx_fwd_kernel<DH, true>), gq, dim3(NTH), shm, st, p);
-            else PA_LAUNCH((attnx_fwd_kernel<DH, false>), gq, dim3(NTH), shm, st, p);
-            g_attn_x3_taken.fetch_add(1);
-            return 0;
-        }
-    }
-    const int shm = 2 * Smem<T, DH>::BUF_FWD;
-    int rc = set_lds(attn_fwd_kernel<T, DH>, shm);
-    if (rc) return rc;
-    dim3 grid((p.Lq + BOWN - 1) / BOWN, p.H, p.B);
-    PA_LAUNCH((attn_fwd_kernel<T, DH>), grid, dim3(NTH), shm, st, p);
-    return 0;
-}
-template <typename T, int DH> int run_bwd(const AttnP& p_in, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) return run_bwd_bf16<DH>(p_in, st);
-    AttnP p = p_in;
-    const int64_t total = (int64_t)p.B * p.H * p.Lq;
-    bool x3 = false;
-    if constexpr (sizeof(T) == 4 && DH == 64) {
-        x3 = pa_split_attn_active() != 0;
-        if (x3) {
-            // PA_X3_PARTS=n (n >= 2): range-split backward, n blocks per owned tile adding their partial dQ / dK / dV with f32
-            // atomics (attention_x3.h x3_add_rows).  OFF by default - MEASURED on MI355X, round 5, x3 train step: 13.0 ms unsplit,
-            // 16.4 ms with 2 parts, 20.2 ms with 4 (packed encoder backward 360 -> 843 us): the atomic adds of 128 x 64 f32 tiles
-            // at a 6 KB row stride cost several times the chain they shorten.  Results are equal to rounding either way
-            // (tests/test_kernels_gpu.py::test_attention_x3_* pass with PA_X3_PARTS=4).
-            static const int parts_env = getenv("PA_X3_PARTS") ? atoi(getenv("PA_X3_PARTS")) : 0;
-            static const int parts_min = getenv("PA_X3_PARTS_MIN") ? atoi(getenv("PA_X3_PARTS_MIN")) : 512;
-            const int n = parts_env;
-            if (n >= 2) {
-                if (p.Lk >= parts_min) p.parts_q = n;
-                if (p.Lq >= parts_min && p.Lk <= p.Lq && (!p.cu_q || p.cu_q == p.cu_k)) p.parts_kv = n;     // self-attention shapes only
-            }
-        }
-    }
-    PA_LAUNCH((attn_delta_kernel<T, DH>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p);
-    if constexpr (sizeof(T) == 4 && DH == 64) {
-        if (x3) {
-            const int shk = X3L<DH>::SHM, shq = X3L<DH>::SHM;
-            static const int rc_ = set_lds(attnx_bwd_dkv_kernel<DH, true, 2>, shk) | set_lds(attnx_bwd_dq_kernel<DH, true>, shq) |
-                                   set_lds(attnx_bwd_dkv_kernel<DH, false, 2>, shk) | set_lds(attnx_bwd_dq_kernel<DH, false>, shq) |
-                                   set_lds(attnx_bwd_dkv_kernel<DH, true, 1>, shk) | set_lds(attnx_bwd_dkv_kernel<DH, false, 1>, shk);
-            if (rc_) return rc_;
-            // dK / dV at two blocks per CU sits at the 256-register limit and spills 160 bytes per lane; allocated for ONE block per CU
-            // (no spills, one wave per SIMD) the x3 step measures 12.72 against 12.82 ms (A/B twice in one session): default 1
-            static const int dkv_occ = getenv("PA_X3_DKV_OCC") ? atoi(getenv("PA_X3_DKV_OCC")) : 1;
-            const dim3 gk(((p.Lk + BOWN - 1) / BOWN) * p.parts_kv, p.H, p.B), gq(((p.Lq + BOWN - 1) / BOWN) * p.parts_q, p.H, p.B);
-            if (p.drop_thr) {
-                if (dkv_occ == 1) PA_LAUNCH((attnx_bwd_dkv_kernel<DH, true, 1>), gk, dim3(NTH), shk, st, p);
-                else PA_LAUNCH((attnx_bwd_dkv_kernel<DH, true, 2>), gk, dim3(NTH), shk, st, p);
-                PA_LAUNCH((attnx_bwd_dq_kernel<DH, true>), gq, dim3(NTH), shq, st, p);
-            } else {
-                if (dkv_occ == 1) PA_LAUNCH((attnx_bwd_dkv_kernel<DH, false, 1>), gk, dim3(NTH), shk, st, p);
-                else PA_LAUNCH((attnx_bwd_dkv_kernel<DH, false, 2>), gk, dim3(NTH), shk, st, p);
-                PA_LAUNCH((attnx_bwd_dq_kernel<DH, false>), gq, dim3(NTH), shq, st, p);
-            }
-            g_attn_x3_taken.fetch_add(1);
-            return 0;
-        }
-    }
-    int shm = 2 * Smem<T, DH>::BUF_DKV;
-    int rc = set_lds(attn_bwd_dkv_kernel<T, DH>, shm);
-    if (rc) return rc;
-    PA_LAUNCH((attn_bwd_dkv_kernel<T, DH>), dim3((p.Lk + BOWN - 1) / BOWN, p.H, p.B), dim3(NTH), shm, st, p);
-    shm = 2 * Smem<T, DH>::BUF_DQ;
-    rc = set_lds(attn_bwd_dq_kernel<T, DH>, shm);
-    if (rc) return rc;
-    PA_LAUNCH((attn_bwd_dq_kernel<T, DH>), dim3((p.Lq + BOWN - 1) / BOWN, p.H, p.B), dim3(NTH), shm, st, p);
-    return 0;
-}
+// ---- the kernels: one row per instantiation, in the order the K_* indices count -------------------------------------------------
+// Every family lists its template arguments in DESCENDING order (true before false, the larger number first); nd = !drop etc. below.
+// That is the order the launch ladders this table replaced instantiated them in, and it is kept because hipcc's register numbering
+// in the bf16 kernels follows the order of instantiation (profiles/attn_dispatch_refactor.txt, section 1).
+struct KernelRow { const char* name; const void* fn; };
+#define ROW(...) {#__VA_ARGS__, reinterpret_cast<const void*>(&__VA_ARGS__)}
+#define ROWS_BB(K) ROW(K<true, true>), ROW(K<true, false>), ROW(K<false, true>), ROW(K<false, false>)
+#define ROWS_KS(K) ROW(K<true, 2>), ROW(K<true, 1>), ROW(K<false, 2>), ROW(K<false, 1>)
+#define ROWS_BWD32(DH, DROP) ROW(attn_bwd_dq_bf16_kernel<DH, DROP, 4>), ROW(attn_bwd_dq_bf16_kernel<DH, DROP, 3>), \
+                             ROW(attn_bwd_dkv_bf16_kernel<DH, DROP, 3, true>), ROW(attn_bwd_dkv_bf16_kernel<DH, DROP, 3, false>), \
+                             ROW(attn_bwd_dkv_bf16_kernel<DH, DROP, 2, true>), ROW(attn_bwd_dkv_bf16_kernel<DH, DROP, 2, false>)
+#define ROWS_32(DH) ROWS_BWD32(DH, true), ROWS_BWD32(DH, false), ROW(attn_fwd_bf16_kernel<DH, true>), ROW(attn_fwd_bf16_kernel<DH, false>)
+#define ROWS_F32(DH) ROW(attn_delta_kernel<float, DH>), ROW(attn_bwd_dkv_kernel<float, DH>), ROW(attn_bwd_dq_kernel<float, DH>), ROW(attn_fwd_kernel<float, DH>)
+enum {                     // first row of a family; dhi = 0 / 1 / 2 for dh 16 / 32 / 64
+    K_32 = 0,              // + 14 dhi + K32_*                             bf16, 32-row waves
+    K_MERGED4 = 42,        // + 2 nd + !causal                             bf16 dh = 64, 16-row waves
+    K_DQ4 = 46,            // + 2 nd + !(key split)
+    K_DKV4 = 50,           // + 2 nd + !causal
+    K_FWD4 = 54,           // + 2 nd + !(key split)
+    K_FWD5 = 58,           // + 2 nd + !(4 stages, 2 blocks per CU)        bf16 dh = 64, v5
+    K_F32 = 62,            // + 4 dhi + F32_*                              exact f32, first generation
+    K_XDKV = 74,           // + 2 nd + !(2 blocks per CU)                  bf16x3, dh = 64
+    K_XDQ = 78,            // + nd
+    K_XFWD = 80,           // + nd
+    K_COUNT = 82
+};
+enum { K32_DQ = 0 /* + 6 nd + !(4 blocks per CU) */, K32_DKV = 2 /* + 6 nd + 2 !(3 blocks per CU) + !causal */, K32_FWD = 12 /* + nd */ };
+enum { F32_DELTA, F32_DKV, F32_DQ, F32_FWD };
+const KernelRow KERNELS[] = {
+    ROWS_32(16), ROWS_32(32), ROWS_32(64),
+    ROWS_BB(attn4_bwd_merged_kernel), ROWS_KS(attn4_bwd_dq_kernel), ROWS_BB(attn4_bwd_dkv_kernel), ROWS_KS(attn4_fwd_kernel),
+    ROW(attn5_fwd_kernel<true, 4, 2>), ROW(attn5_fwd_kernel<true, 3, 3>), ROW(attn5_fwd_kernel<false, 4, 2>), ROW(attn5_fwd_kernel<false, 3, 3>),
+    ROWS_F32(16), ROWS_F32(32), ROWS_F32(64),
+    ROW(attnx_bwd_dkv_kernel<64, true, 2>), ROW(attnx_bwd_dkv_kernel<64, true, 1>), ROW(attnx_bwd_dkv_kernel<64, false, 2>), ROW(attnx_bwd_dkv_kernel<64, false, 1>),
+    ROW(attnx_bwd_dq_kernel<64, true>), ROW(attnx_bwd_dq_kernel<64, false>), ROW(attnx_fwd_kernel<64, true>), ROW(attnx_fwd_kernel<64, false>),
+};
+static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == K_COUNT, "one row per K_* index");
+#define SHM_F32(DH) {0, 2 * Smem<float, DH>::BUF_DKV, 2 * Smem<float, DH>::BUF_DQ, 2 * Smem<float, DH>::BUF_FWD}
+constexpr int SHM_F32_OF[3][4] = {SHM_F32(16), SHM_F32(32), SHM_F32(64)};        // [dhi][F32_*]
+constexpr int SHM_BF16_OF[3] = {BL<16>::SHM, BL<32>::SHM, BL<64>::SHM};
 
-template <typename T> int dispatch(const pa_attn_args* a, bool bwd, hipStream_t st) {
-    const AttnP p = make_params(a);
-    switch (a->dh) {
-        case 16: return bwd ? run_bwd<T, 16>(p, st) : run_fwd<T, 16>(p, st);
-        case 32: return bwd ? run_bwd<T, 32>(p, st) : run_fwd<T, 32>(p, st);
-        case 64: return bwd ? run_bwd<T, 64>(p, st) : run_fwd<T, 64>(p, st);
-        default: return PA_ESHAPE;
-    }
-}
+// ---- the plan ---------------------------------------------------------------------------------------------------------------------
+struct AttnLaunch { int kern; unsigned grid[3]; int block, lds, extra; };      // extra: the merged backward kernel's second argument
+struct AttnPlan {
+    int status = 0;        // 0, or the PA_E* code the call returns
+    AttnP p;               // the argument block of every launch of the call
+    int n = 0; AttnLaunch l[3];
+    bool x3 = false;       // the bf16x3 kernels run (pa_attn_split_taken counts the call)
+    void add(int kern, unsigned gx, unsigned gy, unsigned gz, int block, int lds, int extra = 0) { l[n++] = AttnLaunch{kern, {gx, gy, gz}, block, lds, extra}; }
+    void add(int kern, unsigned gx, int block, int lds, int extra = 0) { add(kern, gx, 1, 1, block, lds, extra); }
+};
 
 int check_args(const pa_attn_args* a, bool bwd) {
     if (!a || !a->q || !a->k || !a->v || !a->o || !a->lse) return PA_EINVAL;
@@ -2559,7 +2332,170 @@ int check_args(const pa_attn_args* a, bool bwd) {
         if (!a->dout || !a->dq || !a->dk || !a->dv || !a->delta) return PA_EINVAL;
         if (!al(a->dout, a->lddo) || !al(a->dq, a->lddq) || !al(a->dk, a->lddk) || !al(a->dv, a->lddv)) return PA_EALIGN;
     }
+    return a->dh == 16 || a->dh == 32 || a->dh == 64 ? 0 : PA_ESHAPE;
+}
+AttnP make_params(const pa_attn_args* a, const AttnSwitches& sw) {
+    AttnP p;
+    p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o; p.lse = a->lse; p.kpm = a->kpm;
+    p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk;
+    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
+    p.causal = a->causal; p.scale = a->scale;
+    p.drop_thr = (uint32_t)((double)a->drop_p * 4294967296.0);     // keep <=> 32-bit product >= thr (pa_device.h drop_keep2)
+    p.drop_scale = (float)(1.0 / (1.0 - (double)p.drop_thr / 4294967296.0));
+    p.drop_seed = a->drop_seed;
+    p.dout = a->dout; p.dq = a->dq; p.dk = a->dk; p.dv = a->dv; p.delta = a->delta;
+    p.lddo = a->lddo; p.lddq = a->lddq; p.lddk = a->lddk; p.lddv = a->lddv;
+    p.cu_q = a->cu_q; p.cu_k = a->cu_k; p.order = a->order;
+    p.ks_min = 4; p.parts_q = 1; p.parts_kv = 1;
+    p.balanced = (sw.balanced && a->order && a->cu_q && a->cu_k && a->H == 8 && a->B <= 64) ? 1 : 0;
+    // range blocks (balanced == 2, set by plan_attn for the kernels that know it): packed self-attention with scratch from the caller
+    p.sp_tick = nullptr; p.sp_part = nullptr; p.sp_slots = 0; p.sp_pmax = sw.split_pmax; p.sp_kmax = sw.split_kmax;
+    if (sw.split && p.balanced && a->ws && a->cu_q == a->cu_k && !a->kpm && !a->causal && a->dtype == PA_BF16 && a->dh == 64 &&
+        (reinterpret_cast<uintptr_t>(a->ws) & 255) == 0 && p.sp_pmax > 1) {
+        const int64_t per = (int64_t)p.sp_pmax * SP_BYTES + 64;          // one (owned tile, head): its range blocks' partials + ticket
+        const int64_t total = a->ws_bytes / per;
+        p.sp_slots = (int)(total / 8 < (1 << 20) ? total / 8 : (1 << 20));
+        p.sp_tick = static_cast<int*>(a->ws);
+        p.sp_part = static_cast<char*>(a->ws) + ((int64_t)p.sp_slots * 8 * 4 + 255) / 256 * 256;
+        if ((int64_t)p.sp_slots * 8 * per > a->ws_bytes || p.sp_slots < 1) { p.sp_slots = 0; p.sp_tick = nullptr; }
+    }
+    return p;
+}
+// blocks of a balanced == 2 launch: an upper bound of the units (the host does not know the elements' lengths; surplus blocks exit)
+unsigned split_grid(const AttnP& p, int owned_max, int streamed_max) {
+    const int ks = (streamed_max + BSTR - 1) / BSTR;
+    const int np = ks > p.sp_kmax ? std::min(p.sp_pmax, (ks + p.sp_kmax - 1) / p.sp_kmax) : 1;
+    return (unsigned)(8 * p.B * ((owned_max + BOWN - 1) / BOWN) * np);
+}
+// 16-row waves (v4, dh = 64) for launches that cannot fill the SIMDs with 32-row waves: variable-length (packed) batches and
+// launches with fewer than four 32-row waves per SIMD.  Measured (tools/attn_bench.py): packed self-attention forward 35.9 ->
+// 32.9 us, cross-attention forward / backward 28.9 -> 23.5 / 57.1 -> 52.9 us, but the dense padded S = 1024 launch (4 096
+// 32-row waves, VALU-bound) 67.9 -> 75.0 us - twice the LDS operand reads and barriers for no extra occupancy.
+bool use_v4(const AttnP& p, const AttnSwitches& sw, int rows_owned) {
+    if (sw.v4 == 0) return false;
+    if (sw.v4 >= 2) return true;
+    const long long waves32 = (long long)p.B * p.H * ((rows_owned + 31) / 32);
+    return p.cu_q != nullptr || p.cu_k != nullptr || waves32 < 4 * 1024;
+}
+// In-block key split of the 16-row-wave forward / dQ kernels (attn4_fwd_kernel): for launches whose duration is one block's
+// serial chain of key steps - few blocks, many keys.  Mode 1: at most one block per CU (cross-attention), every element with
+// >= ksplit_min key tiles; mode 2 also launches of more blocks than CUs (packed self-attention), there only the long elements,
+// whose chain of key steps sets the duration of the launch.  Never with a key-padding mask, causal, or under 4 key tiles.
+struct KeySplit { bool on; int ks_min; };        // ks_min: what AttnP gets (the kernels that do not split ignore it)
+KeySplit key_split(const AttnP& p, const AttnSwitches& sw, unsigned blocks) {
+    if (sw.ksplit == 0 || p.kpm || p.causal || p.Lk < 4 * BSTR) return {false, p.ks_min};
+    return {sw.ksplit >= 2 || blocks <= 256, blocks <= 256 ? sw.ksplit_min : sw.ksplit_min2};
+}
+// v5 forward (attention5.h): mode 1 self-attention-like launches (not causal, at least two 128-row query tiles per element)
+bool use_v5(const AttnP& p, const AttnSwitches& sw) { return sw.v5 != 0 && !p.causal && (sw.v5 >= 2 || p.Lq > BOWN); }
+
+// The selection rule.  Pure: no HIP call, no environment, no global; the operand pointers are compared and tested for alignment only.
+// x3_on: the bf16x3 mode of the caller's context (pa_attn_split_config) - f32 launches with dh = 64 then run attention_x3.h.
+AttnPlan plan_attn(const pa_attn_args* a, bool bwd, const AttnSwitches& sw, bool x3_on) {
+    AttnPlan pl;
+    pl.status = check_args(a, bwd);
+    if (pl.status) return pl;
+    AttnP& p = pl.p;
+    p = make_params(a, sw);
+    const int dhi = a->dh == 16 ? 0 : a->dh == 32 ? 1 : 2;
+    const int nd = p.drop_thr == 0, nc = p.causal == 0;                // (drop_thr, not drop_p: a p below 2^-32 drops nothing)
+    const int tq = (p.Lq + BOWN - 1) / BOWN, tk = (p.Lk + BOWN - 1) / BOWN;
+
+    if (a->dtype == PA_F32) {                                           // grids (tiles, H, B); backward: delta, dK/dV, dQ
+        pl.x3 = x3_on && a->dh == 64;
+        const int* shm = SHM_F32_OF[dhi];
+        constexpr int shx = X3L<64>::SHM;
+        if (!bwd) {
+            if (pl.x3) pl.add(K_XFWD + nd, tq, p.H, p.B, NTH, shx);
+            else pl.add(K_F32 + 4 * dhi + F32_FWD, tq, p.H, p.B, NTH, shm[F32_FWD]);
+            return pl;
+        }
+        if (pl.x3 && sw.x3_parts >= 2) {
+            if (p.Lk >= sw.x3_parts_min) p.parts_q = sw.x3_parts;
+            if (p.Lq >= sw.x3_parts_min && p.Lk <= p.Lq && (!p.cu_q || p.cu_q == p.cu_k)) p.parts_kv = sw.x3_parts;     // self-attention shapes only
+        }
+        pl.add(K_F32 + 4 * dhi + F32_DELTA, (unsigned)(((int64_t)p.B * p.H * p.Lq + 255) / 256), 256, 0);
+        if (pl.x3) {
+            pl.add(K_XDKV + 2 * nd + (sw.x3_dkv_occ == 1), tk * p.parts_kv, p.H, p.B, NTH, shx);
+            pl.add(K_XDQ + nd, tq * p.parts_q, p.H, p.B, NTH, shx);
+        } else {
+            pl.add(K_F32 + 4 * dhi + F32_DKV, tk, p.H, p.B, NTH, shm[F32_DKV]);
+            pl.add(K_F32 + 4 * dhi + F32_DQ, tq, p.H, p.B, NTH, shm[F32_DQ]);
+        }
+        return pl;
+    }
+
+    // bf16: 1-D grids; backward: dQ (which writes delta), then dK/dV.  dh 16 / 32 always run the 32-row-wave kernels.
+    const unsigned gq = tq * p.H * p.B, gk = tk * p.H * p.B;
+    const int shm = SHM_BF16_OF[dhi];
+    constexpr int shm2 = 4 * BL<64>::BUF + 64;                          // key split: two pairs of stages
+    const bool dh64 = a->dh == 64;
+    if (!bwd) {
+        if (dh64 && use_v5(p, sw)) {
+            unsigned g = gq;
+            if (p.balanced && p.sp_tick) { p.balanced = 2; g = split_grid(p, p.Lq, p.Lk); }
+            const bool occ2 = sw.v5_occ == 2;
+            pl.add(K_FWD5 + 2 * nd + !occ2, g, NTH, occ2 ? L5<4>::SHM : L5<3>::SHM);
+        } else if (dh64 && use_v4(p, sw, p.Lq)) {
+            const KeySplit ks = key_split(p, sw, gq);
+            p.ks_min = ks.ks_min;
+            pl.add(K_FWD4 + 2 * nd + !ks.on, gq, ks.on ? 2 * NT4 : NT4, ks.on ? shm2 : shm);
+        } else {
+            pl.add(K_32 + 14 * dhi + K32_FWD + nd, gq, NTH, shm);
+        }
+        return pl;
+    }
+    if (dh64 && use_v4(p, sw, std::max(p.Lq, p.Lk))) {
+        // single query tile per (sample, head): dQ and dK/dV blocks in one launch
+        if (sw.bwd_merge && p.Lq <= sw.bwd_merge_max && p.Lq <= 2048 && (gq & 7) == 0) {
+            pl.add(K_MERGED4 + 2 * nd + nc, gq + gk, NT4, shm + (p.Lq + 15) / 16 * 64 + 64, (int)gq);
+            return pl;
+        }
+        const KeySplit ks = key_split(p, sw, gq);
+        p.ks_min = ks.ks_min;
+        const bool ranges = p.balanced && p.sp_tick && !ks.on;
+        if (ranges) p.balanced = 2;
+        pl.add(K_DQ4 + 2 * nd + !ks.on, ranges ? split_grid(p, p.Lq, p.Lk) : gq, ks.on ? 2 * NT4 : NT4, ks.on ? shm2 : shm);
+        pl.add(K_DKV4 + 2 * nd + nc, ranges ? split_grid(p, p.Lk, p.Lq) : gk, NT4, shm);
+        return pl;
+    }
+    const int oq = sw.occ ? sw.occ / 10 : 3, ok = sw.occ ? sw.occ % 10 : 2;
+    pl.add(K_32 + 14 * dhi + K32_DQ + 6 * nd + (oq < 4), gq, NTH, shm);
+    pl.add(K_32 + 14 * dhi + K32_DKV + 6 * nd + 2 * (ok < 3) + nc, gk, NTH, shm);
+    return pl;
+}
+
+// bf16x3 attention (attention_x3.h) for f32 launches with dh = 64 while pa_attn_split_config(1) is in force
+extern "C" int pa_split_attn_set(int32_t on);       // gemm.hip: the flag lives in the current bf16x3 context (pa_split_ctx_*)
+extern "C" int pa_split_attn_active(void);
+std::atomic<long long> g_attn_x3_taken{0};
+std::atomic<int> g_lds_optin[K_COUNT];              // per kernel: 0 = not asked yet, else 1 + the answer of the > 64 KiB opt-in
+
+int launch_plan(const AttnPlan& pl, hipStream_t st) {
+    for (int i = 0; i < pl.n; ++i) {
+        const AttnLaunch& l = pl.l[i];
+        if (l.lds > 64 * 1024) {
+            int s = g_lds_optin[l.kern].load(std::memory_order_relaxed);
+            if (!s) {
+                s = 1 + (int)hipFuncSetAttribute(KERNELS[l.kern].fn, hipFuncAttributeMaxDynamicSharedMemorySize, l.lds);
+                g_lds_optin[l.kern].store(s, std::memory_order_relaxed);
+            }
+            if (s != 1) return s - 1;
+        }
+        AttnP p = pl.p;
+        int extra = l.extra;
+        void* args[] = {&p, &extra};                 // (only the merged backward kernel has the second parameter)
+        (void)hipGetLastError();
+        (void)hipLaunchKernel(KERNELS[l.kern].fn, dim3(l.grid[0], l.grid[1], l.grid[2]), dim3(l.block), args, (size_t)l.lds, st);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    if (pl.x3) g_attn_x3_taken.fetch_add(1);
     return 0;
+}
+int run_attn(const pa_attn_args* a, bool bwd, void* stream) {
+    const AttnPlan pl = plan_attn(a, bwd, attn_switches(), pa_split_attn_active() != 0);
+    return pl.status ? pl.status : launch_plan(pl, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -2572,29 +2508,36 @@ extern "C" int64_t pa_attn_split_taken(int32_t reset) {
 }
 
 extern "C" int64_t pa_attn_ws_bytes(int32_t rows_total, int32_t B, int32_t H, int32_t L_max) {
-    static const bool sp_env = getenv("PA_ATTN_SPLIT") && atoi(getenv("PA_ATTN_SPLIT")) != 0;     // opt-in: measured slower (profiles/r06_attention_launch_shape.txt)
-    if (!sp_env || split_pmax() < 2 || H != 8 || rows_total <= 0 || B <= 0 || B > 64) return 0;
-    if ((L_max + BSTR - 1) / BSTR <= split_kmax()) return 0;
+    const AttnSwitches& sw = attn_switches();
+    if (!sw.split || sw.split_pmax < 2 || H != 8 || rows_total <= 0 || B <= 0 || B > 64) return 0;
+    if ((L_max + BSTR - 1) / BSTR <= sw.split_kmax) return 0;
     const int64_t slots = (int64_t)(rows_total / BOWN + B);             // owned tiles of all elements, an upper bound
-    return slots * 8 * ((int64_t)split_pmax() * SP_BYTES + 64) + 256;
+    return slots * 8 * ((int64_t)sw.split_pmax * SP_BYTES + 64) + 256;
 }
 extern "C" int64_t pa_attn_ws_ticket_bytes(int64_t ws_bytes) {
-    const int64_t per = (int64_t)split_pmax() * SP_BYTES + 64;
+    const int64_t per = (int64_t)attn_switches().split_pmax * SP_BYTES + 64;
     return (ws_bytes / per / 8 * 8 * 4 + 255) / 256 * 256;
 }
 
-extern "C" int pa_attn_fwd(const pa_attn_args* a, void* stream) {
-    int rc = check_args(a, false);
-    if (rc) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return a->dtype == PA_BF16 ? dispatch<bf16>(a, false, st) : dispatch<float>(a, false, st);
-}
+extern "C" int pa_attn_fwd(const pa_attn_args* a, void* stream) { return run_attn(a, false, stream); }
+extern "C" int pa_attn_bwd(const pa_attn_args* a, void* stream) { return run_attn(a, true, stream); }
 
-extern "C" int pa_attn_bwd(const pa_attn_args* a, void* stream) {
-    int rc = check_args(a, true);
-    if (rc) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return a->dtype == PA_BF16 ? dispatch<bf16>(a, true, st) : dispatch<float>(a, true, st);
+// Dry run (include/plank_hip.h): what pa_attn_fwd / pa_attn_bwd would launch, from the same plan_attn.
+extern "C" int pa_attn_plan(const pa_attn_args* a, int32_t bwd, pa_attn_plan_info* out) {
+    if (!out) return PA_EINVAL;
+    *out = pa_attn_plan_info();
+    const AttnPlan pl = plan_attn(a, bwd != 0, attn_switches(), pa_split_attn_active() != 0);
+    if (pl.status) return pl.status;
+    out->n_launches = pl.n;
+    out->balanced = pl.p.balanced; out->ks_min = pl.p.ks_min; out->parts_q = pl.p.parts_q; out->parts_kv = pl.p.parts_kv;
+    out->sp_slots = pl.p.sp_slots;
+    for (int i = 0; i < pl.n; ++i) {
+        const AttnLaunch& l = pl.l[i];
+        snprintf(out->launch[i].kernel, sizeof(out->launch[i].kernel), "%s", KERNELS[l.kern].name);
+        for (int d = 0; d < 3; ++d) out->launch[i].grid[d] = l.grid[d];
+        out->launch[i].block = l.block; out->launch[i].lds_bytes = l.lds; out->launch[i].extra = l.extra;
+    }
+    return 0;
 }
 
 #ifdef PA_ATTN_TRACE

@@ -518,11 +518,14 @@ def _extract_keep_mask(B, H, Lq, Lk, dh, p, seed, dtype):
     return keep
 
 
-@pytest.mark.parametrize("dtype,B,H,dh,Lq,Lk,causal", [
+DROPOUT_CASES = [
     (torch.bfloat16, 2, 2, 64, 200, 333, False),      # the benchmarked head size, ragged multi-tile shapes
     (torch.bfloat16, 1, 2, 64, 130, 130, True),
     (torch.float32, 1, 2, 16, 70, 100, False),
-])
+]
+
+
+@pytest.mark.parametrize("dtype,B,H,dh,Lq,Lk,causal", DROPOUT_CASES)
 def test_attention_dropout_forward_backward_against_masked_reference(dtype, B, H, dh, Lq, Lk, causal):
     """Dropout is a deterministic function of (seed, query row, key): extract the mask the kernels use, then compare
     forward AND all three backward outputs with a torch reference that applies that same mask - this pins that the
@@ -689,9 +692,12 @@ def test_pack_rows_matches_nonzero():
     assert torch.equal(ops.pack_order(cu._base).cpu().long(), order)     # the whole [2B+1] buffer (what prepare_batch keeps)
 
 
+VARLEN_CASES = [(3, 4, 16, 70, 70, True), (4, 8, 64, 128, 300, False), (2, 8, 64, 260, 260, True),
+                (14, 8, 64, 450, 450, True), (5, 8, 64, 128, 1021, False), (3, 8, 64, 700, 700, True)]
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("B,H,dh,Lq,Lk,self_attn", [(3, 4, 16, 70, 70, True), (4, 8, 64, 128, 300, False), (2, 8, 64, 260, 260, True),
-                                                    (14, 8, 64, 450, 450, True), (5, 8, 64, 128, 1021, False), (3, 8, 64, 700, 700, True)])
+@pytest.mark.parametrize("B,H,dh,Lq,Lk,self_attn", VARLEN_CASES)
 def test_attention_varlen_matches_masked_dense(dtype, B, H, dh, Lq, Lk, self_attn):
     """Packed K/V (and Q for self-attention) without any mask == dense attention with a key-padding mask."""
     dm = H * dh
@@ -1076,12 +1082,15 @@ def test_gemm_ln_fused_equals_separate_launches(M, K, drop, res):
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # bf16x3 ("split") attention (csrc/attention_x3.h): the exact-f32 kernels' function with every product as hi*hi + hi*lo + lo*hi
-@pytest.mark.parametrize("B,H,Lq,Lk,use_kpm,causal,drop", [
+X3_CASES = [
     (2, 8, 128, 1199, True, False, 0.0),      # default cross-attention
     (1, 8, 300, 300, True, False, 0.2),       # self-attention, ragged tiles, dropout (the same decisions as exact f32)
     (2, 8, 128, 128, True, True, 0.2),        # default decoder self-attention
     (2, 4, 1024, 1024, True, False, 0.0),     # benchmark length
-])
+]
+
+
+@pytest.mark.parametrize("B,H,Lq,Lk,use_kpm,causal,drop", X3_CASES)
 def test_attention_x3_equals_exact_f32_to_split_precision(B, H, Lq, Lk, use_kpm, causal, drop):
     from plankassembly_amd import _lib as L
     dh, dm = 64, H * 64
@@ -1311,3 +1320,97 @@ def test_gemm_x3_retained_images_serve_the_weight_gradient():
     for g in (dw, dwg, dwg2):
         assert _x3_err(g, dy64.t(), x64) < 2.0 ** -15
     assert _x3_err(y2, 2.0 * x64, w64.t()) < 2.0 ** -15               # the hand-written image was what the GEMM multiplied
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The opt-in variants of the attention dispatch (csrc/attention.hip AttnSwitches) stay tested paths: the parametrised attention tests
+# above, with their shapes and tolerances, in child processes under bundles of switches that reach kernels the default setting does
+# not.  The switches are read once per process, hence the children (this file run as a script).
+ATTN_BUNDLE_TESTS = ["test_attention_fwd_bwd", "test_attention_dropout_forward_backward_against_masked_reference",
+                     "test_attention_varlen_matches_masked_dense", "test_attention_x3_equals_exact_f32_to_split_precision"]
+# per bundle: the environment, and per switched variant what some case's plan must show that the same case's default plan does not:
+# a kernel name (regular expression) or, where the kernels keep their names, a field of the plan
+ATTN_BUNDLES = {
+    "occupancies_unmerged_keysplit": (
+        {"PA_ATTN_V5_OCC": "2", "PA_ATTN_OCC": "43", "PA_X3_DKV_OCC": "2", "PA_ATTN_BWD_MERGE": "0", "PA_ATTN_KSPLIT": "2"},
+        {"PA_ATTN_V5_OCC": r"attn5_fwd_kernel<\w+, 4, 2>", "PA_ATTN_OCC dq": r"attn_bwd_dq_bf16_kernel<\d+, \w+, 4>",
+         "PA_ATTN_OCC dkv": r"attn_bwd_dkv_bf16_kernel<\d+, \w+, 3, \w+>", "PA_X3_DKV_OCC": r"attnx_bwd_dkv_kernel<64, \w+, 2>",
+         "PA_ATTN_BWD_MERGE": r"attn4_bwd_dkv_kernel<\w+, true>", "PA_ATTN_KSPLIT": r"attn4_bwd_dq_kernel<\w+, 2>"}),
+    "no_v5_x3_parts": (
+        {"PA_ATTN_V5": "0", "PA_X3_PARTS": "2", "PA_X3_PARTS_MIN": "128"},
+        {"PA_ATTN_V5": r"attn4_fwd_kernel<|attn_fwd_bf16_kernel<64", "PA_X3_PARTS": "parts_kv", "PA_X3_PARTS_MIN": "parts_q below 512 keys"}),
+}
+
+
+def _attn_bundle_plans():
+    """pa_attn_plan on the argument blocks of ATTN_BUNDLE_TESTS' cases (made-up aligned addresses: the dry run dereferences nothing),
+    forward and backward: [[Lk, [kernel names], parts_q, parts_kv], ...] under this process's switches."""
+    import ctypes as C
+    blocks = [(dt, B, H, dh, Lq, Lk, kpm, causal, 0.0, None, 0) for dt in (torch.float32, torch.bfloat16) for B, H, dh, Lq, Lk, kpm, causal in CASES]
+    blocks += [(dt, B, H, dh, Lq, Lk, False, causal, 0.2, None, 0) for dt, B, H, dh, Lq, Lk, causal in DROPOUT_CASES]
+    blocks += [(dt, B, H, dh, Lq, Lk, False, False, 0.0, lay, 0) for dt in (torch.float32, torch.bfloat16)
+               for B, H, dh, Lq, Lk, self_attn in VARLEN_CASES for lay in (["self", "self_order"] if self_attn else ["keys", "keys_order"])]
+    blocks += [(torch.float32, B, H, 64, Lq, Lk, kpm, causal, drop, None, 1) for B, H, Lq, Lk, kpm, causal, drop in X3_CASES]
+    rows = []
+    for dt, B, H, dh, Lq, Lk, kpm, causal, drop, lay, x3 in blocks:
+        a = L.AttnArgs()
+        for i, f in enumerate(("q", "k", "v", "o", "lse", "dout", "dq", "dk", "dv", "delta")):
+            setattr(a, f, 0x1000000 * (i + 1))
+        a.B, a.H, a.Lq, a.Lk, a.dh = B, H, Lq, Lk, dh
+        a.ldq = a.ldk = a.ldv = a.ldo = a.lddo = a.lddq = a.lddk = a.lddv = H * dh
+        a.causal, a.scale, a.drop_p, a.drop_seed, a.dtype = int(causal), dh ** -0.5, drop, 7, L.dt(torch.empty(0, dtype=dt))
+        if kpm:
+            a.kpm = 0x20000000
+        if lay:
+            a.cu_k = 0x30000000
+            if lay.startswith("self"):
+                a.cu_q = a.cu_k
+            if lay.endswith("order"):
+                a.order = 0x40000000
+        L.check(L.lib().pa_attn_split_config(x3), "pa_attn_split_config")
+        try:
+            for bwd in (0, 1):
+                info = L.AttnPlanInfo()
+                L.check(L.lib().pa_attn_plan(C.byref(a), bwd, C.byref(info)), "pa_attn_plan")
+                rows.append([Lk, [ln.kernel.decode() for ln in info.launch[:info.n_launches]], info.parts_q, info.parts_kv])
+        finally:
+            L.check(L.lib().pa_attn_split_config(0), "pa_attn_split_config")
+    return rows
+
+
+def _attn_bundle_child(bundle, default_rows):
+    """In the child, before anything runs on the device: every switched variant of the bundle shows in the plan of some case."""
+    import re
+    rows = _attn_bundle_plans()
+    assert len(rows) == len(default_rows)
+    for switch, want in ATTN_BUNDLES[bundle][1].items():
+        if want == "parts_kv":
+            hit = any(r[3] > 1 and d[3] == 1 for r, d in zip(rows, default_rows))
+        elif want == "parts_q below 512 keys":
+            hit = any(r[0] < 512 and r[2] > 1 and d[2] == 1 for r, d in zip(rows, default_rows))
+        else:
+            hit = any(any(re.match(want, n) for n in r[1]) and not any(re.match(want, n) for n in d[1]) for r, d in zip(rows, default_rows))
+        assert hit, f"bundle {bundle}: {switch} selects nothing the default setting does not"
+
+
+@pytest.mark.parametrize("bundle", sorted(ATTN_BUNDLES))
+def test_attention_switch_bundles_in_a_child_process(bundle, tmp_path):
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    default_file = tmp_path / "default_plans.json"
+    default_file.write_text(json.dumps(_attn_bundle_plans()))
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("PA_ATTN_", "PA_X3_"))}
+    env.update(ATTN_BUNDLES[bundle][0], PYTHONPATH=root + os.pathsep + env.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), bundle, str(default_file)], cwd=root, env=env, capture_output=True,
+                       text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "35 passed" in r.stdout, r.stdout[-2000:]
+
+
+if __name__ == "__main__":
+    import json
+    import sys
+    _attn_bundle_child(sys.argv[1], json.load(open(sys.argv[2])))
+    sys.exit(pytest.main(["-q", "-x", "-p", "no:cacheprovider", os.path.abspath(__file__), "-k", " or ".join(ATTN_BUNDLE_TESTS)]))
