@@ -732,6 +732,33 @@ int pa_decode_prefix_begin(pa_model* m, const int32_t* plen, const int64_t* ptok
                            void* stream);
 int pa_decode_prefix_set(pa_model* m, const int32_t* plen, const int64_t* ptok, const int64_t* patt, void* stream);
 int pa_decode_prefix_buffers(pa_model* m, void** prefix_score, void** prefix_lp);
+/* Plank grammar over the same step, in any mode: programs that are valid by construction.  A plank is six
+ * coordinate tokens x0 y0 z0 x1 y1 z1 (out_dof must be 6; PA_EINVAL otherwise) with n_val coordinate values 0 .. n_val - 1, and END
+ * closes the program at a plank boundary.  At step t = 6 k + c the written token of a FREE row must lie in a window that depends on t
+ * and on the row's own token at t - 3 alone:
+ *   c == 0 and k >= max_planks:  END only (max_planks is clamped to (Tmax - 1) / 6, the last boundary that leaves room for END);
+ *   c == 0 otherwise:            [0, n_val - 2], plus END when k >= min_planks;
+ *   c in 1 .. 2:                 [0, n_val - 2];
+ *   c in 3 .. 5:                 [min(tokens[t - 3], n_val - 2) + 1, n_val - 1] (the clamp keeps the window non-empty whatever the
+ *                                history: a greedy row steps on after its END, a forced prefix may put anything at t - 3).
+ * PAD is never allowed.  A vocab candidate k writes token k; a pointer candidate j < t writes the row's own token at j and is judged by
+ * it; a pointer j >= t is never allowed.  The p of every candidate stays what the unconstrained step computes (the 1e-6 pointer fill
+ * included) - the constraint only removes candidates from the selection: the greedy arg-max runs over the allowed candidates (first-max
+ * order; one with p = 0 still beats every disallowed one), the beam ranking and the sampler's candidate set are the allowed candidates
+ * with p > 0.  Scores are not renormalised: beam scores, sample scores and prefix scores stay the model's own log-likelihood.  Forced
+ * positions (pa_decode_prefix_*) are not filtered.  Should every allowed candidate have p == 0 in f32, beam rank 0 and the sampler write
+ * the window's lowest token (END for the END-only window) with log p = -inf; nothing is read out of bounds and no loop depends on it.
+ * The parameters travel as kernel arguments: a captured step depends on them (capture again after a change).  Host state only, no
+ * launch.  pa_decode_begin clears the constraint; pa_decode_step_pair returns PA_EINVAL with one set.
+ *   pa_decode_constraint_set: after pa_decode_begin; p == NULL clears.  PA_EINVAL for a decode that was not begun, min_planks < 0,
+ *     max_planks < max(min_planks, 1), n_val < 2 or n_val above the vocabulary. */
+typedef struct {
+    int32_t n_val;        /* coordinate values: min(END, PAD) */
+    int32_t min_planks;   /* END allowed from this plank boundary on */
+    int32_t max_planks;   /* END forced at this plank boundary */
+    int32_t pad_;
+} pa_constraint_params;
+int pa_decode_constraint_set(pa_model* m, const pa_constraint_params* p);
 /* Cross-attention of one decode step in absorbed ("multi-query") form (reference plankassembly/models.py:284-307, the
  * cross-attention of nn.TransformerDecoderLayer with K = W_k memory + b_k, V = W_v memory + b_v): per batch element and head
  * ctx[b][h][:] = sum_s softmax_s(qt[b][h] . mem[s]) mem[s] over the element's memory rows, where the caller has put

@@ -215,6 +215,7 @@ def lib():
             "pa_decode_prefix_begin": (I, [P, P, P, P, P, I64, P]),
             "pa_decode_prefix_set": (I, [P, P, P, P, P]),
             "pa_decode_prefix_buffers": (I, [P, P, P]),
+            "pa_decode_constraint_set": (I, [P, P]),
             "pa_dec_cross_mq": (I, [P, P, P, P, P, I, I, I, I, P]),
             "pa_dec_cross_mq32": (I, [P, P, P, P, P, I, I, I, I, P]),
             "pa_dec_cross_mq_ws": (I, [P, P, P, P, P, I, I, I, I, P, I64, P]),
@@ -232,6 +233,11 @@ class SampleParams(C.Structure):
     """include/plank_hip.h pa_sample_params."""
     _fields_ = [("seed", C.c_uint32), ("n_per_drawing", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32),
                 ("top_p", C.c_float)]
+
+
+class ConstraintParams(C.Structure):
+    """include/plank_hip.h pa_constraint_params."""
+    _fields_ = [("n_val", C.c_int32), ("min_planks", C.c_int32), ("max_planks", C.c_int32), ("pad_", C.c_int32)]
 
 
 def check(rc: int, what: str):

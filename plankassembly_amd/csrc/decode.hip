@@ -79,6 +79,9 @@ struct DecodeLayout {
     bool px_on = false;
     int32_t *px_len = nullptr, *px_tok = nullptr, *px_att = nullptr;   // [rows], [rows][Tmax], [rows][Tmax]
     float *px_score = nullptr, *px_lp = nullptr;                      // [rows], [rows][Tmax]
+    // plank grammar (pa_decode_constraint_set; any mode): the caller's parameters, handed to the end-of-step kernels by value
+    bool cs_on = false;
+    pa_constraint_params cs{};
 };
 
 namespace {
@@ -401,16 +404,53 @@ __device__ __forceinline__ float dist_p_ptr(const RowDist& r, const float* plog,
     return val;
 }
 
+// Plank grammar: a plank is six coordinate tokens x0 y0 z0 x1 y1 z1 with max > min per axis, END stands at a
+// plank boundary only.  At step t = 6 k + c the written token of a free row must lie in a window that depends on t and on the row's own
+// token at t - 3 alone: tokens [lo, hi] (lo > hi: none), plus END when `end`.  The clamp of the c >= 3 window keeps it non-empty whatever
+// stands at t - 3 (a greedy row steps on after its END, a forced prefix may put anything there).  Passed by value: a captured step
+// depends on the parameters (max_planks arrives clamped to the last boundary that leaves room for END, (Tmax - 1) / 6).
+struct ConstraintDev { int32_t on, n_val, end_tok, min_planks, max_planks; };
+struct Window { int lo, hi, end; };
+__device__ __forceinline__ Window plank_window(const ConstraintDev& cs, const int64_t* row, int t) {
+    const int c = t % 6, k = t / 6;
+    if (c == 0) return k >= cs.max_planks ? Window{1, 0, 1} : Window{0, cs.n_val - 2, k >= cs.min_planks ? 1 : 0};
+    if (c < 3) return Window{0, cs.n_val - 2, 0};
+    const int64_t prev = row[t - 3];
+    return Window{(int)max(min(prev, (int64_t)(cs.n_val - 2)), (int64_t)-1) + 1, cs.n_val - 1, 0};
+}
+// The allowed-predicate of row `row` at step t, by candidate index: vocab entry k writes token k; pointer j < t writes the row's own
+// token at j and is judged by it; a pointer j >= t is never allowed.  Off: everything is allowed and nothing is read.  Every thread of
+// the block builds its own copy (one broadcast load of row[t - 3]).
+struct Allow {
+    Window w; int end_tok, V, t; const int64_t* row; bool on;
+    __device__ __forceinline__ bool token(int64_t k) const { return (k >= w.lo && k <= w.hi) || (w.end && k == end_tok); }
+    __device__ __forceinline__ bool operator()(int idx) const {
+        if (!on) return true;
+        if (idx < V) return token(idx);
+        const int j = idx - V;
+        return j < t && token(row[j]);
+    }
+    // an allowed vocab entry, for the step at which every allowed candidate has p = 0 in f32: the lowest of the window, else END
+    __device__ __forceinline__ int fallback() const { return w.lo <= w.hi ? w.lo : end_tok; }
+};
+__device__ __forceinline__ Allow make_allow(const ConstraintDev& cs, const int64_t* row, int V, int t) {
+    if (!cs.on) return Allow{Window{0, -1, 0}, 0, V, t, row, false};
+    return Allow{plank_window(cs, row, t), cs.end_tok, V, t, row, true};
+}
+
+// f(p, index, ok): ok = the candidate is allowed under the row's constraint (always true without one); p is the same either way - the
+// constraint only removes candidates from a caller's SELECTION.
 template <typename F>
-__device__ __forceinline__ void row_dist_visit(const RowDist& r, const float* vr, int V, const float* plog, int t, int jend, F&& f) {
+__device__ __forceinline__ void row_dist_visit(const RowDist& r, const float* vr, int V, const float* plog, int t, int jend,
+                                               const Allow& al, F&& f) {
     const int tid = threadIdx.x, sz = t + 1, i = t;
     if (sz < 6) {                                                     // models.py:172-173: un-gated vocab softmax
-        for (int k = tid; k < V; k += 256) f(dist_p_vocab(r, vr, k), k);
+        for (int k = tid; k < V; k += 256) f(dist_p_vocab(r, vr, k), k, al(k));
         return;
     }
     const float gate_v = 1.0f - r.prob;
-    for (int k = tid; k < V; k += 256) f(dist_p_vocab(r, vr, k) * gate_v, k);
-    for (int j = tid; j < jend; j += 256) f(dist_p_ptr(r, plog, i, j), V + j);
+    for (int k = tid; k < V; k += 256) f(dist_p_vocab(r, vr, k) * gate_v, k, al(k));
+    for (int j = tid; j < jend; j += 256) f(dist_p_ptr(r, plog, i, j), V + j, al(V + j));
 }
 
 // The p row_dist_visit hands out for the single index idx (vocab k as k, pointer j as V + j).  An index that is no candidate at step
@@ -455,7 +495,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int ldv, const T* pfeat, const T* h, T* hid_cache,
                                                          const float* sw_w, const float* sw_b, int64_t* tokens,
                                                          int64_t* attach, int32_t* first_end, int32_t* t_dev,
-                                                         int Tmax, int d, int V, int end_tok, const PrefixDev px) {
+                                                         int Tmax, int d, int V, int end_tok, const PrefixDev px,
+                                                         const ConstraintDev cs) {
     __shared__ float plog[MAX_T];
     __shared__ float sh[4];
     __shared__ ArgMax sha[4];
@@ -482,10 +523,14 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(const float* vlog, int 
         }
         return;
     }
+    // (constrained, section 15: the arg-max runs over the allowed candidates only - one with p = 0 still beats every disallowed one,
+    // and the window always holds a vocab entry, so best.i is a candidate)
+    const Allow al = make_allow(cs, tokens + (int64_t)b * Tmax, V, t);
     ArgMax best{-INFINITY, 0x7fffffff};
-    row_dist_visit(rd, vr, V, plog, t, sz, [&](float p, int k) { best = better(best, ArgMax{p, k}); });
+    row_dist_visit(rd, vr, V, plog, t, sz, al, [&](float p, int k, bool ok) { if (ok) best = better(best, ArgMax{p, k}); });
     best = block_argmax(best, sha);
     if (tid == 0) {
+        if (al.on && best.i == 0x7fffffff) best.i = al.fallback();  // (every allowed p is NaN: still an allowed token)
         const TokAtt c = candidate_token(best.i, V, tokens + (int64_t)b * Tmax);
         tokens[(int64_t)b * Tmax + t] = c.tok;
         attach[(int64_t)b * Tmax + t] = c.att;
@@ -508,7 +553,7 @@ __global__ __launch_bounds__(256) void dec_beam_cand_kernel(const float* vlog, i
                                                             const float* sw_w, const float* sw_b, const int64_t* tokens,
                                                             const int32_t* finished, const int32_t* t_dev, int Tmax, int d, int V,
                                                             int K, int pad_tok, float* cand_lp, int32_t* cand_tok, int32_t* cand_att,
-                                                            const PrefixDev px) {
+                                                            const PrefixDev px, const ConstraintDev cs) {
     __shared__ float plog[MAX_T];
     __shared__ float sh[4];
     __shared__ ArgMax sha[4];
@@ -536,16 +581,18 @@ __global__ __launch_bounds__(256) void dec_beam_cand_kernel(const float* vlog, i
         } else if (tid < K) { lp[tid] = -INFINITY; ct[tid] = pad_tok; ca[tid] = -1; }
         return;
     }
+    const Allow al = make_allow(cs, tokens + (int64_t)b * Tmax, V, t);   // (section 15: the ranking runs over the allowed candidates only)
     ArgMax prev{INFINITY, -1};
     for (int k = 0; k < K; ++k) {
         ArgMax best{-INFINITY, 0x7fffffff};
-        row_dist_visit(rd, vr, V, plog, t, t, [&](float p, int idx) {       // (jend = t: the self pointer is no candidate)
-            if (p > 0.f && (p < prev.v || (p == prev.v && idx > prev.i))) best = better(best, ArgMax{p, idx});
+        row_dist_visit(rd, vr, V, plog, t, t, al, [&](float p, int idx, bool ok) {      // (jend = t: the self pointer is no candidate)
+            if (ok && p > 0.f && (p < prev.v || (p == prev.v && idx > prev.i))) best = better(best, ArgMax{p, idx});
         });
         best = block_argmax(best, sha);
         __syncthreads();                                            // (sha is rewritten by the next round)
         if (tid == 0) {
-            if (best.i == 0x7fffffff) { lp[k] = -INFINITY; ct[k] = pad_tok; ca[k] = -1; }
+            // no candidate left: (-inf, PAD, -1) - constrained, rank 0 of a row without any candidate of p > 0 carries an allowed token
+            if (best.i == 0x7fffffff) { lp[k] = -INFINITY; ct[k] = (al.on && k == 0) ? al.fallback() : pad_tok; ca[k] = -1; }
             else {
                 const TokAtt c = candidate_token(best.i, V, tokens + (int64_t)b * Tmax);
                 lp[k] = logf(best.v); ct[k] = (int32_t)c.tok; ca[k] = (int32_t)c.att;
@@ -690,7 +737,7 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const float* vlog,
                                                               const float* sw_w, const float* sw_b, int64_t* tokens, int64_t* attach,
                                                               int32_t* first_end, const int32_t* t_dev, int Tmax, int d, int V,
                                                               int end_tok, int pad_tok, const SampleParamsDev* prm, float* scores,
-                                                              const PrefixDev px) {
+                                                              const PrefixDev px, const ConstraintDev cs) {
     __shared__ float plog[MAX_T];
     __shared__ float sp[SAMPLE_MAX_C], sw[SAMPLE_MAX_C];           // p and w of candidate i
     __shared__ float sh[4], scan[4];
@@ -721,8 +768,11 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const float* vlog,
         return;
     }
     const int nc = t + 1 < 6 ? V : V + t;                           // candidates: vocab, then the pointers j < t
+    // (section 15: a disallowed candidate is staged with p = 0, i.e. as no candidate - the allowed ones with p > 0 are the candidate set
+    // of everything below, and the chosen one's sp is its own unfiltered p)
+    const Allow al = make_allow(cs, tokens + (int64_t)r * Tmax, V, t);
     float pmax = -INFINITY;
-    row_dist_visit(rd, vr, V, plog, t, t, [&](float p, int i) { sp[i] = p; pmax = fmaxf(pmax, p); });
+    row_dist_visit(rd, vr, V, plog, t, t, al, [&](float p, int i, bool ok) { p = ok ? p : 0.f; sp[i] = p; pmax = fmaxf(pmax, p); });
     pmax = block_max(pmax, sh);                                     // (its barriers also publish sp)
     const float tau = P.temperature, lpmax = logf(pmax);
     for (int i = tid; i < nc; i += 256) {
@@ -833,7 +883,8 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const float* vlog,
     pick = block_min_i(pick, shi);
     if (pick == 0x7fffffff) pick = -block_min_i(-last, shi);       // rounding left no crossing: the last kept candidate
     if (tid == 0) {
-        const int idx = pick < 0 ? 0 : pick;                        // (the top candidate always has w = 1: pick >= 0)
+        // (the top candidate always has w = 1: pick >= 0 - unless no candidate has p > 0; constrained, that step writes an allowed token)
+        const int idx = pick < 0 ? (al.on ? al.fallback() : 0) : pick;
         const TokAtt c = candidate_token(idx, V, tokens + (int64_t)r * Tmax);
         tokens[(int64_t)r * Tmax + t] = c.tok;
         attach[(int64_t)r * Tmax + t] = c.att;
@@ -1109,6 +1160,13 @@ PrefixDev prefix_arg(const pa_model* m) {
     return PrefixDev{L->px_len, L->px_tok, L->px_att, L->px_score, L->px_lp, m->cfg.pad, 0};
 }
 
+// The constraint as the end-of-step kernels take it (none: off, and the kernels select among every candidate as without this argument).
+ConstraintDev constraint_arg(const pa_model* m) {
+    const DecodeLayout* L = m->dec;
+    if (!L->cs_on) return ConstraintDev{0, 0, 0, 0, 0};
+    return ConstraintDev{1, L->cs.n_val, m->cfg.end, L->cs.min_planks, std::min(L->cs.max_planks, (L->Tmax - 1) / 6)};
+}
+
 // The end of a greedy step: arg-max (or the forced candidate) per row.
 template <typename T>
 int greedy_tail(pa_model* m, int ldv, hipStream_t s) {
@@ -1117,7 +1175,7 @@ int greedy_tail(pa_model* m, int ldv, hipStream_t s) {
     const int tl = m->tail();
     PA_LAUNCH(dec_sample_kernel<T>, dim3(L->B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h, (T*)L->hid_cache,
               (const float*)m->pf[tl + T_SW_W], (const float*)m->pf[tl + T_SW_B], L->tokens, L->attach, L->first_end, L->t_dev, L->Tmax,
-              c.d_model, c.vocab, c.end, prefix_arg(m));
+              c.d_model, c.vocab, c.end, prefix_arg(m), constraint_arg(m));
     return 0;
 }
 
@@ -1130,7 +1188,7 @@ int beam_tail(pa_model* m, int ldv, hipStream_t s) {
     const int rows = L->B, K = L->beamK, tl = m->tail();
     PA_LAUNCH(dec_beam_cand_kernel<T>, dim3(rows), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h, (T*)L->hid_cache,
               (const float*)m->pf[tl + T_SW_W], (const float*)m->pf[tl + T_SW_B], L->tokens, L->bm_fin, L->t_dev, L->Tmax, c.d_model, c.vocab,
-              K, c.pad, L->bm_clp, L->bm_ctok, L->bm_catt, prefix_arg(m));
+              K, c.pad, L->bm_clp, L->bm_ctok, L->bm_catt, prefix_arg(m), constraint_arg(m));
     PA_LAUNCH(dec_beam_merge_kernel, dim3(rows / K), dim3(256), 0, s, L->bm_clp, L->bm_ctok, L->bm_catt, L->bm_score, L->bm_fin,
               L->first_end, L->bm_parent, L->tokens, L->attach, L->t_dev, L->Tmax, K, c.end);
     if (K > 1) {
@@ -1150,7 +1208,8 @@ int sample_tail(pa_model* m, int ldv, hipStream_t s) {
     const int tl = m->tail();
     PA_LAUNCH(dec_sample_draw_kernel<T>, dim3(L->B), dim3(256), 0, s, L->vlog, ldv, (const T*)L->pfeat, (const T*)L->h, (T*)L->hid_cache,
               (const float*)m->pf[tl + T_SW_W], (const float*)m->pf[tl + T_SW_B], L->tokens, L->attach, L->first_end, L->t_dev, L->Tmax,
-              c.d_model, c.vocab, c.end, c.pad, (const SampleParamsDev*)L->sm_prm, L->sm_score, prefix_arg(m));
+              c.d_model, c.vocab, c.end, c.pad, (const SampleParamsDev*)L->sm_prm, L->sm_score, prefix_arg(m),
+              constraint_arg(m));
     return 0;
 }
 
@@ -1438,6 +1497,7 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
     L->mq_contract = sf.mq_contract; L->mq_self = sf.mq_self; L->mq_self_bf = sf.mq_self_bf;   // (step_form)
     L->beamK = 0; L->sampleN = 0;                               // greedy until pa_decode_beam_begin / pa_decode_sample_begin
     L->px_on = false;                                           // and no forced prefix until pa_decode_prefix_begin
+    L->cs_on = false;                                           // and no constraint until pa_decode_constraint_set
     if (L->mq) {
         // absorbed cross-attention: the step reads the encoder output rows themselves - no K / V projection of the memory at all
         HIP_RC(hipMemcpyAsync(L->mem, memory, (size_t)m->NE * d * e, hipMemcpyDeviceToDevice, s));
@@ -1525,6 +1585,7 @@ extern "C" int pa_decode_step_pair(pa_model* a, pa_model* b, void* stream_a, voi
     if (a->dec->beamK > 0 || b->dec->beamK > 0) return PA_EINVAL;     // beams run as one lane
     if (a->dec->sampleN > 0 || b->dec->sampleN > 0) return PA_EINVAL; // so does sampling
     if (a->dec->px_on || b->dec->px_on) return PA_EINVAL;             // and a decode with a forced prefix
+    if (a->dec->cs_on || b->dec->cs_on) return PA_EINVAL;             // or a constraint
     const int n = 2 * a->cfg.n_dec;
     std::vector<hipEvent_t>& ev = a->dec->pair_ev;
     if ((int)ev.size() != 2 * n) {
@@ -1718,5 +1779,17 @@ extern "C" int pa_decode_prefix_set(pa_model* m, const int32_t* plen, const int6
 extern "C" int pa_decode_prefix_buffers(pa_model* m, void** prefix_score, void** prefix_lp) {
     if (!m || !m->dec || !m->dec->px_on || !prefix_score || !prefix_lp) return PA_EINVAL;
     *prefix_score = m->dec->px_score; *prefix_lp = m->dec->px_lp;
+    return 0;
+}
+
+// Plank grammar over a begun decode, in any mode (include/plank_hip.h).  Host state only: the parameters reach the
+// end-of-step kernels as arguments of the next pa_decode_step.
+extern "C" int pa_decode_constraint_set(pa_model* m, const pa_constraint_params* p) {
+    if (!m || !m->dec || m->dec->B <= 0) return PA_EINVAL;
+    DecodeLayout* L = m->dec;
+    if (!p) { L->cs_on = false; return 0; }
+    if (p->min_planks < 0 || p->max_planks < std::max(p->min_planks, 1) || p->n_val < 2) return PA_EINVAL;
+    if (p->n_val > m->cfg.vocab || m->cfg.out_dof != 6) return PA_EINVAL;      // (the window's tokens are vocab entries; planks of six)
+    L->cs = *p; L->cs_on = true;
     return 0;
 }

@@ -11,6 +11,7 @@ their kernels overlap for only 6.6 % of the busy time), so ``lanes=2`` stays as 
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -159,6 +160,44 @@ def prefix_table(prefix, B, Tmax, vocab_size, end_token, pad_token, strict=True)
     return lengths, ptok, patt
 
 
+PlankGrammar = collections.namedtuple("PlankGrammar", "min_planks max_planks")
+_NO_MAX = 2 ** 31 - 1                                  # max_planks None: the library clamps to the decode's last plank boundary
+
+
+def plank_grammar(min_planks=1, max_planks=None):
+    """Checked parameters of the plank grammar (include/plank_hip.h pa_decode_constraint_set): END is allowed
+    from plank boundary ``min_planks`` on and forced at boundary ``max_planks`` (None: the last boundary that leaves room for END,
+    (Tmax - 1) // 6, to which a larger value is clamped).  ValueError for what the library would refuse: a value that is no integer,
+    min_planks < 0, max_planks < max(min_planks, 1)."""
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+    if not is_int(min_planks) or not 0 <= min_planks < _NO_MAX:
+        raise ValueError(f"MIN_PLANKS must be an integer >= 0, got {min_planks!r}")
+    if max_planks is not None and (not is_int(max_planks) or not max(min_planks, 1) <= max_planks <= _NO_MAX):
+        raise ValueError(f"MAX_PLANKS must be an integer >= max(MIN_PLANKS, 1) = {max(min_planks, 1)} (or None), got {max_planks!r}")
+    return PlankGrammar(min_planks, max_planks)
+
+
+def check_planks(tokens, end, n_val, min_planks=1):
+    """Is every row a valid plank program up to its first END?  ``tokens`` int [B, n]; returns bool [B] (CPU).
+    Valid: the row has an END, at a plank boundary (position 6 k) with k >= ``min_planks``; every position before it holds a
+    coordinate value in [0, ``n_val``) - so no PAD - and each plank x0 y0 z0 x1 y1 z1 has max > min on every axis."""
+    tok = torch.as_tensor(tokens).detach().cpu().long()
+    B, n = tok.shape
+    is_end = tok == end
+    has_end = is_end.any(1)
+    e = torch.where(has_end, is_end.long().argmax(1), torch.zeros(B, dtype=torch.long))
+    ok = has_end & (e % 6 == 0) & (e // 6 >= min_planks)
+    pos = torch.arange(n)[None, :]
+    inside = pos < e[:, None]
+    bad = inside & ((tok < 0) | (tok >= n_val))
+    if n > 3:
+        lo = torch.zeros_like(tok)
+        lo[:, 3:] = tok[:, :-3]
+        bad |= inside & (pos % 6 >= 3) & (tok <= lo)
+    return ok & ~bad.any(1)
+
+
 class GreedyDecoder:
     _repeat = None                                     # rows per drawing (BeamDecoder: K, SampleDecoder: N; None: the batch as given)
 
@@ -183,7 +222,7 @@ class GreedyDecoder:
         self._side = None
         self._active = 0
         self.last_steps = 0
-        self._key = {"lanes": None, "mode": None, "prefix": None}     # what the captured step depends on (_rekey)
+        self._key = {"lanes": None, "mode": None, "prefix": None, "constraint": None}   # what the captured step depends on (_rekey)
         self._mws = _Arena()                               # the mode's workspace (beam / sampling)
         self._pws = _Arena()                               # prefix workspace (pa_decode_prefix_begin)
         self._pkeep = None
@@ -203,7 +242,8 @@ class GreedyDecoder:
         return self._lanes[i]
 
     def _rekey(self, **parts):
-        """The one place a captured step is dropped: when a part of what it captured - ``lanes``, ``mode``, ``prefix`` - changed."""
+        """The one place a captured step is dropped: when a part of what it captured - ``lanes``, ``mode``, ``prefix``,
+        ``constraint`` - changed."""
         key = {**self._key, **parts}
         if key != self._key:
             self._graph = None
@@ -317,6 +357,33 @@ class GreedyDecoder:
         score, lp = _buffers("pa_decode_prefix_buffers", ln.h(), 2)
         return self._pws.view(score, rows * 4, torch.float32, (rows,)), self._pws.view(lp, rows * Tmax * 4, torch.float32, (rows, Tmax))
 
+    def _check_constraint(self, constraint):
+        """The checked grammar of ``constraint`` (a plank_grammar() result; True: the default grammar), before anything is launched;
+        None for None / False."""
+        if constraint is None or constraint is False:
+            return None
+        if constraint is True:
+            constraint = plank_grammar()
+        if not isinstance(constraint, PlankGrammar):
+            raise ValueError(f"constraint must come from decode.plank_grammar(), got {constraint!r}")
+        constraint = plank_grammar(*constraint)
+        if self.max_lanes >= 2:
+            raise ValueError("a constraint needs the one-lane decode (lanes=1)")
+        if getattr(self.model, "num_output_dof", 6) != 6:
+            raise ValueError("the plank grammar is defined for six output DOF")
+        return constraint
+
+    def _constraint_begin(self, grammar):
+        """pa_decode_constraint_set on the begun decode (``grammar`` None: nothing - pa_decode_begin cleared it).  The parameters are
+        kernel arguments of the step: a captured step is dropped when they change, and replayed when they are the same."""
+        if grammar is None:
+            self._rekey(constraint=None)
+            return
+        tk = self.model.token
+        p = L.ConstraintParams(min(tk.END, tk.PAD), grammar.min_planks, _NO_MAX if grammar.max_planks is None else grammar.max_planks, 0)
+        L.check(L.lib().pa_decode_constraint_set(self._lanes[0].h(), C.byref(p)), "pa_decode_constraint_set")
+        self._rekey(constraint=(p.n_val, p.min_planks, p.max_planks))
+
     def _loop(self, Tmax, early_stop, all_done, min_steps=0, max_steps=None):
         """The stepping loop of every mode: ``max_steps`` steps exactly, or up to Tmax with - ``early_stop`` - one look at the device
         (``all_done()``: has every row finished) after every ``check_every`` replays once ``min_steps`` have run; that look is the
@@ -335,7 +402,7 @@ class GreedyDecoder:
         self.last_steps = done
         return done
 
-    def run(self, batch, max_len=None, early_stop=True, prefix=None, max_steps=None, strict_prefix=True):
+    def run(self, batch, max_len=None, early_stop=True, prefix=None, max_steps=None, strict_prefix=True, constraint=None):
         """Full greedy decode.  Returns (samples int64 [B, n], attach int64 [B, n]) with the
         reference's early-stop length n.
 
@@ -344,10 +411,15 @@ class GreedyDecoder:
         first END) and ``last_prefix_logprobs`` f32 [B, n] (per position, 0 where nothing was forced) are left on the decoder as CPU
         tensors (None after a run without a prefix).  The loop never stops before max(lengths) steps and n is at least that.
         ``max_steps``: run exactly this many steps (n = max_steps; the scorer).  ``strict_prefix=False``: prefix_table's
-        non-strict checks (the scorer)."""
+        non-strict checks (the scorer).
+
+        ``constraint`` (plank_grammar()): the arg-max of every free step runs over the candidates the plank
+        grammar allows, so every row is a valid program up to its first END.  Forced positions are not filtered."""
         table = self._check_prefix(prefix, batch, max_len, strict_prefix)
+        grammar = self._check_constraint(constraint)
         B, Tmax = self.begin(batch, max_len)
         pbuf = self._prefix_begin(table, 1, B, Tmax)
+        self._constraint_begin(grammar)
         bufs = [self._lanes[i].buffers(hi - lo, Tmax) for i, (lo, hi) in enumerate(self._bounds)]
         min_steps = int(table[0].max()) if table is not None and B > 0 else 0
         ends = None                                                   # every row's first END, once the host has seen them all
@@ -413,7 +485,7 @@ class BeamDecoder(GreedyDecoder):
         return [self._mws.view(p, rows * 4, dt, (rows,))
                 for p, dt in zip(_buffers("pa_decode_beam_buffers", self._lanes[0].h(), 3), (torch.float32, torch.int32, torch.int32))]
 
-    def run(self, batch, max_len=None, early_stop=True, prefix=None):
+    def run(self, batch, max_len=None, early_stop=True, prefix=None, constraint=None):
         """Full beam search.  Returns a dict: ``tokens`` / ``attach`` int64 [B, n] (the best beam), ``beam_tokens`` /
         ``beam_attach`` int64 [B, K, n], ``scores`` f32 [B, K] (cumulative log-probability), ``finished`` bool [B, K] and
         ``lengths`` int64 [B, K], beams in final-ranking order.  n = max over rows of first END + 1 once every beam has
@@ -422,11 +494,16 @@ class BeamDecoder(GreedyDecoder):
         ``prefix`` (prefix_table, per drawing; DESIGN.md section 14): the first ``lengths`` positions of every drawing are forced;
         beam 0 carries the hypothesis through them and the first free step fans out.  The dict always has ``prefix_scores`` f32
         [B, K] and ``prefix_logprobs`` f32 [B, K, n] - the log-probabilities of the forced positions, which every beam of a drawing
-        shares; zeros without a prefix.  ``scores`` stay the log-likelihood of the whole sequence."""
+        shares; zeros without a prefix.  ``scores`` stay the log-likelihood of the whole sequence.
+
+        ``constraint`` (plank_grammar()): the per-row top-K of every free step is taken among the candidates
+        the plank grammar allows; ``scores`` are not renormalised."""
         K = self.beam_size
         table = self._check_prefix(prefix, batch, max_len)
+        grammar = self._check_constraint(constraint)
         rows, Tmax = self.begin(batch, max_len)
         pbuf = self._prefix_begin(table, K, rows, Tmax)
+        self._constraint_begin(grammar)
         B = rows // K
         tokens, attach, first_end = self._lanes[0].buffers(rows, Tmax)
         scores, _, finished = self._beam_buffers(rows)
@@ -508,7 +585,7 @@ class SampleDecoder(GreedyDecoder):
     def _scores(self, rows):
         return self._mws.view(_buffers("pa_decode_sample_buffers", self._lanes[0].h(), 1)[0], rows * 4, torch.float32, (rows,))
 
-    def run(self, batch, max_len=None, early_stop=True, seed=None, prefix=None):
+    def run(self, batch, max_len=None, early_stop=True, seed=None, prefix=None, constraint=None):
         """N samples per drawing.  ``seed``: this call's seed instead of the decoder's (pa_decode_sample_set: the captured step is
         reused).  Returns a dict: ``tokens`` / ``attach`` int64 [B, n] (the best sample), ``sample_tokens`` / ``sample_attach``
         int64 [B, N, n], ``scores`` f32 [B, N] (log-likelihood of each sample), ``finished`` bool [B, N] and ``lengths`` int64
@@ -518,11 +595,16 @@ class SampleDecoder(GreedyDecoder):
         ``prefix`` (prefix_table, per drawing): the first ``lengths`` positions of every sample of a drawing
         are forced (no draw; the random numbers of the free steps are those of a run without a prefix).  The dict always has
         ``prefix_scores`` f32 [B, N] and ``prefix_logprobs`` f32 [B, N, n], zeros without a prefix; ``scores`` stay the
-        log-likelihood of the whole sample."""
+        log-likelihood of the whole sample.
+
+        ``constraint`` (plank_grammar()): the candidate set of every free step is what the plank grammar
+        allows; temperature, top-k, top-p and the draw act on that set, u is unchanged and ``scores`` are not renormalised."""
         N = self.num_samples
         table = self._check_prefix(prefix, batch, max_len)
+        grammar = self._check_constraint(constraint)
         rows, Tmax = self.begin(batch, max_len)
         pbuf = self._prefix_begin(table, N, rows, Tmax)
+        self._constraint_begin(grammar)
         if seed is not None:
             p = self.params
             q = sample_params(N, p.temperature, p.top_k, p.top_p, seed)

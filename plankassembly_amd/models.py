@@ -136,7 +136,7 @@ class PlankModel(nn.Module):
                  normalize_before=True, num_encoder_layers=6, num_decoder_layers=6, num_view=3, num_type=2,
                  num_input_dof=4, num_output_dof=6, max_input_length=400, max_output_length=128, vocab_size=514,
                  token=None, compute_dtype=None, beam_size=1, length_penalty=0.0, num_samples=0, temperature=1.0, top_k=0,
-                 top_p=1.0, sample_seed=0):
+                 top_p=1.0, sample_seed=0, constraint=None):
         super().__init__()
         # the reference hands the string to torch's Transformer layers (models.py:60-61,66-67), which take "relu" or "gelu"
         if activation not in ("relu", "gelu"):
@@ -160,6 +160,19 @@ class PlankModel(nn.Module):
             raise ValueError(f"NUM_SAMPLES ({num_samples}) and BEAM_SIZE ({beam_size}) > 1 exclude each other")
         self.num_samples = int(num_samples)
         self.sample_cfg = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(sample_seed))
+        # eval_step's plank grammar (decode.plank_grammar()): None = unconstrained, True = the default grammar
+        from .decode import PlankGrammar, plank_grammar
+        if constraint is True:
+            constraint = plank_grammar()
+        if constraint is False:
+            constraint = None
+        if constraint is not None:
+            if not isinstance(constraint, PlankGrammar):
+                raise ValueError(f"constraint must come from decode.plank_grammar(), got {constraint!r}")
+            constraint = plank_grammar(*constraint)
+            if num_output_dof != 6:
+                raise ValueError("the plank grammar (CONSTRAIN_PLANKS) is defined for six output DOF")
+        self.constraint = constraint
         self.compute_mode = compute_dtype                      # what the caller asked for
         self.split3 = compute_dtype == "x3"
         self.compute_dtype = "f32" if self.split3 else compute_dtype     # storage / kernel dtype: 'x3' is f32 with split products
@@ -863,20 +876,30 @@ class PlankModel(nn.Module):
         num_plank = len(valid_seq) // self.num_output_dof
         return valid_seq[:num_plank * self.num_output_dof].reshape(-1, self.num_output_dof)
 
-    def eval_step(self, batch, prefix=None):
+    def _grammar(self, constraint):
+        """The grammar of a call: its own ``constraint`` (False: none), else the one the model was built with."""
+        return self.constraint if constraint is None else constraint
+
+    def eval_step(self, batch, prefix=None, constraint=None):
         """reference models.py:267-323: greedy autoregressive sampling (KV-cached HIP decode); beam search instead when the
         model was built with beam_size > 1 (cfg.MODEL.BEAM_SIZE), seeded sampling of num_samples per drawing, best returned,
         when it was built with num_samples >= 1 (cfg.MODEL.NUM_SAMPLES).
 
         ``prefix`` (decode.prefix_table): a dict ``tokens`` [B, P], optional ``attach`` / ``lengths`` - the
         decode continues these positions instead of starting from the empty sequence; the dict then also carries
-        ``prefix_scores`` / ``prefix_logprobs``, the model's log-probabilities of the forced positions."""
+        ``prefix_scores`` / ``prefix_logprobs``, the model's log-probabilities of the forced positions.
+
+        ``constraint`` (decode.plank_grammar()): every free step selects among the candidates the plank
+        grammar allows, so every decoded row is a valid program up to its END.  None: the grammar the model was built with
+        (cfg.MODEL.CONSTRAIN_PLANKS; default none); False: none."""
+        constraint = self._grammar(constraint)
         if self.beam_size > 1:
-            return self.beam_search(batch, self.beam_size, self.length_penalty, prefix=prefix)
+            return self.beam_search(batch, self.beam_size, self.length_penalty, prefix=prefix, constraint=constraint or False)
         if self.num_samples >= 1:
-            return self.sample(batch, self.num_samples, length_penalty=self.length_penalty, prefix=prefix, **self.sample_cfg)
+            return self.sample(batch, self.num_samples, length_penalty=self.length_penalty, prefix=prefix,
+                               constraint=constraint or False, **self.sample_cfg)
         dec = self._decoder_for()
-        output, attach = dec.run(batch, prefix=prefix)
+        output, attach = dec.run(batch, prefix=prefix, constraint=constraint)
         return self._decode_dict(batch, {"tokens": output, "attach": attach, "prefix_scores": dec.last_prefix_scores,
                                          "prefix_logprobs": dec.last_prefix_logprobs}, prefix)
 
@@ -906,7 +929,7 @@ class PlankModel(nn.Module):
             prefix["lengths"] = lengths
         table = dec._check_prefix(prefix, batch, None, strict=False)
         n = int(table[0].max()) if table[0].numel() else 0
-        written, _ = dec.run(batch, early_stop=False, prefix=prefix, max_steps=n, strict_prefix=False)
+        written, _ = dec.run(batch, early_stop=False, prefix=prefix, max_steps=n, strict_prefix=False)    # (no constraint: all forced)
         # The step's own prefix_score is an f32 running sum: at |score| ~ 1 600 (128 positions of the headline model) one addition
         # rounds by up to 6e-5 and the sum drifted 4e-4 from float64 while every per-token value was within 1.1e-5
         # (tests/test_decode_logprob_gpu.py case A).  The scorer therefore sums the per-token values itself, in float64, over the
@@ -922,10 +945,10 @@ class PlankModel(nn.Module):
         scores = torch.where(summed, logprobs.double(), torch.zeros((), dtype=torch.float64)).sum(1).float()
         return {"scores": scores, "logprobs": logprobs, "lengths": table[0]}
 
-    def complete(self, batch, num_planks):
+    def complete(self, batch, num_planks, constraint=None):
         """eval_step continuing the first ``num_planks`` planks of the ground truth: the first num_planks * num_output_dof
         positions of ``batch["output_value"]``, clipped before each row's END, with the pointers of ``batch["output_label"]`` when
-        the batch has it, as the forced prefix."""
+        the batch has it, as the forced prefix.  ``constraint``: as in eval_step (the forced positions are not filtered)."""
         tok = batch["output_value"]
         P = min(int(num_planks) * self.num_output_dof, tok.shape[1])
         tok = tok[:, :P].detach().cpu()
@@ -935,7 +958,7 @@ class PlankModel(nn.Module):
         if "output_label" in batch:
             label = batch["output_label"][:, :P].detach().cpu()
             prefix["attach"] = torch.where(label >= self.vocab_size, label - self.vocab_size, torch.full_like(label, -1))
-        return self.eval_step(batch, prefix=prefix)
+        return self.eval_step(batch, prefix=prefix, constraint=constraint)
 
     def _decoder_for(self, key=None, build=None):
         """The way into a decoder: a bound handle, fresh bf16 shadows, and the cached decoder - the greedy one (``_decoder``; None
@@ -967,22 +990,24 @@ class PlankModel(nn.Module):
             groundtruths.append(self.parse_sequence(batch["output_value"][i].to(output.device)))
         return {"samples": output, "attach": attach, "predicts": predicts, "groundtruths": groundtruths}
 
-    def beam_search(self, batch, beam_size, length_penalty=0.0, prefix=None):
+    def beam_search(self, batch, beam_size, length_penalty=0.0, prefix=None, constraint=None):
         """Beam-search decode (decode.BeamDecoder): the eval_step dict of the best beam of every drawing plus ``scores``
-        [B, K], the cumulative log-probabilities of all beams in final-ranking order.  ``prefix``: as in eval_step, per drawing."""
+        [B, K], the cumulative log-probabilities of all beams in final-ranking order.  ``prefix``: as in eval_step, per drawing;
+        ``constraint``: as in eval_step."""
         from .decode import BeamDecoder
         dec = self._decoder_for(("beam", int(beam_size), float(length_penalty)), lambda: BeamDecoder(self, beam_size, length_penalty))
-        return self._decode_dict(batch, dec.run(batch, prefix=prefix), prefix)
+        return self._decode_dict(batch, dec.run(batch, prefix=prefix, constraint=self._grammar(constraint)), prefix)
 
-    def sample(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0, prefix=None):
+    def sample(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0, prefix=None,
+               constraint=None):
         """Seeded sampling decode (decode.SampleDecoder): the eval_step dict of the best sample of every drawing (by score /
         len^length_penalty) plus ``scores`` [B, N] (log-likelihood of every sample) and ``sample_tokens`` / ``sample_attach``
         [B, N, n], samples in final-ranking order.  The same seed and batch give the same samples on every call.  ``prefix``: as in
-        eval_step, per drawing."""
+        eval_step, per drawing; ``constraint``: as in eval_step."""
         from .decode import SampleDecoder
         key = ("sample", int(num_samples), float(temperature), int(top_k), float(top_p), float(length_penalty))
         dec = self._decoder_for(key, lambda: SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, length_penalty))
-        return self._decode_dict(batch, dec.run(batch, seed=seed, prefix=prefix), prefix)
+        return self._decode_dict(batch, dec.run(batch, seed=seed, prefix=prefix, constraint=self._grammar(constraint)), prefix)
 
     def forward(self, batch):
         """reference models.py:325-330."""
@@ -1018,7 +1043,9 @@ def build_model(cfg):
     (eval_step decodes by beam search with this many beams, 1 <= K <= 16; absent or 1: greedy), ``cfg.MODEL.LENGTH_PENALTY``
     (alpha of the final beam / sample ranking score / len^alpha, default 0) and the sampling keys ``cfg.MODEL.NUM_SAMPLES``
     (eval_step samples this many per drawing and returns the best, 1 <= N <= 64; absent or 0: greedy), ``TEMPERATURE`` (> 0,
-    default 1), ``TOP_K`` (>= 0, 0 = off), ``TOP_P`` (in (0, 1], 1 = off) and ``SAMPLE_SEED`` (default 0).  A bad value, or
+    default 1), ``TOP_K`` (>= 0, 0 = off), ``TOP_P`` (in (0, 1], 1 = off) and ``SAMPLE_SEED`` (default 0).  ``CONSTRAIN_PLANKS``
+    (bool, default off): eval_step decodes - in whichever mode - under the plank grammar of DESIGN.md section 15, with
+    ``MIN_PLANKS`` (default 1) and ``MAX_PLANKS`` (default: the last plank boundary of the decode).  A bad value, or
     NUM_SAMPLES >= 1 together with BEAM_SIZE > 1, raises ValueError."""
     model_cfg = cfg.MODEL
 
@@ -1027,6 +1054,11 @@ def build_model(cfg):
         return default if v is None else v
 
     dtype = opt("COMPUTE_DTYPE")
+    from .decode import plank_grammar
+    constrain = opt("CONSTRAIN_PLANKS", False)
+    if not isinstance(constrain, bool):
+        raise ValueError(f"CONSTRAIN_PLANKS must be a bool, got {constrain!r}")
+    grammar = plank_grammar(opt("MIN_PLANKS", 1), opt("MAX_PLANKS")) if constrain else None
     return PlankModel(
         cfg.MODEL.NUM_MODEL, cfg.MODEL.NUM_HEAD, cfg.MODEL.NUM_FEEDFORWARD, cfg.MODEL.DROPOUT,
         cfg.MODEL.ACTIVATION, cfg.MODEL.NORMALIZE_BEFORE, cfg.MODEL.NUM_ENCODER_LAYERS,
@@ -1034,4 +1066,4 @@ def build_model(cfg):
         cfg.DATA.NUM_OUTPUT_DOF, cfg.DATA.MAX_INPUT_LENGTH, cfg.DATA.MAX_OUTPUT_LENGTH, cfg.DATA.VOCAB_SIZE,
         cfg.TOKEN, compute_dtype=dtype, beam_size=opt("BEAM_SIZE", 1), length_penalty=float(opt("LENGTH_PENALTY", 0.0)),
         num_samples=opt("NUM_SAMPLES", 0), temperature=opt("TEMPERATURE", 1.0), top_k=opt("TOP_K", 0), top_p=opt("TOP_P", 1.0),
-        sample_seed=opt("SAMPLE_SEED", 0))
+        sample_seed=opt("SAMPLE_SEED", 0), constraint=grammar)
