@@ -502,6 +502,44 @@ int pa_mixture_nll_bwd_up(void* dvocab, void* dptr, int32_t out_dtype, float* ds
 int pa_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float b1,
                  float b2, float eps, int32_t step, float gscale, void* stream);
 int pa_cast(void* dst, int32_t dst_dtype, const void* src, int32_t src_dtype, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Gradient guard: global-norm clipping (torch.nn.utils.clip_grad_norm_), value clipping (clip_grad_value_) and the skip
+ * of a step whose gradient is not finite, decided ON THE DEVICE - no entry point below synchronises, allocates or reads
+ * anything back.  The caller owns one workspace of pa_grad_guard_ws_bytes() bytes, 16-byte aligned:
+ *   [0, 4 * PA_GRAD_GUARD_PARTIALS)   f32 per-block partial sums of squares
+ *   [4 * PA_GRAD_GUARD_PARTIALS, ..)  one pa_grad_guard_ctl (the control block; pass its address to pa_adam_step_guarded)
+ * pa_grad_guard_init zeroes the counters and sets `applied` = step0 >= 0 (the Adam step count a resumed optimizer hands over);
+ * `first_skipped_attempt` = -1.
+ *
+ * pa_grad_guard (two launches): sum of squares of g[0, n) - per-thread f32 accumulation, wave shuffle, LDS, ONE plain store per
+ * block, no atomics: block b sums the same elements in the same order every call, so the norm is bit-reproducible - then a
+ * one-block finish that adds the partials in double in a fixed order and writes the control block:
+ *   norm  = sqrt(sum) * |gscale|                       (the norm of the gradient Adam will see, g * gscale)
+ *   coef  = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1
+ *   apply = isfinite(norm) || !skip_nonfinite
+ *   attempts += 1;  apply ? (applied += 1, step_size = lr / (1 - b1^applied), inv_sqrt_bc2 = 1 / sqrt(1 - b2^applied), in
+ *   double as pa_adam_step computes them on the host) : (skipped += 1, first_skipped_attempt = attempts if it was -1).
+ * The squares are taken in f32: an entry with |g| above ~1.8e19 overflows its square and the step counts as NON-FINITE,
+ * although the entry itself is finite.
+ *
+ * pa_adam_step_guarded: pa_adam_step's loop, tail and bf16 shadow store, with step_size / inv_sqrt_bc2 / coef / apply read from
+ * the control block: apply == 0 returns before any store (p, m, v and the shadow keep every bit); else the gradient it applies
+ * is g * gscale * coef, clamped to +-clip_value when clip_value > 0.
+ * g and ws must be 16-byte aligned (PA_EALIGN), n > 0, max_norm / clip_value >= 0 and not NaN, ws_bytes >= the size above
+ * (PA_EINVAL); a failed check launches nothing. */
+#define PA_GRAD_GUARD_PARTIALS 2048
+typedef struct {
+    float norm, coef, step_size, inv_sqrt_bc2;
+    int32_t apply, applied, skipped, attempts, first_skipped_attempt;
+    int32_t pad_[7];
+} pa_grad_guard_ctl;
+int64_t pa_grad_guard_ws_bytes(void);
+int pa_grad_guard_init(void* ws, int64_t ws_bytes, int32_t step0, void* stream);
+int pa_grad_guard(const float* g, int64_t n, float gscale, float max_norm, int32_t skip_nonfinite, float lr, float b1,
+                  float b2, void* ws, int64_t ws_bytes, void* stream);
+int pa_adam_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float b1, float b2,
+                         float eps, float gscale, float clip_value, const pa_grad_guard_ctl* ctl, void* stream);
 /* One-GPU rehearsal of the data-parallel gradient exchange (the reference's `strategy: ddp`, configs/train_complete.yaml:18-21):
  * a stand-in for one ring all-reduce.  `blocks` workgroups (<= 256) stay resident for at least `min_us` microseconds and stream
  * `buf` (16-byte aligned, `bytes` long; contents unchanged) through HBM at least `passes` times.  Launched on a side stream by

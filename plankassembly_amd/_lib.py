@@ -88,6 +88,17 @@ class GroupDesc(C.Structure):
                 ("tok_ld", C.c_int32), ("order", C.c_void_p), ("seg", C.c_void_p)]
 
 
+class GradGuardCtl(C.Structure):
+    """include/plank_hip.h pa_grad_guard_ctl: the control block at byte GRAD_GUARD_CTL_OFFSET of the guard's workspace."""
+    _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("step_size", C.c_float), ("inv_sqrt_bc2", C.c_float),
+                ("apply", C.c_int32), ("applied", C.c_int32), ("skipped", C.c_int32), ("attempts", C.c_int32),
+                ("first_skipped_attempt", C.c_int32), ("pad_", C.c_int32 * 7)]
+
+
+GRAD_GUARD_PARTIALS = 2048
+GRAD_GUARD_CTL_OFFSET = 4 * GRAD_GUARD_PARTIALS
+GRAD_GUARD_WS_BYTES = GRAD_GUARD_CTL_OFFSET + C.sizeof(GradGuardCtl)      # == pa_grad_guard_ws_bytes()
+
 _lib = None
 
 
@@ -183,6 +194,10 @@ def lib():
             "pa_mixture_nll_bwd_up": (I, [P, P, I, P, P, P, P, I, P, P, P, I, I, I, I, F, P, P]),
             "pa_model_set_upstream": (I, [P, P]),
             "pa_adam_step": (I, [P, P, P, P, P, I64, F, F, F, F, I, F, P]),
+            "pa_grad_guard_ws_bytes": (I64, []),
+            "pa_grad_guard_init": (I, [P, I64, I, P]),
+            "pa_grad_guard": (I, [P, I64, F, F, I, F, F, F, P, I64, P]),
+            "pa_adam_step_guarded": (I, [P, P, P, P, P, I64, F, F, F, F, F, P, P]),
             "pa_cast": (I, [P, I, P, I, I64, P]),
             "pa_fake_collective": (I, [P, I64, I, I, F, P]),
             "pa_model_create": (I, [P, P]),

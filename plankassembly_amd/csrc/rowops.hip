@@ -873,6 +873,116 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     }
 }
 
+// ---- gradient guard (include/plank_hip.h pa_grad_guard): the sum of squares of the flat gradient as one partial per block.
+// No atomics: block b always adds the same elements in the same order (4 lane chains per thread, xor butterfly, 4 wave sums),
+// so two calls on the same buffer give the same bits.  NaN / inf entries propagate into the partial.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, int64_t n, float* partial) {
+    __shared__ float wsum[4];
+    const int64_t n4 = n >> 2;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
+        const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e * 4);
+        acc += gg * gg;
+    }
+    float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {           // tail (n % 4)
+        const float t = g[(n4 << 2) + threadIdx.x];
+        s += t * t;
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// One block: the partials in double, thread t takes t, t + 256, ... then a fixed LDS tree; thread 0 writes the control block.
+__global__ __launch_bounds__(256) void grad_guard_finish_kernel(const float* partial, int nparts, float gscale, float max_norm,
+                                                                int skip_nonfinite, float lr, float b1, float b2,
+                                                                pa_grad_guard_ctl* ctl) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += (double)partial[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const float norm = (float)(sqrt(red[0]) * fabs((double)gscale));
+    const bool finite = isfinite(norm);
+    float coef = 1.f;
+    if (max_norm > 0.f) {
+        coef = max_norm / (norm + 1e-6f);                      // torch.nn.utils.clip_grad_norm_
+        coef = coef > 1.f ? 1.f : coef;
+    }
+    const int apply = (finite || !skip_nonfinite) ? 1 : 0;
+    const int attempts = ctl->attempts + 1;
+    ctl->norm = norm;
+    ctl->coef = coef;
+    ctl->apply = apply;
+    ctl->attempts = attempts;
+    if (apply) {
+        const int step = ctl->applied + 1;
+        ctl->applied = step;
+        ctl->step_size = (float)((double)lr / (1.0 - pow((double)b1, (double)step)));
+        ctl->inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, (double)step)));
+    } else {
+        ctl->skipped = ctl->skipped + 1;
+        if (ctl->first_skipped_attempt < 0) ctl->first_skipped_attempt = attempts;
+    }
+}
+
+__global__ void grad_guard_init_kernel(pa_grad_guard_ctl* ctl, int step0) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    ctl->norm = 0.f; ctl->coef = 1.f; ctl->step_size = 0.f; ctl->inv_sqrt_bc2 = 0.f;
+    ctl->apply = 0; ctl->applied = step0; ctl->skipped = 0; ctl->attempts = 0; ctl->first_skipped_attempt = -1;
+    for (int i = 0; i < 7; ++i) ctl->pad_[i] = 0;
+}
+
+// adam_kernel with the step's scalars read from the guard's control block: a step the guard refused returns before any store.
+__global__ __launch_bounds__(256) void adam_guarded_kernel(float* p, const float* g, float* m, float* v, bf16* pb, int64_t n,
+                                                           float b1, float b2, float eps, float gscale, float clip,
+                                                           const pa_grad_guard_ctl* ctl) {
+    if (ctl->apply == 0) return;
+    const float step_size = ctl->step_size, inv_sqrt_bc2 = ctl->inv_sqrt_bc2, coef = ctl->coef;
+    const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+    const int64_t n4 = n >> 2;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 pp = *reinterpret_cast<f32x4*>(p + e * 4);
+        f32x4 gg = *reinterpret_cast<const f32x4*>(g + e * 4);
+        f32x4 mm = *reinterpret_cast<f32x4*>(m + e * 4);
+        f32x4 vv = *reinterpret_cast<f32x4*>(v + e * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gj = gg[j] * gscale * coef;
+            gj = gj > clip ? clip : (gj < -clip ? -clip : gj);          // (clip = +inf when off; a NaN stays a NaN)
+            // The fused multiply-adds are spelled out in the forms the compiler gives adam_kernel's expressions (which product
+            // of a sum goes into the fma is its choice, and it chose differently here when left to it): with coef == 1 and no
+            // clamp the moments then equal pa_adam_step's bit for bit - tests/test_grad_guard_gpu.py holds the two together.
+            mm[j] = __builtin_fmaf(omb1, gj, b1 * mm[j]);
+            vv[j] = __builtin_fmaf(b2, vv[j], (omb2 * gj) * gj);
+            pp[j] -= step_size * mm[j] / __builtin_fmaf(sqrtf(vv[j]), inv_sqrt_bc2, eps);
+        }
+        *reinterpret_cast<f32x4*>(p + e * 4) = pp;
+        *reinterpret_cast<f32x4*>(m + e * 4) = mm;
+        *reinterpret_cast<f32x4*>(v + e * 4) = vv;
+        if (pb) st4<bf16>(pb + e * 4, pp);
+    }
+    // tail (n % 4)
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t e = (n4 << 2) + threadIdx.x;
+        float gj = g[e] * gscale * coef;
+        gj = gj > clip ? clip : (gj < -clip ? -clip : gj);
+        const float mj = __builtin_fmaf(b1, m[e], omb1 * gj);            // (adam_kernel's tail fuses the OTHER product of m)
+        const float vj = __builtin_fmaf(b2, v[e], (omb2 * gj) * gj);
+        m[e] = mj; v[e] = vj;
+        p[e] -= step_size * mj / __builtin_fmaf(sqrtf(vj), inv_sqrt_bc2, eps);
+        if (pb) pb[e] = (bf16)p[e];
+    }
+}
+
 template <typename TD, typename TS>
 __global__ __launch_bounds__(256) void cast_kernel(TD* dst, const TS* src, int64_t n) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
@@ -1335,6 +1445,51 @@ extern "C" int pa_adam_step(float* p, const float* g, float* m, float* v, void* 
     const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
     PA_LAUNCH(adam_kernel, dim3(grid_for(n >> 2, 256, 2048)), dim3(256), 0, ST(stream), p, g, m, v, (bf16*)p_bf16, n,
                        step_size, b1, b2, eps, inv_sqrt_bc2, gscale);
+    return 0;
+}
+
+// ---- gradient guard: workspace = PA_GRAD_GUARD_PARTIALS f32 partials, then the control block
+static constexpr int64_t GUARD_CTL_OFFSET = (int64_t)PA_GRAD_GUARD_PARTIALS * sizeof(float);
+static_assert(sizeof(pa_grad_guard_ctl) == 64, "pa_grad_guard_ctl is 64 bytes (plankassembly_amd/_lib.py mirrors it)");
+
+extern "C" int64_t pa_grad_guard_ws_bytes(void) { return GUARD_CTL_OFFSET + (int64_t)sizeof(pa_grad_guard_ctl); }
+
+static int guard_ws_check(const void* ws, int64_t ws_bytes) {
+    if (!ws || ws_bytes < pa_grad_guard_ws_bytes()) return PA_EINVAL;
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return PA_EALIGN;
+    return 0;
+}
+
+extern "C" int pa_grad_guard_init(void* ws, int64_t ws_bytes, int32_t step0, void* stream) {
+    if (int rc = guard_ws_check(ws, ws_bytes)) return rc;
+    if (step0 < 0) return PA_EINVAL;
+    PA_LAUNCH(grad_guard_init_kernel, dim3(1), dim3(64), 0, ST(stream),
+              reinterpret_cast<pa_grad_guard_ctl*>(static_cast<char*>(ws) + GUARD_CTL_OFFSET), step0);
+    return 0;
+}
+
+extern "C" int pa_grad_guard(const float* g, int64_t n, float gscale, float max_norm, int32_t skip_nonfinite, float lr, float b1,
+                             float b2, void* ws, int64_t ws_bytes, void* stream) {
+    if (!g || n <= 0 || !(max_norm >= 0.f)) return PA_EINVAL;
+    if (int rc = guard_ws_check(ws, ws_bytes)) return rc;
+    if (reinterpret_cast<uintptr_t>(g) & 15) return PA_EALIGN;
+    const int grid = grid_for(n >> 2, 256, PA_GRAD_GUARD_PARTIALS);
+    float* partial = static_cast<float*>(ws);
+    PA_LAUNCH(grad_sumsq_kernel, dim3(grid), dim3(256), 0, ST(stream), g, n, partial);
+    PA_LAUNCH(grad_guard_finish_kernel, dim3(1), dim3(256), 0, ST(stream), (const float*)partial, grid, gscale, max_norm,
+              (int)(skip_nonfinite != 0), lr, b1, b2,
+              reinterpret_cast<pa_grad_guard_ctl*>(static_cast<char*>(ws) + GUARD_CTL_OFFSET));
+    return 0;
+}
+
+extern "C" int pa_adam_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float b1, float b2,
+                                    float eps, float gscale, float clip_value, const pa_grad_guard_ctl* ctl, void* stream) {
+    if (!p || !g || !m || !v || !ctl || n <= 0 || !(clip_value >= 0.f)) return PA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+         reinterpret_cast<uintptr_t>(v)) & 15) return PA_EALIGN;
+    if (reinterpret_cast<uintptr_t>(ctl) & 3) return PA_EALIGN;
+    PA_LAUNCH(adam_guarded_kernel, dim3(grid_for(n >> 2, 256, 2048)), dim3(256), 0, ST(stream), p, g, m, v, (bf16*)p_bf16, n,
+              b1, b2, eps, gscale, clip_value > 0.f ? clip_value : __builtin_inff(), ctl);
     return 0;
 }
 

@@ -386,6 +386,35 @@ def adam_step(p, g, m, v, step, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0,
                                  C.c_float(gscale), L.stream()), "pa_adam_step")
 
 
+def grad_guard_ws(device, step0=0):
+    """A workspace of the gradient guard (include/plank_hip.h pa_grad_guard), counters zeroed, Adam step count = ``step0``."""
+    ws = torch.empty(L.ws_bytes("pa_grad_guard_ws_bytes"), dtype=torch.uint8, device=device)
+    L.check(L.lib().pa_grad_guard_init(L.ptr(ws), C.c_int64(ws.numel()), int(step0), L.stream()), "pa_grad_guard_init")
+    return ws
+
+
+def grad_guard(g, ws, gscale=1.0, max_norm=0.0, skip_nonfinite=False, lr=1e-4, b1=0.9, b2=0.999):
+    """Enqueue the norm of ``g * gscale`` and the step decision into ``ws`` (two launches, nothing read back)."""
+    L.check(L.lib().pa_grad_guard(L.ptr(g), C.c_int64(g.numel()), C.c_float(gscale), C.c_float(max_norm or 0.0),
+                                  int(bool(skip_nonfinite)), C.c_float(lr), C.c_float(b1), C.c_float(b2), L.ptr(ws),
+                                  C.c_int64(ws.numel()), L.stream()), "pa_grad_guard")
+
+
+def grad_guard_ctl(ws):
+    """The guard's control block as a dict.  SYNCHRONISES (a device-to-host copy of 64 bytes)."""
+    raw = ws[L.GRAD_GUARD_CTL_OFFSET:L.GRAD_GUARD_WS_BYTES].cpu().numpy().tobytes()
+    c = L.GradGuardCtl.from_buffer_copy(raw)
+    return {k: getattr(c, k) for k, _ in L.GradGuardCtl._fields_ if k != "pad_"}
+
+
+def adam_step_guarded(p, g, m, v, ws, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, clip_value=0.0, p_bf16=None):
+    """pa_adam_step with step size, bias correction, clip coefficient and the apply flag taken from the guard's ``ws``."""
+    ctl = C.c_void_p(ws.data_ptr() + L.GRAD_GUARD_CTL_OFFSET)
+    L.check(L.lib().pa_adam_step_guarded(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(p_bf16), C.c_int64(p.numel()),
+                                         C.c_float(b1), C.c_float(b2), C.c_float(eps), C.c_float(gscale),
+                                         C.c_float(clip_value or 0.0), ctl, L.stream()), "pa_adam_step_guarded")
+
+
 def cast(src, dtype):
     dst = torch.empty(src.shape, dtype=dtype, device=src.device)
     L.check(L.lib().pa_cast(L.ptr(dst), L.dt(dst), L.ptr(src), L.dt(src), C.c_int64(src.numel()), L.stream()),

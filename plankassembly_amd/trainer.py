@@ -79,6 +79,7 @@ class Trainer(torch.nn.Module):
         self.logger = None
         self.global_step = 0
         self._logged = {}
+        self.optimizer_kwargs = {}             # FusedAdam's guard arguments, from the `trainer:` block (optimizer_options)
 
     # ------------------------------------------------------------------ logging (self.log of Lightning)
     def log(self, name, value, **kw):
@@ -173,7 +174,7 @@ class Trainer(torch.nn.Module):
     def configure_optimizers(self):
         from .optim import FusedAdam
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
-        return {"optimizer": FusedAdam(self.model, lr=self.cfg.LR, grad_scale=1.0 / world)}
+        return {"optimizer": FusedAdam(self.model, lr=self.cfg.LR, grad_scale=1.0 / world, **self.optimizer_kwargs)}
 
     # ------------------------------------------------------------------ checkpoints (Lightning-shaped)
     def checkpoint(self, epoch, optimizer=None, best_score=None, steps_this_epoch=0, best_path="", last_path="",
@@ -269,6 +270,40 @@ def _to_device(batch, dev, model=None):
     return {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
 
 
+def _flag(tkw, key):
+    v = tkw.get(key)
+    if v is None or isinstance(v, bool):
+        return bool(v)
+    if isinstance(v, str) and v.lower() in ("true", "false"):      # `--trainer.detect_anomaly True` arrives as a string
+        return v.lower() == "true"
+    raise ValueError(f"trainer.{key} must be a bool, got {v!r}")
+
+
+def optimizer_options(tkw):
+    """The gradient-guard keys of the `trainer:` block -> (FusedAdam keyword arguments, raise_on_skip).
+
+    ``gradient_clip_val`` (None / 0: off) with ``gradient_clip_algorithm`` ``norm`` (default) or ``value``: Lightning's own
+    keys, clip_grad_norm_ resp. clip_grad_value_ before the optimizer step.  ``detect_anomaly`` (the reference sets it,
+    configs/train_complete.yaml:16 there: a run dies on a non-finite gradient): a step with a non-finite gradient is not
+    applied, and the loop raises at the next epoch boundary - with the weights still clean.  ``skip_nonfinite_steps`` (this
+    repository's key): the same skip without the raise."""
+    kw = {}
+    algo = tkw.get("gradient_clip_algorithm")
+    algo = "norm" if algo is None else algo
+    if algo not in ("norm", "value"):
+        raise ValueError(f"trainer.gradient_clip_algorithm must be 'norm' or 'value', got {algo!r}")
+    val = tkw.get("gradient_clip_val")
+    if val is not None:
+        if isinstance(val, bool) or not isinstance(val, (int, float)) or val != val or val < 0 or val == float("inf"):
+            raise ValueError(f"trainer.gradient_clip_val must be a finite number >= 0 (0 / null: off), got {val!r}")
+        if val > 0:
+            kw["max_grad_norm" if algo == "norm" else "clip_value"] = float(val)
+    raise_on_skip = _flag(tkw, "detect_anomaly")
+    if raise_on_skip or _flag(tkw, "skip_nonfinite_steps"):
+        kw["skip_nonfinite"] = True
+    return kw, raise_on_skip
+
+
 def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
     """The part of ``pl.Trainer.fit/test`` the reference relies on."""
     seed, tkw, hparams = load_cli_config(config)
@@ -310,6 +345,7 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
         if rank == 0:
             print({k: round(v, 4) for k, v in module._logged.items()})
         return module
+    module.optimizer_kwargs, raise_on_skip = optimizer_options(tkw)
     opt = module.configure_optimizers()["optimizer"]
     module.optimizer = opt
     start_epoch, best, best_file = 0, -1.0, ""
@@ -320,6 +356,7 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
         best_file = getattr(module, "resume_best_path", "")
         if best_file and not os.path.exists(best_file):
             best_file = ""
+    guard_base = module.global_step                # the guard counts attempts from here (optimizer built / state loaded)
     sync = None
     if world > 1:
         from .distributed import GradSync
@@ -351,6 +388,15 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
         l, a = module._train_stats
         module.log("train/loss", l); module.log("train/accuracy", a)
         torch.cuda.synchronize()
+        if getattr(opt, "guarded", False):                 # the guard's one read-back, where the loop synchronises anyway
+            gs = opt.guard_stats()
+            module.log("train/grad_norm", gs["norm"]); module.log("train/skipped_steps", gs["skipped_steps"])
+            if raise_on_skip and gs["skipped_steps"] > 0:
+                # every rank sees the same summed gradients, so every rank skipped the same steps and raises here
+                raise RuntimeError(
+                    f"detect_anomaly: {gs['skipped_steps']} optimizer step(s) had a non-finite gradient and were not applied; "
+                    f"the first at global step {guard_base + gs['first_skipped_attempt'] - 1} (epoch {epoch}). The weights "
+                    f"hold only the steps with finite gradients.")
         if rank == 0:
             print(f"epoch {epoch}: train/loss {float(l):.4f} train/accuracy {float(a):.4f} "
                   f"{n * world / (time.perf_counter() - t0):.1f} samples/s")
