@@ -823,6 +823,38 @@ int pa_dec_cross_mq32(float* ctx, const float* qt, const float* mem, const uint8
 int pa_dec_self_mq32(float* ctx, const float* qt, const float* xcache, const int32_t* t_dev, int32_t B, int32_t Tmax, int32_t H,
                      int32_t d, void* stream);
 
+/* ---- device-resident dataset (csrc/tokenise.hip; plankassembly_amd/device_data.py) ----
+ * One launch, one block of 256 threads per batch element: the prepared drawings stay in HBM as CSR arrays and a batch is
+ * tokenised where the model reads it.  Restates plankassembly_amd/datasets.py `_sorted_tokens`, `_pad_inputs`,
+ * `prepare_output_sequence` and `add_noise` (reference plankassembly/datasets/line_data.py:34-83 input sequence, :85-109
+ * output sequence, :128-133 augmentation; sideface_data.py:137-213; data_utils.py:6-12 quantisation, :24-68 noise), bit for
+ * bit: float64, every product and sum rounded on its own, truncation toward zero.
+ *   line_off int32 [N+1], box f64 [L][4] (xmin ymin xmax ymax, used as stored when a drawing is not augmented), seg f64
+ *   [L][4] (x0 y0 x1 y1 of the straight segment; NULL: side faces, no augmentation), view / type uint8 [L] (type NULL
+ *   with with_type = 0), plank_off int32 [N+1], coords f64 [P][6], attach int32 [P][6] (-1: no pointer);
+ *   index int32 [B]: the drawing of each batch row (outside [0, N): the empty drawing);
+ *   S = MAX_INPUT_LENGTH - 1, T = MAX_OUTPUT_LENGTH, n_bits <= 11 (PA_ESHAPE beyond); END / PAD tokens, vocab size;
+ *   outputs int64 [B][S] value / pos / coord / view / type (type NULL with with_type = 0), uint8 [B][S] mask, int64
+ *   [B][T] value / label, uint8 [B][T] mask, n_tokens int32 [B] = the unmasked encoder rows of each drawing (4 per kept
+ *   line + END).
+ * A drawing with more than PA_TOKENISE_MAX_LINES lines, more than (S - 1) / 4 lines or more than (T - 1) / 6 planks is cut
+ * there (the host rejects such data when it is loaded); coordinates must lie in [-1, 1].
+ * augmentation != 0 (needs seg): the draws are counter-based - mix32 (csrc/pa_device.h) of (seed, epoch, drawing number,
+ * line number, draw slot), so a drawing's tokens in an epoch do not depend on the batch it is in.  A drawing is augmented
+ * when its draw is < aug_ratio; num_select is uniform in [1, min(n, ceil(n * noise_ratio))]; the selected lines are those
+ * with the num_select smallest (hash, line) pairs; each is deleted (draw > 0.5), or loses noise = rint(u * noise_length *
+ * 1000) / 1000 of its length at the tail (draw > 0.5) or the head, or is deleted when it is not longer than the noise.  A
+ * drawing that loses every line tokenises as [END, PAD, ...]. */
+#define PA_TOKENISE_MAX_LINES 1024
+int pa_tokenise_drawings(const int32_t* line_off, const double* box, const double* seg, const uint8_t* view,
+                         const uint8_t* type, const int32_t* plank_off, const double* coords, const int32_t* attach,
+                         int32_t N, const int32_t* index, int32_t B, int32_t S, int32_t T, int32_t n_bits,
+                         int32_t tok_end, int32_t tok_pad, int32_t vocab, int32_t with_type, int32_t augmentation,
+                         double aug_ratio, double noise_ratio, double noise_length, uint32_t seed, uint32_t epoch,
+                         int64_t* in_value, int64_t* in_pos, int64_t* in_coord, int64_t* in_view, int64_t* in_type,
+                         uint8_t* in_mask, int64_t* out_value, int64_t* out_label, uint8_t* out_mask,
+                         int32_t* n_tokens, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

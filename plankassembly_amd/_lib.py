@@ -126,7 +126,7 @@ def lib():
                 "(hipcc, gfx950).  plankassembly_amd has no fallback path.")
         _lib = C.CDLL(LIB_PATH)
         _check_single_hip_runtime()
-        P, I, I64, F, U = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint32
+        P, I, I64, F, U, D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint32, C.c_double
         sig = {
             "pa_version": (I, []),
             "pa_gemm": (I, [P, P]),
@@ -237,6 +237,8 @@ def lib():
             "pa_dec_cross_mq_ws_bytes": (I64, [I, I]),
             "pa_dec_cross_mq32_ws": (I, [P, P, P, P, P, I, I, I, I, P, I64, P]),
             "pa_dec_self_mq32": (I, [P, P, P, P, I, I, I, I, P]),
+            "pa_tokenise_drawings": (I, [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, D, D, D, U, U,
+                                         P, P, P, P, P, P, P, P, P, P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(_lib, name)

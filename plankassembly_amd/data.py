@@ -175,6 +175,11 @@ class DevicePrefetcher:
         # (no wait on the main stream: a collated batch does not depend on the step in flight, and waiting would park
         # prepare_batch's device -> host read behind that whole step)
         with torch.cuda.stream(self.side):
+            ready = raw.get("_ready")                            # device_data.DeviceLoader: tokenised on the loader's own stream
+            if ready is not None:
+                self.side.wait_event(ready)
+                for t in _tensors_of(raw):
+                    t.record_stream(self.side)
             if known is not None:
                 dev = self.model._flat.device
                 moved = {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in raw.items()}

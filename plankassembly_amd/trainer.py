@@ -66,6 +66,7 @@ class Trainer(torch.nn.Module):
     with_type = True
     default_lines = (8, 299)
     dataset_cls = LineDataset
+    device_kind = "line"                       # plankassembly_amd.device_data.pack_infos(kind=...)
     train_augmentation = True
 
     def __init__(self, hparams):
@@ -105,7 +106,26 @@ class Trainer(torch.nn.Module):
             return self.dataset_cls(root, parse_splits_list(split), self.cfg.TOKEN, self.cfg.DATA, augmentation)
         return SyntheticDrawings(int(self.cfg.get("SYNTHETIC_SAMPLES", n_default)), self._spec(), seed)
 
+    def _split_on_disk(self, split_key):
+        split = self.cfg.get(split_key)
+        return bool(split) and all(os.path.exists(s) for s in str(split).split()) and os.path.isdir(str(self.cfg.get("ROOT", "")))
+
+    def _device_loader(self, split_key, shuffle, drop_last, seed, augmentation):
+        """``DEVICE_DATASET: true``: the split's drawings packed once into HBM and every batch tokenised there
+        (device_data.py).  ``NUM_WORKERS`` has no meaning on this path."""
+        from .device_data import DeviceDrawings, DeviceLoader, pack_infos
+        dev = self.model._flat.device
+        if dev.type != "cuda":
+            dev = torch.device("cuda", torch.cuda.current_device())
+        cache = self.__dict__.setdefault("_device_drawings", {})       # a split is read and uploaded once, not per validation
+        if (split_key, dev) not in cache:
+            packed = pack_infos(str(self.cfg.get("ROOT", "")), parse_splits_list(self.cfg.get(split_key)), self.device_kind)
+            cache[split_key, dev] = DeviceDrawings(packed, self.cfg.TOKEN, self.cfg.DATA, dev)
+        return DeviceLoader(cache[split_key, dev], self.cfg.BATCH_SIZE, shuffle, drop_last, augmentation, seed)
+
     def _loader(self, split_key, n_default, shuffle, drop_last, seed, augmentation=False):
+        if self.cfg.get("DEVICE_DATASET", False) and self._split_on_disk(split_key):
+            return self._device_loader(split_key, shuffle, drop_last, seed, augmentation)
         ds = self._dataset(split_key, n_default, seed, augmentation)
         sampler = None
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -247,6 +267,7 @@ class SidefaceTrainer(Trainer):
     with_type = False
     default_lines = (0, 74)
     dataset_cls = SidefaceDataset
+    device_kind = "sideface"
 
     def test_step(self, batch, batch_idx):
         outputs = self.model(batch)
@@ -370,7 +391,9 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
         if 0 < max_steps <= module.global_step:            # a resumed run whose epoch was cut by max_steps: nothing left to do
             break
         module.model.train()
-        if hasattr(loader.sampler, "set_epoch"):
+        if hasattr(loader, "set_epoch"):                   # device_data.DeviceLoader: sampler order and augmentation draws
+            loader.set_epoch(epoch)
+        elif hasattr(loader.sampler, "set_epoch"):
             loader.sampler.set_epoch(epoch)
         t0, n, steps_here = time.perf_counter(), 0, 0
         from .data import DevicePrefetcher
