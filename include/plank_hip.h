@@ -483,7 +483,8 @@ int pa_mixture_nll_bwd(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, 
                        void* stream);
 /* The same forward on an EIGHT-float statistics block that the launch zeroes itself: [0] summed NLL, [1] unmasked rows, [2] correct
  * rows, [3] upstream d(loss) (armed with 1.0), [4] loss = [0] / [1], [5] accuracy = [2] / ([1] + 1e-10) - reference
- * plankassembly/models.py:226-231 - written by a one-wave finishing launch behind the forward kernel, [6], [7] spare.  The training step returns
+ * plankassembly/models.py:226-231 - written by a one-wave finishing launch behind the forward kernel; [6], [7]: one int64, the NLL sum in units of 2^-30 (the blocks add
+ * their sums there with an integer atomic, so the loss does not depend on the order they arrive in; stats8 must be 8-byte aligned).  The training step returns
  * views of [4] / [5]: no element-wise launches behind the forward.  pa_mixture_nll_bwd_up: `upstream` (device f32 scalar, or NULL =
  * stats[3]) is d(loss) from the caller's autograd - read in place instead of being copied into stats[3]. */
 int pa_mixture_nll_fwd_fin(float* stats8, float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
@@ -624,7 +625,8 @@ int64_t pa_model_train_ws_bytes(pa_model* m, int32_t B, int32_t S, int32_t T);
  * [0] sum of -log p(label) over non-PAD labels, [1] #non-PAD, [2] #correct.
  * loss = stats[0]/stats[1] (reference models.py:221), accuracy = stats[2]/(stats[1]+1e-10) (:227);
  * [3] upstream gradient d(objective)/d(loss), initialised to 1 by the forward and read (on the
- * device, no host sync) by the backward; [4] loss, [5] accuracy (written by the forward's last launch), [6], [7] spare.
+ * device, no host sync) by the backward; [4] loss, [5] accuracy (written by the forward's last launch), [6], [7] the NLL sum as one
+ * int64 in units of 2^-30 (order-free; the block must be 8-byte aligned).
  * A caller that sized the block for the four-float layout of rounds 1-4 gets a 16-byte out-of-bounds write: size it with
  * pa_model_stats_floats().
  * `seed` keys this step's dropout masks (training != 0 and cfg.dropout > 0). */

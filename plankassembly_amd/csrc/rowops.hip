@@ -736,6 +736,12 @@ __device__ __forceinline__ RowStat wave_merge(RowStat a) {
 constexpr int NLL_ROWS = 4;      // rows per block (one per wave); the three statistics leave a block as ONE atomic each
 constexpr int NLL_VSLOTS = 16;   // a lane holds up to 16 vocabulary logits (V <= 1024) / 4 pointer logits (T <= 256) of its row:
 constexpr int NLL_PSLOTS = 4;    // all loads are issued up front, unconditionally (clamped index), then reduced in order
+// FIXED (the stats8 form): the blocks' NLL sums meet in a 64-bit fixed-point word (stats[6..7], 2^-30 units) - integer addition is
+// associative, so the loss has the same bits whatever order the blocks arrive in (a float atomic gave the last bits of the loss to
+// the arrival order: the same batch twice differed by 3 ulp).  The two counts are whole numbers below 2^24 and exact in any order.  A
+// sum that is not finite, or too large for the word, still goes to stats[0] as a float and reaches the loss.
+constexpr float NLL_FIXED_ONE = 1073741824.f;                        // 2^30
+template <bool FIXED>
 __global__ __launch_bounds__(256) void mixture_nll_fwd_kernel(float* stats, float* row_lse, const float* vocab, int ldv,
                                                               const float* ptr, const float* sw, const int64_t* label,
                                                               int B, int Tn, int V, int pad) {
@@ -786,7 +792,9 @@ __global__ __launch_bounds__(256) void mixture_nll_fwd_kernel(float* stats, floa
     __syncthreads();
     if (threadIdx.x < 3) {
         const float v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-        if (v != 0.f) atomicAdd(stats + threadIdx.x, v);
+        if (FIXED && threadIdx.x == 0 && fabsf(v) < 4294967296.f) {                       // (false for a NaN)
+            if (v != 0.f) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 6), (unsigned long long)__float2ll_rn(v * NLL_FIXED_ONE));
+        } else if (v != 0.f) atomicAdd(stats + threadIdx.x, v);
     }
 }
 // stats8 form (pa_mixture_nll_fwd_fin): loss = nll / count, accuracy = hits / (count + 1e-10) (reference models.py:226-231) and the
@@ -796,7 +804,9 @@ __global__ __launch_bounds__(256) void mixture_nll_fwd_kernel(float* stats, floa
 // instead of the fence to 33.8 us (512 blocks x 4 returning atomics on four words) - more than the launches they replaced.
 __global__ void mixture_nll_finish_kernel(float* stats) {
     if (threadIdx.x == 0) {
-        const float s0 = stats[0], s1 = stats[1], s2 = stats[2];
+        const long long q = *reinterpret_cast<const long long*>(stats + 6);               // the fixed-point NLL sum (8-byte aligned)
+        const float s0 = stats[0] + (float)((double)q * (1.0 / (double)NLL_FIXED_ONE)), s1 = stats[1], s2 = stats[2];
+        stats[0] = s0;
         stats[4] = s0 / s1; stats[5] = s2 / (s1 + 1e-10f); stats[3] = 1.0f;
     }
 }
@@ -1403,16 +1413,17 @@ extern "C" int pa_mixture_nll_fwd(float* stats, float* row_lse, const float* voc
                                   void* stream) {
     if (!stats || !row_lse || !vocab || !ptr || !sw || !label || B <= 0 || T <= 0 || V <= 0 || ldv < V) return PA_EINVAL;
     const int grid = (int)(((int64_t)B * T + NLL_ROWS - 1) / NLL_ROWS);
-    PA_LAUNCH(mixture_nll_fwd_kernel, dim3(grid), dim3(256), 0, ST(stream), stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad);
+    PA_LAUNCH(mixture_nll_fwd_kernel<false>, dim3(grid), dim3(256), 0, ST(stream), stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad);
     return 0;
 }
 extern "C" int pa_mixture_nll_fwd_fin(float* stats8, float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
                                       const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
                                       void* stream) {
     if (!stats8 || !row_lse || !vocab || !ptr || !sw || !label || B <= 0 || T <= 0 || V <= 0 || ldv < V) return PA_EINVAL;
+    if (reinterpret_cast<uintptr_t>(stats8) & 7) return PA_EINVAL;                         // stats8[6..7] is one 64-bit word
     const int grid = (int)(((int64_t)B * T + NLL_ROWS - 1) / NLL_ROWS);
     if (hipMemsetAsync(stats8, 0, 8 * sizeof(float), ST(stream)) != hipSuccess) return PA_EINVAL;      // sums, ticket (and the rest)
-    PA_LAUNCH(mixture_nll_fwd_kernel, dim3(grid), dim3(256), 0, ST(stream), stats8, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad);
+    PA_LAUNCH(mixture_nll_fwd_kernel<true>, dim3(grid), dim3(256), 0, ST(stream), stats8, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad);
     PA_LAUNCH(mixture_nll_finish_kernel, dim3(1), dim3(64), 0, ST(stream), stats8);
     return 0;
 }
