@@ -377,6 +377,13 @@ int pa_segment_tail(const pa_ln_finish_desc* ln, int32_t n_ln, int32_t d_model, 
  *   same function the Linear epilogues use; tests/dropout_masks.py attn_keep); survivors are scaled by 1/(1-p); the backward
  *   kernels regenerate the same decisions.
  * bwd: dq/dk/dv have the layouts of q/k/v; delta is f32 scratch [B][H][Lq].
+ *   Rows without an allowed key (a packed batch element with no keys; every key of the row masked by kpm, alone or together with the
+ *   causal j <= i - row 0 when key 0 is masked): the softmax is over an empty set and the row is defined as O = 0 and lse = 0; in the
+ *   backward it contributes nothing to dK / dV and its dQ row is 0.  dK / dV rows of masked keys are exactly 0, and a dropped
+ *   probability contributes exactly 0.  Every kernel family keeps this contract (the first-generation f32 kernels are the standard:
+ *   `l_tot > 0 ? ... : 0`); tests/attn_parity.py holds all of them to it.
+ *   A launch writes only its windows: the H*dh columns of the rows of o / dq / dk / dv it owns (never the gap up to ld), and of lse
+ *   only the rows of each batch element that exist (rows past a packed element's length keep what they held).
  */
 typedef struct {
     const void* q; const void* k; const void* v; void* o;
