@@ -864,6 +864,29 @@ int pa_tokenise_drawings(const int32_t* line_off, const double* box, const doubl
                          uint8_t* in_mask, int64_t* out_value, int64_t* out_label, uint8_t* out_mask,
                          int32_t* n_tokens, void* stream);
 
+/* ---- plank matching (csrc/match.hip, core csrc/match_core.h; plankassembly_amd/metric.py DevicePlankScorer) ----
+ * One launch, one wave per pair: two token rows compared as sets of planks.  Restates plankassembly_amd/metric.py
+ * `pairwise_iou_3d` and `HungarianMatcher` (reference third_party/matcher.py:15-27 IoU, :29-61 cost -1 where IoU > threshold
+ * else 100000, assignment, TP) behind `PlankModel.parse_sequence` (reference models.py:258-265) and the trainers' box pipeline
+ * (trainer_complete.py:78-80: zero-extent predictions dropped, row 0 of both sides dropped).
+ *   seq_a int64 rows of len_a tokens, row r at seq_a + r * stride_a (stride in elements, >= 0); seq_b alike;
+ *   pair_a / pair_b int32 [n_pairs]: pair i compares row pair_a[i] of a with row pair_b[i] of b (both NULL: rows i and i).  The
+ *     rows named must exist: the kernel does not know how many there are;
+ *   a row holds L / dof planks, L = the index of its first end_token (len without one); plank 0 is dropped; with filter_x != 0
+ *     planks with any hi - lo == 0 are dropped (inverted planks stay); coordinates are clamped to [-32768, 32767];
+ *   out int32 [n_pairs][4] = tp (the maximum matching over iou > threshold), n_a, n_b (planks left), ties (pairs with
+ *     iou >= threshold && !(iou > threshold)); iou = inter / (vol_a + vol_b - inter) as one double division of exact
+ *     integers, 0 where inter == 0 - the `>` and `==` decisions of metric.py bit for bit.
+ * The cost being binary, tp equals the reference's TP whenever ties == 0; with ties > 0 the reference's TP depends on how scipy
+ * breaks equal costs, and the caller re-scores that pair on the host (DevicePlankScorer).
+ * len above PA_MATCH_MAX_LEN (170 planks a side after row 0) or dof != 6: PA_ESHAPE; threshold == 0 (the reference asserts it) or
+ * NaN, a null row / out pointer, one pair list without the other, a negative stride: PA_EINVAL; a failed check launches nothing.
+ * n_pairs == 0 launches nothing and returns 0. */
+#define PA_MATCH_MAX_LEN 1026
+int pa_plank_match(const int64_t* seq_a, int64_t stride_a, int32_t len_a, const int64_t* seq_b, int64_t stride_b, int32_t len_b,
+                   const int32_t* pair_a, const int32_t* pair_b, int32_t n_pairs, int32_t end_token, int32_t dof,
+                   int32_t filter_a, int32_t filter_b, double threshold, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,7 @@ def lib():
             "pa_dec_self_mq32": (I, [P, P, P, P, I, I, I, I, P]),
             "pa_tokenise_drawings": (I, [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, D, D, D, U, U,
                                          P, P, P, P, P, P, P, P, P, P, P]),
+            "pa_plank_match": (I, [P, I64, I, P, I64, I, P, P, I, I, I, I, I, D, P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(_lib, name)

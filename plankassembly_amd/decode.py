@@ -12,6 +12,7 @@ their kernels overlap for only 6.6 % of the busy time), so ``lanes=2`` stays as 
 from __future__ import annotations
 
 import collections
+import functools
 import ctypes as C
 import math
 import os
@@ -614,3 +615,44 @@ class SampleDecoder(GreedyDecoder):
         scores = self._scores(rows)
         self._loop(Tmax, early_stop, lambda: bool((first_end >= 0).all().cpu()))
         return _ranked("sample", tokens, attach, first_end, scores, first_end >= 0, B, N, Tmax, self.length_penalty, pbuf)
+
+
+@functools.lru_cache(maxsize=8)
+def _consensus_pairs(B, N, device):
+    """The B * N (N - 1) / 2 row pairs n < m of a [B * N, n] sample matrix (int32 [P, 2] on ``device``) and the (n, m) index rows."""
+    iu = torch.triu_indices(N, N, 1)
+    base = torch.arange(B)[:, None] * N
+    pairs = torch.stack([(base + iu[0]).reshape(-1), (base + iu[1]).reshape(-1)], 1).to(torch.int32)
+    return pairs.to(device), iu[0].to(device), iu[1].to(device)
+
+
+def consensus_select(sample_tokens, end_token, threshold=0.5):
+    """Minimum-Bayes-risk choice among the N samples of every drawing under the project's own metric.
+
+    ``sample_tokens`` int64 [B, N, n] on the device.  One ``ops.plank_match`` launch compares the samples of a drawing pairwise as
+    sets of planks (both sides without their zero-extent planks, edges at IoU > ``threshold``, ties no edges); F1(n, m) = 2 tp /
+    (n_a + n_b) in float64, 0 where tp == 0.  The utility of sample n is the INTEGER sum over m != n of rint(F1 * 2^40): integer
+    sums do not depend on their order, so duplicated samples - common at low temperature - get exactly equal utilities and the
+    lowest index (the most likely sample) wins among equals.  Everything stays on the device; nothing is read back.
+    Returns ``consensus_index`` int64 [B] and ``consensus_f1`` float64 [B, N] = utility / 2^40 / max(N - 1, 1)."""
+    from . import ops
+    B, N, n = sample_tokens.shape
+    dev = sample_tokens.device
+    if N == 1 or B == 0:
+        return {"consensus_index": torch.zeros(B, dtype=torch.int64, device=dev),
+                "consensus_f1": torch.zeros(B, N, dtype=torch.float64, device=dev)}
+    flat = sample_tokens.reshape(B * N, n)
+    pairs, iu0, iu1 = _consensus_pairs(B, N, dev)
+    c = ops.plank_match(flat, flat, pairs, end_token=end_token, filter_a=True, filter_b=True, threshold=threshold,
+                        check_pairs=False).view(B, -1, 4).to(torch.int64)
+    f1 = (2 * c[..., 0]).double() / (c[..., 1] + c[..., 2]).clamp(min=1).double()
+    q = torch.round(f1 * 2.0 ** 40).to(torch.int64)
+    pairwise = torch.zeros(B, N, N, dtype=torch.int64, device=dev)
+    pairwise[:, iu0, iu1] = q
+    pairwise[:, iu1, iu0] = q
+    utility = pairwise.sum(2)
+    best = utility.max(1, keepdim=True).values
+    index = torch.where(utility == best, torch.arange(N, device=dev)[None, :], N).min(1).values
+    # (a device tensor as the divisor: torch divides by a host scalar as a multiplication by its reciprocal, one rounding too many)
+    others = torch.full((), float(max(N - 1, 1)), dtype=torch.float64, device=dev)
+    return {"consensus_index": index, "consensus_f1": utility.double() / 2.0 ** 40 / others}

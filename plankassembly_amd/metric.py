@@ -5,6 +5,9 @@ predicted and ground-truth planks, Hungarian assignment with cost -1 where IoU >
 counted where the matched IoU >= threshold) and ``Criterion`` follows reference
 plankassembly/metric.py:6-30 (running sums of precision / recall / F1 and a count, summed over
 ranks).  Written from scratch on numpy/scipy: <= 21 boxes per sample, CPU work by nature.
+
+``DevicePlankScorer`` (opt-in, trainer hparam ``DEVICE_METRIC``) does the matching of a whole batch in one
+launch of ``ops.plank_match`` and keeps only the tie cases for the host matcher; its means are ``PlankScorer``'s bit for bit.
 """
 from __future__ import annotations
 
@@ -97,6 +100,118 @@ class PlankScorer:
 
     def means(self, sync=True):
         """(precision, recall, fmeasure) averaged over every sample added since the last call; resets."""
+        out = tuple(float(x) for x in self.criterion.compute(sync=sync))
+        self.criterion.reset()
+        return out
+
+
+def prf_from_counts(tp, n_pred, n_gt):
+    """``HungarianMatcher.__call__``'s last four lines for many drawings at once: float64 quotients rounded to float32, then the
+    same float32 torch CPU expressions - elementwise, so every drawing gets the bits the one-at-a-time call gives it."""
+    tp = np.asarray(tp, dtype=np.float64).reshape(-1)
+    n_pred = np.asarray(n_pred, dtype=np.int64).reshape(-1)
+    n_gt = np.asarray(n_gt, dtype=np.int64).reshape(-1)
+    prec = torch.from_numpy(np.where(n_pred > 0, tp / np.maximum(n_pred, 1), 0.0)).to(torch.float32)
+    rec = torch.from_numpy(np.where(n_gt > 0, tp / np.maximum(n_gt, 1), 0.0)).to(torch.float32)
+    f1 = prec * rec * 2 / (prec + rec + 1e-10)
+    return prec, rec, f1
+
+
+def planks_of_row(row, end_token, dof=6):
+    """``PlankModel.parse_sequence`` on a host row: the whole planks before the first END, [n, dof]."""
+    row = np.asarray(row).reshape(-1)
+    hits = np.nonzero(row == end_token)[0]
+    n = (int(hits[0]) if len(hits) else len(row)) // dof
+    return row[: n * dof].reshape(-1, dof)
+
+
+def valid_planks(pred):
+    """The trainers' ``_valid_pred`` on a host array: planks with a zero extent dropped, row 0 (the bounding box) kept."""
+    if len(pred) <= 1:
+        return pred
+    ok = np.all(np.abs(pred[1:, 3:] - pred[1:, :3]) != 0, axis=1)
+    return np.concatenate((pred[:1], pred[1:][ok]))
+
+
+class DevicePlankScorer:
+    """``PlankScorer`` with the matching on the GPU: ``add_batch`` launches ``ops.plank_match`` once for a
+    whole batch of decoded rows against their ground-truth rows and reads nothing back; ``means`` copies the integers of every
+    batch to the host in one transfer, forms precision / recall / F1 per drawing with HungarianMatcher's own float32 expressions
+    and feeds the same ``Criterion`` in drawing order - the means are bit-identical to ``PlankScorer``'s.
+
+    A pair of planks at IoU == threshold exactly is no edge of the matching but counts as a true positive when scipy happens to
+    assign it among the equal-cost leftovers; the kernel reports the number of such pairs per drawing (``ties``) and those
+    drawings - only those - are scored by ``HungarianMatcher`` on their tokens, like the host path.
+
+    ``match``: the launch, ``(samples, truth) -> int [B, 4]`` (tp, n_pred, n_gt, ties); the tests put a restatement here."""
+
+    def __init__(self, threshold: float, end_token: int, match=None):
+        self.threshold, self.end_token = float(threshold), int(end_token)
+        self.matcher = build_matcher(threshold)
+        self.criterion = build_criterion()
+        self._match = match or self._launch
+        self._pending = []                     # (counts [B, 4], samples, truth, keep) of the batches not yet read back
+        self.fallbacks = 0                     # drawings that went to the host matcher because of a tie
+
+    def _launch(self, samples, truth):
+        from . import ops
+        return ops.plank_match(samples, truth.to(samples.device), end_token=self.end_token, filter_a=True, filter_b=False,
+                               threshold=self.threshold)
+
+    def add(self, planks, truth):
+        """One drawing on the host, as ``PlankScorer.add`` (after everything ``add_batch`` has queued: the sums keep their order)."""
+        self._resolve()
+        scores = self.matcher(planks[1:], truth[1:])
+        self.criterion.update(*scores)
+        return {"precision": float(scores[0]), "recall": float(scores[1]), "fmeasure": float(scores[2])}
+
+    def add_batch(self, samples, truth_tokens, scores=False, keep=None):
+        """Decoded rows ``samples`` int64 [B, n] against the ground-truth rows ``truth_tokens`` int64 [B, T]: one launch, nothing
+        read back.  ``keep``: host booleans [B], False for a drawing that takes no part (SidefaceTrainer's empty inputs).
+        ``scores=True`` reads this batch (and everything queued before it) back now and returns the per-drawing dicts of
+        ``PlankScorer.add`` (None where ``keep`` is False)."""
+        if samples.shape[0] != truth_tokens.shape[0]:
+            raise ValueError(f"{samples.shape[0]} decoded rows against {truth_tokens.shape[0]} ground-truth rows")
+        keep = None if keep is None else [bool(k) for k in keep]
+        self._pending.append((self._match(samples, truth_tokens), samples, truth_tokens, keep))
+        return self._resolve()[-1] if scores else None
+
+    def _resolve(self):
+        """Everything queued -> the criterion, in drawing order.  One device-to-host copy of the integers; tokens only for ties."""
+        pending, self._pending = self._pending, []
+        if not pending:
+            return []
+        counts = torch.cat([p[0].reshape(-1, 4) for p in pending]).cpu().numpy().astype(np.int64)
+        prec, rec, f1 = prf_from_counts(counts[:, 0], counts[:, 1], counts[:, 2])
+        out, at = [], 0
+        for c, samples, truth, keep in pending:
+            B = c.shape[0]
+            mine = counts[at:at + B]
+            p, r, f = prec[at:at + B].clone(), rec[at:at + B].clone(), f1[at:at + B].clone()
+            tied = [i for i in np.nonzero(mine[:, 3] > 0)[0].tolist() if keep is None or keep[i]]
+            if tied:                                                    # the host path for these drawings, on their tokens
+                idx = torch.as_tensor(tied)
+                s_rows = samples.index_select(0, idx.to(samples.device)).cpu().numpy()
+                t_rows = truth.index_select(0, idx.to(truth.device)).cpu().numpy()
+                for k, i in enumerate(tied):
+                    pred = valid_planks(planks_of_row(s_rows[k], self.end_token))
+                    gt = planks_of_row(t_rows[k], self.end_token)
+                    p[i], r[i], f[i] = self.matcher(pred[1:], gt[1:])
+                self.fallbacks += len(tied)
+            dicts = []
+            for i in range(B):
+                if keep is not None and not keep[i]:
+                    dicts.append(None)
+                    continue
+                self.criterion.update(p[i], r[i], f[i])
+                dicts.append({"precision": float(p[i]), "recall": float(r[i]), "fmeasure": float(f[i])})
+            out.append(dicts)
+            at += B
+        return out
+
+    def means(self, sync=True):
+        """(precision, recall, fmeasure) averaged over every drawing added since the last call; resets."""
+        self._resolve()
         out = tuple(float(x) for x in self.criterion.compute(sync=sync))
         self.criterion.reset()
         return out

@@ -136,7 +136,7 @@ class PlankModel(nn.Module):
                  normalize_before=True, num_encoder_layers=6, num_decoder_layers=6, num_view=3, num_type=2,
                  num_input_dof=4, num_output_dof=6, max_input_length=400, max_output_length=128, vocab_size=514,
                  token=None, compute_dtype=None, beam_size=1, length_penalty=0.0, num_samples=0, temperature=1.0, top_k=0,
-                 top_p=1.0, sample_seed=0, constraint=None):
+                 top_p=1.0, sample_seed=0, constraint=None, sample_select=None):
         super().__init__()
         # the reference hands the string to torch's Transformer layers (models.py:60-61,66-67), which take "relu" or "gelu"
         if activation not in ("relu", "gelu"):
@@ -160,6 +160,11 @@ class PlankModel(nn.Module):
             raise ValueError(f"NUM_SAMPLES ({num_samples}) and BEAM_SIZE ({beam_size}) > 1 exclude each other")
         self.num_samples = int(num_samples)
         self.sample_cfg = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(sample_seed))
+        # which of the samples eval_step returns: None / "none" = the most likely one, "consensus" = the one that agrees best with
+        # the others as a set of planks (sample(select=))
+        self.sample_select = self._check_select(sample_select)
+        if self.sample_select is not None and off:
+            raise ValueError(f"SAMPLE_SELECT ({sample_select!r}) chooses among samples: it needs NUM_SAMPLES >= 1 (and so BEAM_SIZE 1)")
         # eval_step's plank grammar (decode.plank_grammar()): None = unconstrained, True = the default grammar
         from .decode import PlankGrammar, plank_grammar
         if constraint is True:
@@ -880,7 +885,15 @@ class PlankModel(nn.Module):
         """The grammar of a call: its own ``constraint`` (False: none), else the one the model was built with."""
         return self.constraint if constraint is None else constraint
 
-    def eval_step(self, batch, prefix=None, constraint=None):
+    @staticmethod
+    def _check_select(select):
+        if select in (None, False, "none", "None", ""):
+            return None
+        if select != "consensus":
+            raise ValueError(f"SAMPLE_SELECT must be 'consensus' or none, got {select!r}")
+        return select
+
+    def eval_step(self, batch, prefix=None, constraint=None, parse=True):
         """reference models.py:267-323: greedy autoregressive sampling (KV-cached HIP decode); beam search instead when the
         model was built with beam_size > 1 (cfg.MODEL.BEAM_SIZE), seeded sampling of num_samples per drawing, best returned,
         when it was built with num_samples >= 1 (cfg.MODEL.NUM_SAMPLES).
@@ -891,17 +904,21 @@ class PlankModel(nn.Module):
 
         ``constraint`` (decode.plank_grammar()): every free step selects among the candidates the plank
         grammar allows, so every decoded row is a valid program up to its END.  None: the grammar the model was built with
-        (cfg.MODEL.CONSTRAIN_PLANKS; default none); False: none."""
+        (cfg.MODEL.CONSTRAIN_PLANKS; default none); False: none.
+
+        ``parse=False``: the dict carries the token tensors only - no ``predicts`` / ``groundtruths``, whose per-row boolean
+        indexing costs two host synchronisations per drawing; for callers that score on the device (metric.DevicePlankScorer)."""
         constraint = self._grammar(constraint)
         if self.beam_size > 1:
-            return self.beam_search(batch, self.beam_size, self.length_penalty, prefix=prefix, constraint=constraint or False)
+            return self.beam_search(batch, self.beam_size, self.length_penalty, prefix=prefix, constraint=constraint or False,
+                                    parse=parse)
         if self.num_samples >= 1:
             return self.sample(batch, self.num_samples, length_penalty=self.length_penalty, prefix=prefix,
-                               constraint=constraint or False, **self.sample_cfg)
+                               constraint=constraint or False, parse=parse, select=self.sample_select, **self.sample_cfg)
         dec = self._decoder_for()
         output, attach = dec.run(batch, prefix=prefix, constraint=constraint)
         return self._decode_dict(batch, {"tokens": output, "attach": attach, "prefix_scores": dec.last_prefix_scores,
-                                         "prefix_logprobs": dec.last_prefix_logprobs}, prefix)
+                                         "prefix_logprobs": dec.last_prefix_logprobs}, prefix, parse)
 
     def score(self, batch, tokens=None, attach=None, lengths=None):
         """Log-likelihood of given sequences under the model, on the GPU: the greedy decode step with every position forced
@@ -975,39 +992,58 @@ class PlankModel(nn.Module):
             dec = self._mode_decoders[key] = build()
         return dec
 
-    def _decode_dict(self, batch, r, prefix):
-        """The eval_step dict of a decoder's result ``r``: the best row's parse, then what the mode adds - ``scores``, the prefix
-        keys when a prefix was given, ``sample_*``."""
-        out = self._eval_dict(batch, r["tokens"], r["attach"])
+    def _decode_dict(self, batch, r, prefix, parse=True):
+        """The eval_step dict of a decoder's result ``r``: the best row's parse (``parse``), then what the mode adds - ``scores``,
+        the prefix keys when a prefix was given, ``sample_*``."""
+        out = self._eval_dict(batch, r["tokens"], r["attach"], parse)
         keys = ["scores"] + (["prefix_scores", "prefix_logprobs"] if prefix is not None else []) + ["sample_tokens", "sample_attach"]
         out.update((k, r[k]) for k in keys if k in r)
         return out
 
-    def _eval_dict(self, batch, output, attach):
+    def _eval_dict(self, batch, output, attach, parse=True):
+        if not parse:
+            return {"samples": output, "attach": attach}
         predicts, groundtruths = [], []
         for i in range(output.shape[0]):
             predicts.append(self.parse_sequence(output[i]))
             groundtruths.append(self.parse_sequence(batch["output_value"][i].to(output.device)))
         return {"samples": output, "attach": attach, "predicts": predicts, "groundtruths": groundtruths}
 
-    def beam_search(self, batch, beam_size, length_penalty=0.0, prefix=None, constraint=None):
+    def beam_search(self, batch, beam_size, length_penalty=0.0, prefix=None, constraint=None, parse=True):
         """Beam-search decode (decode.BeamDecoder): the eval_step dict of the best beam of every drawing plus ``scores``
         [B, K], the cumulative log-probabilities of all beams in final-ranking order.  ``prefix``: as in eval_step, per drawing;
-        ``constraint``: as in eval_step."""
+        ``constraint`` / ``parse``: as in eval_step."""
         from .decode import BeamDecoder
         dec = self._decoder_for(("beam", int(beam_size), float(length_penalty)), lambda: BeamDecoder(self, beam_size, length_penalty))
-        return self._decode_dict(batch, dec.run(batch, prefix=prefix, constraint=self._grammar(constraint)), prefix)
+        return self._decode_dict(batch, dec.run(batch, prefix=prefix, constraint=self._grammar(constraint)), prefix, parse)
 
     def sample(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0, prefix=None,
-               constraint=None):
+               constraint=None, parse=True, select=None, consensus_threshold=None):
         """Seeded sampling decode (decode.SampleDecoder): the eval_step dict of the best sample of every drawing (by score /
         len^length_penalty) plus ``scores`` [B, N] (log-likelihood of every sample) and ``sample_tokens`` / ``sample_attach``
         [B, N, n], samples in final-ranking order.  The same seed and batch give the same samples on every call.  ``prefix``: as in
-        eval_step, per drawing; ``constraint``: as in eval_step."""
-        from .decode import SampleDecoder
+        eval_step, per drawing; ``constraint`` / ``parse``: as in eval_step.
+
+        ``select="consensus"`` (decode.consensus_select): the returned ``samples`` / ``attach`` / ``predicts``
+        are those of the sample that agrees best with the other N - 1 as a set of planks - the largest sum of pairwise plank F1 at
+        IoU > ``consensus_threshold`` (default 0.5), the most likely one among equals - instead of the most likely one.  The dict
+        then also has ``consensus_f1`` float64 [B, N] (each sample's mean F1 against the others) and ``consensus_index`` int64 [B];
+        ``scores`` / ``sample_tokens`` / ``sample_attach`` and their order are those of ``select=None``."""
+        from .decode import SampleDecoder, consensus_select
+        select = self._check_select(select)
         key = ("sample", int(num_samples), float(temperature), int(top_k), float(top_p), float(length_penalty))
         dec = self._decoder_for(key, lambda: SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, length_penalty))
-        return self._decode_dict(batch, dec.run(batch, seed=seed, prefix=prefix, constraint=self._grammar(constraint)), prefix)
+        r = dec.run(batch, seed=seed, prefix=prefix, constraint=self._grammar(constraint))
+        if select == "consensus":
+            if self.num_output_dof != 6:
+                raise ValueError("select='consensus' compares planks of six output DOF")
+            pick = consensus_select(r["sample_tokens"], self.token.END, 0.5 if consensus_threshold is None else consensus_threshold)
+            at = pick["consensus_index"][:, None, None].expand(-1, 1, r["sample_tokens"].shape[2])
+            r = dict(r, tokens=r["sample_tokens"].gather(1, at)[:, 0], attach=r["sample_attach"].gather(1, at)[:, 0])
+        out = self._decode_dict(batch, r, prefix, parse)
+        if select == "consensus":
+            out.update(pick)
+        return out
 
     def forward(self, batch):
         """reference models.py:325-330."""
@@ -1045,7 +1081,9 @@ def build_model(cfg):
     (eval_step samples this many per drawing and returns the best, 1 <= N <= 64; absent or 0: greedy), ``TEMPERATURE`` (> 0,
     default 1), ``TOP_K`` (>= 0, 0 = off), ``TOP_P`` (in (0, 1], 1 = off) and ``SAMPLE_SEED`` (default 0).  ``CONSTRAIN_PLANKS``
     (bool, default off): eval_step decodes - in whichever mode - under the plank grammar of DESIGN.md section 15, with
-    ``MIN_PLANKS`` (default 1) and ``MAX_PLANKS`` (default: the last plank boundary of the decode).  A bad value, or
+    ``MIN_PLANKS`` (default 1) and ``MAX_PLANKS`` (default: the last plank boundary of the decode).  ``SAMPLE_SELECT``
+    (``consensus``; default none): which of the NUM_SAMPLES samples eval_step returns (PlankModel.sample); it needs NUM_SAMPLES
+    >= 1.  A bad value, SAMPLE_SELECT without samples, or
     NUM_SAMPLES >= 1 together with BEAM_SIZE > 1, raises ValueError."""
     model_cfg = cfg.MODEL
 
@@ -1066,4 +1104,4 @@ def build_model(cfg):
         cfg.DATA.NUM_OUTPUT_DOF, cfg.DATA.MAX_INPUT_LENGTH, cfg.DATA.MAX_OUTPUT_LENGTH, cfg.DATA.VOCAB_SIZE,
         cfg.TOKEN, compute_dtype=dtype, beam_size=opt("BEAM_SIZE", 1), length_penalty=float(opt("LENGTH_PENALTY", 0.0)),
         num_samples=opt("NUM_SAMPLES", 0), temperature=opt("TEMPERATURE", 1.0), top_k=opt("TOP_K", 0), top_p=opt("TOP_P", 1.0),
-        sample_seed=opt("SAMPLE_SEED", 0), constraint=grammar)
+        sample_seed=opt("SAMPLE_SEED", 0), constraint=grammar, sample_select=opt("SAMPLE_SELECT"))

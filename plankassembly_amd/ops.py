@@ -495,3 +495,49 @@ def dec_self_mq32(qt, xcache, t_dev):
     L.check(L.lib().pa_dec_self_mq32(L.ptr(ctx), L.ptr(qt), L.ptr(xcache), L.ptr(t_dev), B, xcache.shape[1], H, d, L.stream()),
             "pa_dec_self_mq32")
     return ctx
+
+
+def plank_match(seq_a, seq_b, pairs=None, *, end_token, filter_a, filter_b, threshold, check_pairs=True):
+    """Token rows compared as sets of planks, one launch for all pairs (pa_plank_match, csrc/match.hip).
+
+    seq_a [Ra, len_a], seq_b [Rb, len_b]: int64 device tensors, last dimension contiguous, any row stride (a slice such as
+    ``samples[:, :n]`` works as it is).  ``pairs``: None - rows i of both (Ra == Rb) - or an integer tensor / sequence [n, 2] of
+    (row of a, row of b).  Pairs given on the host are range-checked there; pairs that already live on the device are checked
+    with one read-back unless ``check_pairs=False`` (the kernel cannot know how many rows exist).  ``filter_x``: drop the
+    zero-extent planks of that side.  Returns int32 [n, 4] on the device: tp, n_a, n_b, ties (include/plank_hip.h)."""
+    for name, t in (("seq_a", seq_a), ("seq_b", seq_b)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 2):
+            raise TypeError(f"{name} must be a 2-D int64 device tensor")
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError(f"{name}: the tokens of a row must be contiguous (stride {t.stride(1)})")
+    if seq_b.device != seq_a.device:
+        raise ValueError("seq_a and seq_b must be on the same device")
+    dev = seq_a.device
+    pa = pb = None
+    if pairs is None:
+        if seq_a.shape[0] != seq_b.shape[0]:
+            raise ValueError(f"without pairs both sides need the same number of rows ({seq_a.shape[0]} != {seq_b.shape[0]})")
+        n = seq_a.shape[0]
+    else:
+        p = torch.as_tensor(pairs)
+        if p.numel() == 0 and p.dim() == 1:                   # an empty list: no pairs
+            p = torch.empty(0, 2, dtype=torch.int32)
+        if p.dim() != 2 or p.shape[1] != 2 or p.dtype in (torch.bool, torch.float16, torch.bfloat16, torch.float32, torch.float64):
+            raise ValueError("pairs must be an integer [n, 2] tensor")
+        n = p.shape[0]
+        if n and (not p.is_cuda or check_pairs):
+            lo, hi = p.amin(0).tolist(), p.amax(0).tolist()
+            if min(lo) < 0 or hi[0] >= seq_a.shape[0] or hi[1] >= seq_b.shape[0]:
+                raise IndexError(f"pairs name rows outside seq_a ({seq_a.shape[0]} rows) / seq_b ({seq_b.shape[0]} rows)")
+        p = p.to(device=dev, dtype=torch.int32)
+        pa, pb = p[:, 0].contiguous(), p[:, 1].contiguous()
+    out = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out
+    sa = seq_a.stride(0) if seq_a.shape[0] > 1 else seq_a.shape[1]
+    sb = seq_b.stride(0) if seq_b.shape[0] > 1 else seq_b.shape[1]
+    with torch.cuda.device(dev):
+        L.check(L.lib().pa_plank_match(L.ptr(seq_a), C.c_int64(sa), int(seq_a.shape[1]), L.ptr(seq_b), C.c_int64(sb),
+                                       int(seq_b.shape[1]), L.ptr(pa), L.ptr(pb), int(n), int(end_token), 6, int(bool(filter_a)),
+                                       int(bool(filter_b)), float(threshold), L.ptr(out), L.stream()), "pa_plank_match")
+    return out

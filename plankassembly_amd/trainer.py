@@ -26,7 +26,7 @@ import torch.distributed as dist
 from .config import CfgNode, load_cli_config
 from .data import SynthSpec, synth_sample
 from .datasets import LineDataset, SidefaceDataset, parse_splits_list  # noqa: F401  (parse_splits_list re-exported)
-from .metric import PlankScorer
+from .metric import DevicePlankScorer, PlankScorer, planks_of_row, valid_planks
 from .models import build_model
 
 
@@ -75,7 +75,10 @@ class Trainer(torch.nn.Module):
         cfg = CfgNode(hparams)
         self.cfg = cfg
         self.model = build_model(cfg)
-        self.scorer = PlankScorer(cfg.THRESHOLD)
+        # DEVICE_METRIC: true (opt-in, like DEVICE_DATASET): validation / test drawings are matched on the GPU, one launch per batch
+        # (metric.DevicePlankScorer); the logged means and the pred_jsons are those of the host path, bit for bit
+        self.device_metric = bool(cfg.get("DEVICE_METRIC", False))
+        self.scorer = DevicePlankScorer(cfg.THRESHOLD, cfg.TOKEN.END) if self.device_metric else PlankScorer(cfg.THRESHOLD)
         self.matcher, self.criterion = self.scorer.matcher, self.scorer.criterion      # the reference's attribute names
         self.logger = None
         self.global_step = 0
@@ -159,6 +162,10 @@ class Trainer(torch.nn.Module):
         return torch.concat((pred[:1], pred[1:][ok]))
 
     def validation_step(self, batch, batch_idx):
+        if self.device_metric:
+            outputs = self.model.eval_step(batch, parse=False)
+            self.scorer.add_batch(outputs["samples"], batch["output_value"])
+            return
         outputs = self.model(batch)
         for pred, gt in zip(outputs["predicts"], outputs["groundtruths"]):
             self.scorer.add(self._valid_pred(pred), gt)
@@ -170,10 +177,30 @@ class Trainer(torch.nn.Module):
     def validation_epoch_end(self, outputs=None):
         self._log_means("val")
 
+    def _device_test_rows(self, batch, keep=None):
+        """DEVICE_METRIC test_step: decode without the per-row parse, one matching launch, then per drawing (name, kept planks
+        [n, 6], ground-truth planks, attach row, scores).  Beside the scorer's read-back of its integers, ONE device-to-host
+        copy per batch: decoded tokens, attach and ground-truth tokens side by side in one tensor."""
+        outputs = self.model.eval_step(batch, parse=False)
+        scores = self.scorer.add_batch(outputs["samples"], batch["output_value"], scores=True, keep=keep)
+        end = self.cfg.TOKEN.END
+        n = outputs["samples"].shape[1]
+        rows = torch.cat((outputs["samples"], outputs["attach"], batch["output_value"].to(outputs["samples"].device)), 1).cpu().numpy()
+        samples, attach, truth = rows[:, :n], rows[:, n:2 * n], rows[:, 2 * n:]
+        for i, name in enumerate(batch["name"]):
+            yield name, valid_planks(planks_of_row(samples[i], end)), planks_of_row(truth[i], end), attach[i], scores[i]
+
     def test_step(self, batch, batch_idx):
-        outputs = self.model(batch)
         out_dir = os.path.join(self.logger.log_dir, "pred_jsons")
         os.makedirs(out_dir, exist_ok=True)
+        if self.device_metric:
+            for name, vp, gt, atta, scores in self._device_test_rows(batch):
+                atta = atta[: vp.size]
+                atta = atta[: len(atta) // 6 * 6].reshape(-1, 6).tolist()
+                self._write_pred_json(out_dir, name, {"prediction": vp.reshape(-1, 6).tolist(), "attach": atta,
+                                                      "groundtruth": gt.reshape(-1, 6).tolist(), **scores})
+            return
+        outputs = self.model(batch)
         for name, pred, gt, atta in zip(batch["name"], outputs["predicts"], outputs["groundtruths"], outputs["attach"]):
             vp = self._valid_pred(pred)
             scores = self.scorer.add(vp, gt)
@@ -270,9 +297,17 @@ class SidefaceTrainer(Trainer):
     device_kind = "sideface"
 
     def test_step(self, batch, batch_idx):
-        outputs = self.model(batch)
         out_dir = os.path.join(self.logger.log_dir, "pred_jsons")
         os.makedirs(out_dir, exist_ok=True)
+        if self.device_metric:
+            empty = torch.all(batch["input_mask"][:, 1:], dim=1).cpu().tolist()
+            rows = self._device_test_rows(batch, keep=[not e for e in empty])
+            for (name, vp, gt, _, scores), e in zip(rows, empty):
+                predl = [] if e else vp.reshape(-1, 6).tolist()
+                scores = {"precision": 0.0, "recall": 0.0, "fmeasure": 0.0} if e else scores
+                self._write_pred_json(out_dir, name, {"prediction": predl, "groundtruth": gt.reshape(-1, 6).tolist(), **scores})
+            return
+        outputs = self.model(batch)
         for name, mask, pred, gt in zip(batch["name"], batch["input_mask"], outputs["predicts"], outputs["groundtruths"]):
             gtl = gt.cpu().numpy().reshape(-1, 6).tolist()
             if bool(torch.all(mask[1:])):
