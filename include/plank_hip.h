@@ -548,6 +548,38 @@ int pa_grad_guard(const float* g, int64_t n, float gscale, float max_norm, int32
                   float b2, void* ws, int64_t ws_bytes, void* stream);
 int pa_adam_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float b1, float b2,
                          float eps, float gscale, float clip_value, const pa_grad_guard_ctl* ctl, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Extended Adam: pa_adam_step / pa_adam_step_guarded with decoupled weight decay (torch.optim.AdamW) and an exponential moving
+ * average (EMA) of the weights inside the same streaming pass.  One launch; no atomics, no LDS, nothing depends on block order.
+ * Per element of an applied step, in this order:
+ *   gj = g * gscale * coef, clamped to +-clip_value when clip_value > 0        (coef = 1 without ctl)
+ *   m, v                    as pa_adam_step_guarded forms them (same fused multiply-adds, main loop and tail)
+ *   p  = p * f              f = (float)(1.0 - (double)lr * weight_decay), computed once on the host; only when weight_decay > 0
+ *                           and (decay_bits == NULL or the element's bit is set); rounded to f32 before the next line
+ *   p -= step_size * m / fma(sqrt(v), inv_sqrt_bc2, eps)
+ *   p_bf16 = (bf16)p        when p_bf16 != NULL
+ *   e  = fma(1 - d_t, p - e, e)                                                 when ema != NULL
+ * with d_t = ema_decay, or min(ema_decay, (1 + t) / (10 + t)) when ema_warmup, t = the Adam step count of THIS step.
+ * ctl == NULL: t = step, and step_size, inv_sqrt_bc2 and 1 - d_t are computed on the host in double and rounded once.
+ * ctl != NULL (the control block pa_grad_guard has just written): step_size / inv_sqrt_bc2 / coef / apply are read from it, t is
+ * ctl->applied and every thread forms 1 - d_t by the host's expression; `step` is ignored, `lr` only enters f.  apply == 0 returns
+ * before any store: p, m, v, the shadow AND the EMA keep every bit.
+ * decay_bits: bit (i & 7) of byte (i >> 3) set = element i decays; ceil(n / 8) bytes, any alignment.
+ * p, g, m, v, ema 16-byte aligned, ctl 4-byte aligned (PA_EALIGN); n > 0, clip_value >= 0, weight_decay >= 0 and finite,
+ * 0 <= ema_decay < 1, none NaN, step >= 1 when ctl == NULL (PA_EINVAL); a failed check launches nothing. */
+typedef struct {
+    float* p; const float* g; float* m; float* v; void* p_bf16;
+    float* ema;
+    const uint8_t* decay_bits;
+    int64_t n;
+    float lr, b1, b2, eps, gscale, clip_value, weight_decay, ema_decay;
+    int32_t step;
+    int32_t ema_warmup;
+    const pa_grad_guard_ctl* ctl;
+} pa_adam_ext_args;
+int64_t pa_adam_ext_args_bytes(void);
+int pa_adam_step_ext(const pa_adam_ext_args* a, void* stream);
 /* One-GPU rehearsal of the data-parallel gradient exchange (the reference's `strategy: ddp`, configs/train_complete.yaml:18-21):
  * a stand-in for one ring all-reduce.  `blocks` workgroups (<= 256) stay resident for at least `min_us` microseconds and stream
  * `buf` (16-byte aligned, `bytes` long; contents unchanged) through HBM at least `passes` times.  Launched on a side stream by

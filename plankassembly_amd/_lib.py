@@ -99,6 +99,15 @@ GRAD_GUARD_PARTIALS = 2048
 GRAD_GUARD_CTL_OFFSET = 4 * GRAD_GUARD_PARTIALS
 GRAD_GUARD_WS_BYTES = GRAD_GUARD_CTL_OFFSET + C.sizeof(GradGuardCtl)      # == pa_grad_guard_ws_bytes()
 
+
+class AdamExtArgs(C.Structure):
+    """include/plank_hip.h pa_adam_ext_args (pa_adam_step_ext); sizeof == pa_adam_ext_args_bytes()."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("p_bf16", C.c_void_p),
+                ("ema", C.c_void_p), ("decay_bits", C.c_void_p), ("n", C.c_int64),
+                ("lr", C.c_float), ("b1", C.c_float), ("b2", C.c_float), ("eps", C.c_float), ("gscale", C.c_float),
+                ("clip_value", C.c_float), ("weight_decay", C.c_float), ("ema_decay", C.c_float),
+                ("step", C.c_int32), ("ema_warmup", C.c_int32), ("ctl", C.c_void_p)]
+
 _lib = None
 
 
@@ -198,6 +207,8 @@ def lib():
             "pa_grad_guard_init": (I, [P, I64, I, P]),
             "pa_grad_guard": (I, [P, I64, F, F, I, F, F, F, P, I64, P]),
             "pa_adam_step_guarded": (I, [P, P, P, P, P, I64, F, F, F, F, F, P, P]),
+            "pa_adam_ext_args_bytes": (I64, []),
+            "pa_adam_step_ext": (I, [P, P]),
             "pa_cast": (I, [P, I, P, I, I64, P]),
             "pa_fake_collective": (I, [P, I64, I, I, F, P]),
             "pa_model_create": (I, [P, P]),

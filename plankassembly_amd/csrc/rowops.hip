@@ -993,6 +993,86 @@ __global__ __launch_bounds__(256) void adam_guarded_kernel(float* p, const float
     }
 }
 
+// ---- extended Adam (include/plank_hip.h pa_adam_step_ext): adam_guarded_kernel's element rule with decoupled weight decay
+// before the update and an exponential moving average of the new weights after it, all in the one streaming pass.
+// A product the compiler may not contract into the subtraction that follows it: the decayed weight is rounded to f32 before the
+// Adam update, as torch.optim.AdamW's p.mul_(1 - lr * wd) rounds it.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+struct adam_ext_scalars {
+    float step_size, inv_sqrt_bc2, b1, b2, eps, gscale, clip, decay_f, ema_decay, one_minus_d;
+    int ema_warmup;
+};
+
+// DECAY 0: none, 1: every element, 2: the elements whose bit is set in `bits`.  `ctl` (guarded or not) is uniform over the launch.
+template <int DECAY, bool EMA>
+__global__ __launch_bounds__(256) void adam_ext_kernel(float* p, const float* g, float* m, float* v, bf16* pb, float* ema,
+                                                       const uint8_t* bits, int64_t n, adam_ext_scalars s,
+                                                       const pa_grad_guard_ctl* ctl) {
+    float step_size = s.step_size, inv_sqrt_bc2 = s.inv_sqrt_bc2, coef = 1.f, omd = s.one_minus_d;
+    if (ctl) {
+        if (ctl->apply == 0) return;                                       // a refused step: no store at all, the EMA included
+        step_size = ctl->step_size; inv_sqrt_bc2 = ctl->inv_sqrt_bc2; coef = ctl->coef;
+        if (EMA) {                                                         // the host's expression, on the device's own step count
+            const double t = (double)ctl->applied;
+            double d = (double)s.ema_decay;
+            if (s.ema_warmup) {
+                const double w = (1.0 + t) / (10.0 + t);
+                d = w < d ? w : d;
+            }
+            omd = (float)(1.0 - d);
+        }
+    }
+    const float b1 = s.b1, b2 = s.b2, eps = s.eps, gscale = s.gscale, clip = s.clip, f = s.decay_f;
+    const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+    const int64_t n4 = n >> 2;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 pp = *reinterpret_cast<f32x4*>(p + e * 4);
+        f32x4 gg = *reinterpret_cast<const f32x4*>(g + e * 4);
+        f32x4 mm = *reinterpret_cast<f32x4*>(m + e * 4);
+        f32x4 vv = *reinterpret_cast<f32x4*>(v + e * 4);
+        f32x4 ee = {0.f, 0.f, 0.f, 0.f};
+        if (EMA) ee = *reinterpret_cast<f32x4*>(ema + e * 4);
+        unsigned nib = 0;                                                  // elements 4e .. 4e + 3 are one nibble of byte e >> 1
+        if (DECAY == 2) nib = (unsigned)bits[e >> 1] >> (((unsigned)e & 1u) * 4u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gj = gg[j] * gscale * coef;
+            gj = gj > clip ? clip : (gj < -clip ? -clip : gj);
+            mm[j] = __builtin_fmaf(omb1, gj, b1 * mm[j]);                  // (adam_guarded_kernel's forms, main loop and tail)
+            vv[j] = __builtin_fmaf(b2, vv[j], (omb2 * gj) * gj);
+            if (DECAY == 1) pp[j] = mul_rounded(pp[j], f);
+            if (DECAY == 2) pp[j] = ((nib >> j) & 1u) ? mul_rounded(pp[j], f) : pp[j];
+            pp[j] -= step_size * mm[j] / __builtin_fmaf(sqrtf(vv[j]), inv_sqrt_bc2, eps);
+            if (EMA) ee[j] = __builtin_fmaf(omd, pp[j] - ee[j], ee[j]);
+        }
+        *reinterpret_cast<f32x4*>(p + e * 4) = pp;
+        *reinterpret_cast<f32x4*>(m + e * 4) = mm;
+        *reinterpret_cast<f32x4*>(v + e * 4) = vv;
+        if (pb) st4<bf16>(pb + e * 4, pp);
+        if (EMA) *reinterpret_cast<f32x4*>(ema + e * 4) = ee;
+    }
+    // tail (n % 4)
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t e = (n4 << 2) + threadIdx.x;
+        float gj = g[e] * gscale * coef;
+        gj = gj > clip ? clip : (gj < -clip ? -clip : gj);
+        const float mj = __builtin_fmaf(b1, m[e], omb1 * gj);
+        const float vj = __builtin_fmaf(b2, v[e], (omb2 * gj) * gj);
+        m[e] = mj; v[e] = vj;
+        float pj = p[e];
+        if (DECAY == 1) pj = mul_rounded(pj, f);
+        if (DECAY == 2) pj = ((bits[e >> 3] >> ((unsigned)e & 7u)) & 1u) ? mul_rounded(pj, f) : pj;
+        pj -= step_size * mj / __builtin_fmaf(sqrtf(vj), inv_sqrt_bc2, eps);
+        p[e] = pj;
+        if (pb) pb[e] = (bf16)pj;
+        if (EMA) ema[e] = __builtin_fmaf(omd, pj - ema[e], ema[e]);
+    }
+}
+
 template <typename TD, typename TS>
 __global__ __launch_bounds__(256) void cast_kernel(TD* dst, const TS* src, int64_t n) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
@@ -1501,6 +1581,48 @@ extern "C" int pa_adam_step_guarded(float* p, const float* g, float* m, float* v
     if (reinterpret_cast<uintptr_t>(ctl) & 3) return PA_EALIGN;
     PA_LAUNCH(adam_guarded_kernel, dim3(grid_for(n >> 2, 256, 2048)), dim3(256), 0, ST(stream), p, g, m, v, (bf16*)p_bf16, n,
               b1, b2, eps, gscale, clip_value > 0.f ? clip_value : __builtin_inff(), ctl);
+    return 0;
+}
+
+static_assert(sizeof(pa_adam_ext_args) == 112, "pa_adam_ext_args is 112 bytes (plankassembly_amd/_lib.py mirrors it)");
+extern "C" int64_t pa_adam_ext_args_bytes(void) { return (int64_t)sizeof(pa_adam_ext_args); }
+
+extern "C" int pa_adam_step_ext(const pa_adam_ext_args* a, void* stream) {
+    if (!a || !a->p || !a->g || !a->m || !a->v || a->n <= 0 || !(a->clip_value >= 0.f)) return PA_EINVAL;
+    if (!(a->weight_decay >= 0.f && a->weight_decay < __builtin_inff())) return PA_EINVAL;
+    if (!(a->ema_decay >= 0.f && a->ema_decay < 1.f)) return PA_EINVAL;
+    if (!a->ctl && a->step < 1) return PA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(a->p) | reinterpret_cast<uintptr_t>(a->g) | reinterpret_cast<uintptr_t>(a->m) |
+         reinterpret_cast<uintptr_t>(a->v) | reinterpret_cast<uintptr_t>(a->ema)) & 15) return PA_EALIGN;
+    if (reinterpret_cast<uintptr_t>(a->ctl) & 3) return PA_EALIGN;
+    adam_ext_scalars s = {};
+    s.b1 = a->b1; s.b2 = a->b2; s.eps = a->eps; s.gscale = a->gscale;
+    s.clip = a->clip_value > 0.f ? a->clip_value : __builtin_inff();
+    s.decay_f = (float)(1.0 - (double)a->lr * (double)a->weight_decay);
+    s.ema_decay = a->ema_decay; s.ema_warmup = a->ema_warmup != 0;
+    if (!a->ctl) {                                     // unguarded: the step's scalars on the host, in double, rounded once
+        const double t = (double)a->step;
+        const double bc1 = 1.0 - pow((double)a->b1, t), bc2 = 1.0 - pow((double)a->b2, t);
+        s.step_size = (float)((double)a->lr / bc1);
+        s.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+        double d = (double)a->ema_decay;
+        if (s.ema_warmup) {
+            const double w = (1.0 + t) / (10.0 + t);
+            d = w < d ? w : d;
+        }
+        s.one_minus_d = (float)(1.0 - d);
+    }
+    const int decay = a->weight_decay > 0.f ? (a->decay_bits ? 2 : 1) : 0;
+    const dim3 grid(grid_for(a->n >> 2, 256, 2048));
+#define PA_ADAM_EXT(D, E)                                                                                                      \
+    PA_LAUNCH((adam_ext_kernel<D, E>), grid, dim3(256), 0, ST(stream), a->p, a->g, a->m, a->v, (bf16*)a->p_bf16, a->ema,        \
+              a->decay_bits, a->n, s, a->ctl)
+    if (a->ema) {
+        if (decay == 2) PA_ADAM_EXT(2, true); else if (decay == 1) PA_ADAM_EXT(1, true); else PA_ADAM_EXT(0, true);
+    } else {
+        if (decay == 2) PA_ADAM_EXT(2, false); else if (decay == 1) PA_ADAM_EXT(1, false); else PA_ADAM_EXT(0, false);
+    }
+#undef PA_ADAM_EXT
     return 0;
 }
 

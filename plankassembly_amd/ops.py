@@ -415,6 +415,19 @@ def adam_step_guarded(p, g, m, v, ws, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, cl
                                          C.c_float(clip_value or 0.0), ctl, L.stream()), "pa_adam_step_guarded")
 
 
+def adam_step_ext(p, g, m, v, step=0, ws=None, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, clip_value=0.0,
+                  weight_decay=0.0, decay_bits=None, ema=None, ema_decay=0.0, ema_warmup=False, p_bf16=None):
+    """pa_adam_step_ext: Adam with decoupled weight decay (``decay_bits``: uint8 bitmask of the elements that decay, None: all)
+    and a weight EMA in the same pass.  ``ws`` (a guard workspace pa_grad_guard has just written): the guarded form, ``step``
+    ignored; else ``step`` >= 1 is this step's Adam step count."""
+    ad = lambda t: None if t is None else t.data_ptr()
+    a = L.AdamExtArgs(p=ad(p), g=ad(g), m=ad(m), v=ad(v), p_bf16=ad(p_bf16), ema=ad(ema), decay_bits=ad(decay_bits),
+                      n=p.numel(), lr=lr, b1=b1, b2=b2, eps=eps, gscale=gscale, clip_value=clip_value or 0.0,
+                      weight_decay=weight_decay, ema_decay=ema_decay, step=int(step), ema_warmup=int(bool(ema_warmup)),
+                      ctl=None if ws is None else ws.data_ptr() + L.GRAD_GUARD_CTL_OFFSET)
+    L.check(L.lib().pa_adam_step_ext(C.byref(a), L.stream()), "pa_adam_step_ext")
+
+
 def cast(src, dtype):
     dst = torch.empty(src.shape, dtype=dtype, device=src.device)
     L.check(L.lib().pa_cast(L.ptr(dst), L.dt(dst), L.ptr(src), L.dt(src), C.c_int64(src.numel()), L.stream()),

@@ -14,6 +14,7 @@ so the reference's published checkpoints load and ours load in the reference.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import sys
@@ -84,6 +85,7 @@ class Trainer(torch.nn.Module):
         self.global_step = 0
         self._logged = {}
         self.optimizer_kwargs = {}             # FusedAdam's guard arguments, from the `trainer:` block (optimizer_options)
+        self.recipe = recipe_options(self.hparams_dict)  # weight decay / LR schedule / EMA keys of the hparams, validated
 
     # ------------------------------------------------------------------ logging (self.log of Lightning)
     def log(self, name, value, **kw):
@@ -221,7 +223,15 @@ class Trainer(torch.nn.Module):
     def configure_optimizers(self):
         from .optim import FusedAdam
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
-        return {"optimizer": FusedAdam(self.model, lr=self.cfg.LR, grad_scale=1.0 / world, **self.optimizer_kwargs)}
+        return {"optimizer": FusedAdam(self.model, lr=self.cfg.LR, grad_scale=1.0 / world, **self.optimizer_kwargs,
+                                       **self.recipe["optimizer"])}
+
+    def scheduled_lr(self, base_lr, step, total_steps):
+        """The learning rate of optimizer step ``step`` (0-based count of attempted steps = ``global_step``)."""
+        from .optim import lr_factor
+        sch = self.recipe["schedule"]
+        total = sch["total_steps"] if sch["total_steps"] is not None else int(total_steps)
+        return base_lr * lr_factor(sch["kind"], int(step), sch["warmup_steps"], total, sch["min_ratio"])
 
     # ------------------------------------------------------------------ checkpoints (Lightning-shaped)
     def checkpoint(self, epoch, optimizer=None, best_score=None, steps_this_epoch=0, best_path="", last_path="",
@@ -244,6 +254,16 @@ class Trainer(torch.nn.Module):
         if optimizer is not None:
             ck["optimizer_states"] = [optimizer.torch_state_dict() if hasattr(optimizer, "torch_state_dict")
                                       else optimizer.state_dict()]
+            ema = optimizer.ema_state_dict() if hasattr(optimizer, "ema_state_dict") else None
+            if ema is not None:                # the raw weights stay in `state_dict` (exact resume); the EMA travels beside them
+                ck["ema_state_dict"] = {"model." + k: v for k, v in ema.items()}
+                ck["ema_updates"] = int(optimizer.ema_updates)
+            if self.recipe["schedule"]["kind"] != "constant" and hasattr(optimizer, "base_lr"):
+                # one record in the shape of torch.optim.lr_scheduler.LambdaLR.state_dict(); _last_lr: the rate of the NEXT step
+                total = getattr(self, "lr_total_steps", 0)
+                ck["lr_schedulers"] = [{"last_epoch": self.global_step, "_step_count": self.global_step + 1,
+                                        "base_lrs": [optimizer.base_lr],
+                                        "_last_lr": [self.scheduled_lr(optimizer.base_lr, self.global_step, total)]}]
         return ck
 
     @staticmethod
@@ -261,16 +281,25 @@ class Trainer(torch.nn.Module):
             print(f"[plankassembly_amd] WARNING: unpickling {path} without restrictions (PLANK_TRUST_CHECKPOINT=1)")
             return torch.load(path, map_location="cpu", weights_only=False)
 
-    def load_checkpoint(self, path, optimizer=None):
-        """Weights always; with ``optimizer`` also the Adam moments / step, epoch and global_step (what Lightning's
-        ``fit --ckpt_path`` resumes).  Returns the checkpoint dict."""
+    def load_checkpoint(self, path, optimizer=None, use_ema=False):
+        """Weights always; with ``optimizer`` also the Adam moments / step, the EMA, the schedule record, epoch and global_step
+        (what Lightning's ``fit --ckpt_path`` resumes).  ``use_ema`` (without ``optimizer``): the weights loaded are the file's
+        ``ema_state_dict`` when it has one.  Returns the checkpoint dict."""
         from . import lightning_state as LS
         ck = self._read_checkpoint_file(path)
         sd = ck.get("state_dict", ck)
-        sd = {(k[6:] if k.startswith("model.") else k): v for k, v in sd.items()}
-        self.model.load_state_dict(sd)
+        if optimizer is None and use_ema and ck.get("ema_state_dict"):
+            sd = ck["ema_state_dict"]
+        strip = lambda d: {(k[6:] if k.startswith("model.") else k): v for k, v in d.items()}
+        self.model.load_state_dict(strip(sd))
         if optimizer is not None and ck.get("optimizer_states"):
             optimizer.load_state_dict(ck["optimizer_states"][0])
+        if optimizer is not None and ck.get("ema_state_dict") and getattr(optimizer, "ema_decay", None) is not None:
+            optimizer.load_ema_state_dict(strip(ck["ema_state_dict"]), int(ck.get("ema_updates", 0)))
+        if optimizer is not None and ck.get("lr_schedulers") and hasattr(optimizer, "base_lr"):
+            rec = ck["lr_schedulers"][0]
+            optimizer.base_lr = float(rec["base_lrs"][0])
+            optimizer.param_groups[0]["lr"] = float(rec["_last_lr"][0])
         if optimizer is not None:
             self.global_step = int(ck.get("global_step", 0))
             self.resume_epoch = LS.epochs_done_of(ck)
@@ -360,6 +389,71 @@ def optimizer_options(tkw):
     return kw, raise_on_skip
 
 
+def _number(key, v, lo, hi, hi_open=False):
+    ok = not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and lo <= v and (v < hi if hi_open else v <= hi)
+    if not ok:
+        raise ValueError(f"{key} must be a number in [{lo}, {hi}{')' if hi_open else ']'}, got {v!r}")
+    return float(v)
+
+
+def _count(key, v, lo=0):
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+        raise ValueError(f"{key} must be an integer >= {lo}, got {v!r}")
+    return v
+
+
+def _bool(key, v):
+    if not isinstance(v, bool):
+        raise ValueError(f"{key} must be a bool, got {v!r}")
+    return v
+
+
+def recipe_options(hparams):
+    """The training-recipe keys of the hparams (next to ``LR``), validated -> {"optimizer": FusedAdam keyword arguments,
+    "schedule": {kind, warmup_steps, total_steps, min_ratio}, "eval_ema": bool}.  All off by default.
+
+    ``WEIGHT_DECAY`` (0) with ``NO_DECAY`` ``1d`` (default: biases and LayerNorm parameters do not decay) or ``none``;
+    ``LR_SCHEDULE`` ``constant`` (default) / ``warmup`` / ``cosine`` / ``inverse_sqrt`` with ``WARMUP_STEPS`` (0), ``LR_TOTAL_STEPS``
+    (null: the run's own length - max_steps, else max_epochs * batches per epoch) and ``MIN_LR_RATIO`` (0), see optim.lr_factor;
+    ``EMA_DECAY`` (null: off) with ``EMA_WARMUP`` (false); ``EVAL_EMA`` (default: true exactly when EMA_DECAY is set): validation,
+    and with it the best-checkpoint choice, and ``test --ckpt_path`` use the averaged weights."""
+    from .optim import LR_SCHEDULES, NO_DECAY_MODES, lr_factor
+    get = lambda k, d=None: d if hparams.get(k) is None else hparams.get(k)
+    wd = _number("WEIGHT_DECAY", get("WEIGHT_DECAY", 0.0), 0.0, float("inf"), hi_open=True)
+    no_decay = get("NO_DECAY", "1d")
+    if no_decay not in NO_DECAY_MODES:
+        raise ValueError(f"NO_DECAY must be one of {NO_DECAY_MODES}, got {no_decay!r}")
+    kind = get("LR_SCHEDULE", "constant")
+    if kind not in LR_SCHEDULES:
+        raise ValueError(f"LR_SCHEDULE must be one of {LR_SCHEDULES}, got {kind!r}")
+    warmup = _count("WARMUP_STEPS", get("WARMUP_STEPS", 0))
+    total = hparams.get("LR_TOTAL_STEPS")
+    if total is not None:
+        total = _count("LR_TOTAL_STEPS", total, 1)
+    min_ratio = _number("MIN_LR_RATIO", get("MIN_LR_RATIO", 0.0), 0.0, 1.0)
+    lr_factor(kind, 0, warmup, total if total is not None else warmup + 1, min_ratio)     # (the schedule's own argument rules)
+    ema = hparams.get("EMA_DECAY")
+    if ema is not None:
+        ema = _number("EMA_DECAY", ema, 0.0, 1.0, hi_open=True)
+    ema_warmup = _bool("EMA_WARMUP", get("EMA_WARMUP", False))
+    eval_ema = _bool("EVAL_EMA", get("EVAL_EMA", ema is not None))
+    if eval_ema and ema is None:
+        raise ValueError("EVAL_EMA: true needs EMA_DECAY")
+    return {"optimizer": {"weight_decay": wd, "no_decay": no_decay, "ema_decay": ema, "ema_warmup": ema_warmup},
+            "schedule": {"kind": kind, "warmup_steps": warmup, "total_steps": total, "min_ratio": min_ratio},
+            "eval_ema": eval_ema}
+
+
+def ema_checkpoint(ck):
+    """A copy of checkpoint dict ``ck`` whose ``state_dict`` is the EMA: the file to hand to the reference, which knows no
+    ``ema_state_dict`` key.  The raw weights are dropped from the copy, so it is for evaluation, not for an exact resume."""
+    if "ema_state_dict" not in ck:
+        raise KeyError("ema_checkpoint(): the checkpoint has no ema_state_dict (written with EMA_DECAY set)")
+    out = {k: v for k, v in ck.items() if k not in ("ema_state_dict", "ema_updates")}
+    out["state_dict"] = {k: v.clone() for k, v in ck["ema_state_dict"].items()}
+    return out
+
+
 def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
     """The part of ``pl.Trainer.fit/test`` the reference relies on."""
     seed, tkw, hparams = load_cli_config(config)
@@ -391,7 +485,7 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
     dev = torch.device("cuda", local)
     module.model.to(dev)
     if ckpt_path and subcommand == "test":
-        module.load_checkpoint(ckpt_path)
+        module.load_checkpoint(ckpt_path, use_ema=module.recipe["eval_ema"])
     if subcommand == "test":
         module.model.eval()
         with torch.no_grad():
@@ -422,6 +516,9 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
     every = int(tkw.get("check_val_every_n_epoch", 1))
     max_steps = int(tkw.get("max_steps", -1))
     loader = module.train_dataloader()
+    scheduled = module.recipe["schedule"]["kind"] != "constant"
+    module.lr_total_steps = max_steps if max_steps > 0 else max_epochs * (len(loader) if hasattr(loader, "__len__") else 0)
+    eval_weights = opt.ema_weights if module.recipe["eval_ema"] else contextlib.nullcontext
     for epoch in range(start_epoch, max_epochs):
         if 0 < max_steps <= module.global_step:            # a resumed run whose epoch was cut by max_steps: nothing left to do
             break
@@ -437,6 +534,8 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
             opt.zero_grad()
             loss = module.training_step(batch, i)
             loss.backward()
+            if scheduled:                                  # keyed on the steps attempted so far: host-known, no read-back
+                opt.param_groups[0]["lr"] = module.scheduled_lr(opt.base_lr, module.global_step, module.lr_total_steps)
             opt.step()
             module.global_step += 1
             steps_here += 1
@@ -445,6 +544,7 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
                 break
         l, a = module._train_stats
         module.log("train/loss", l); module.log("train/accuracy", a)
+        module.log("train/lr", opt.param_groups[0]["lr"])      # the rate of the epoch's last step
         torch.cuda.synchronize()
         if getattr(opt, "guarded", False):                 # the guard's one read-back, where the loop synchronises anyway
             gs = opt.guard_stats()
@@ -467,7 +567,7 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
                 torch.save(module.checkpoint(epoch, opt, best if best >= 0 else None, steps_here, best_file, last,
                                              epoch_finished=finished), last)
             module.model.eval()
-            with torch.no_grad():
+            with torch.no_grad(), eval_weights():
                 for i, batch in enumerate(module.val_dataloader()):
                     module.validation_step(_to_device(batch, dev, module.model), i)
             module.validation_epoch_end()
