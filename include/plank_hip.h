@@ -710,12 +710,26 @@ int pa_model_tensor(pa_model* m, int32_t which, void** ptr, int64_t* numel);
 int64_t pa_decode_ws_bytes(pa_model* m, int32_t B, int32_t S, int32_t Tmax);
 int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t Tmax, void* stream);
 int pa_decode_step(pa_model* m, void* stream);
-/* One step of TWO half-batches of the same decode (two handles over the same parameters, each after its own
- * pa_decode_begin) on two streams, attention launches strictly alternating between them so that one lane's K/V streaming
- * overlaps the other lane's latency-bound launches.  Under stream capture stream_b must already belong to stream_a's
- * capture (fork before, join after).  Host-side scheduling only: each lane computes exactly what pa_decode_step computes.
- * Experimental: on MI355X / ROCm 7.2 the cross-queue event edges cost more than the overlap. */
-int pa_decode_step_pair(pa_model* a, pa_model* b, void* stream_a, void* stream_b);
+/* Dry run of the decode dispatch: the status pa_decode_begin / pa_decode_ws_bytes would answer for a handle of `cfg` with a batch of B
+ * rows, memory length S and Tmax steps and, when that is 0, the forms the step takes and the bytes it needs.  Made by the same pure
+ * function the real calls run, under the same PLANK_DECODE_* switches (read once per process).  It needs no handle and no GPU and
+ * launches nothing.  Two half-batch lanes are two handles, each planned for its own rows. */
+typedef struct {
+    int32_t fold;               /* LayerNorm folded into the Linear that consumes it */
+    int32_t f32res;             /* bf16 step with an f32 residual stream */
+    int32_t mq;                 /* absorbed cross-attention: the step attends over the memory rows, no per-layer K / V caches */
+    int32_t mq_contract;        /* W_v as its own launch + the ordinary out-projection behind the absorbed cross-attention */
+    int32_t mq_self;            /* exact f32: the self-attention absorbed too (row cache of the layer inputs) */
+    int32_t mq_self_bf;         /* bf16: the same */
+    int32_t parts_cross, parts_self;    /* range blocks per row of the absorbed cross- / self-attention launch; 0 = no such launch */
+    int32_t mq_nt, mq_swap, mq32_w8;    /* kernel variants of the absorbed launches: PLANK_DECODE_MQ_NT / _MQ_SWAP / _MQ32_W8 */
+    int32_t pad_;
+    int64_t mq_sp_bytes;        /* scratch of the range blocks inside the workspace */
+    int64_t ws_bytes;           /* = pa_decode_ws_bytes(handle of cfg, B, S, Tmax) */
+    int64_t scr_row;            /* beam reorder scratch per hypothesis row (B = rows; independent of K and of the row count), or a
+                                 * negative PA_E* code where pa_decode_beam_ws_bytes answers with one */
+} pa_decode_plan_info;
+int pa_decode_plan(const pa_model_cfg* cfg, int32_t B, int32_t S, int32_t Tmax, pa_decode_plan_info* out);
 int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void** first_end, void** t_dev);
 /* Beam search over the same step.  K beams per drawing, 1 <= K <= PA_BEAM_MAX: the caller runs the encoder and
  * pa_decode_begin on the batch with every drawing repeated K times (row b*K + k is beam k of drawing b), then switches the decode to
@@ -726,8 +740,7 @@ int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void** first_en
  *     become the new beams; a beam that emits END is finished and frozen;
  *   - rows whose parent is another row take the parent's history (self-attention caches, hidden-state cache, tokens, attach).
  * Everything is read from device memory: the step still captures into one hipGraph.  K = 1 gives the greedy tokens, with PAD / -1
- * after a row's first END.  pa_decode_step_pair returns PA_EINVAL for a decode in beam mode (beams run as one lane); the next
- * pa_decode_begin returns the handle to greedy mode.
+ * after a row's first END.  The next pa_decode_begin returns the handle to greedy mode.
  *   pa_decode_beam_ws_bytes: bytes of the beam workspace for `rows` = B*K rows (the batch pa_decode_begin was given), memory length S
  *     and Tmax (the same values as pa_decode_ws_bytes); PA_EINVAL for K outside [1, PA_BEAM_MAX] or rows not a multiple of K.
  *   pa_decode_beam_begin: after pa_decode_begin, lays out `ws` (256-byte aligned, pa_decode_beam_ws_bytes bytes) and resets the beam
@@ -753,8 +766,8 @@ int pa_decode_beam_buffers(pa_model* m, void** scores, void** parents, void** fi
  *     unfiltered: the model's log-likelihood of the sample); a row that has emitted END is frozen (PAD, attach -1, score + 0).
  * Everything is read from device memory, the parameters included: the step captures into one hipGraph, and pa_decode_sample_set
  * changes seed / temperature / top_k / top_p for the next steps without a new capture.  The same parameters give bitwise the same
- * samples on every run.  top_k = 1 gives the greedy tokens up to each row's first END.  pa_decode_step_pair returns PA_EINVAL for a
- * decode in sampling mode; pa_decode_begin returns the handle to greedy mode; pa_decode_beam_begin and pa_decode_sample_begin replace
+ * samples on every run.  top_k = 1 gives the greedy tokens up to each row's first END.
+ * pa_decode_begin returns the handle to greedy mode; pa_decode_beam_begin and pa_decode_sample_begin replace
  * each other's mode (the last one called wins).  Vocabularies above 2048 entries: PA_ESHAPE.
  *   pa_sample_params: seed; n_per_drawing = N; temperature > 0 and finite; top_k >= 0 (0 = off); 0 < top_p <= 1 (1 = off).
  *   pa_decode_sample_ws_bytes: bytes of the sampling workspace for `rows` = B*N rows (the batch pa_decode_begin was given).
@@ -798,7 +811,7 @@ int pa_decode_sample_buffers(pa_model* m, void** scores);
  * from beam 0, and prefix_score / prefix_lp of the drawing are those of its row b*K.  Rows with t >= plen[r] behave exactly as without
  * a table, in the same step.  Without pa_decode_prefix_begin every mode launches the kernels it launched before and gives the same
  * bits, and a step with a table has the same launches.  Everything is read from device memory: the step captures into one hipGraph and
- * a new table needs no new capture.  pa_decode_begin clears the prefix; pa_decode_step_pair returns PA_EINVAL with a prefix set.
+ * a new table needs no new capture.  pa_decode_begin clears the prefix.
  *   pa_decode_prefix_ws_bytes: bytes of the prefix workspace for `rows` rows and Tmax positions.
  *   pa_decode_prefix_begin: after pa_decode_begin and after any pa_decode_beam_begin / pa_decode_sample_begin.  plen int32 [rows],
  *     ptok / patt int64 [rows][Tmax] are DEVICE pointers (positions t >= plen[r] are not read by the step); a kernel on `stream` copies
@@ -828,7 +841,7 @@ int pa_decode_prefix_buffers(pa_model* m, void** prefix_score, void** prefix_lp)
  * positions (pa_decode_prefix_*) are not filtered.  Should every allowed candidate have p == 0 in f32, beam rank 0 and the sampler write
  * the window's lowest token (END for the END-only window) with log p = -inf; nothing is read out of bounds and no loop depends on it.
  * The parameters travel as kernel arguments: a captured step depends on them (capture again after a change).  Host state only, no
- * launch.  pa_decode_begin clears the constraint; pa_decode_step_pair returns PA_EINVAL with one set.
+ * launch.  pa_decode_begin clears the constraint.
  *   pa_decode_constraint_set: after pa_decode_begin; p == NULL clears.  PA_EINVAL for a decode that was not begun, min_planks < 0,
  *     max_planks < max(min_planks, 1), n_val < 2 or n_val above the vocabulary. */
 typedef struct {

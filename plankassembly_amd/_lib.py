@@ -82,6 +82,14 @@ class AttnPlanInfo(C.Structure):
                 ("parts_kv", C.c_int32), ("sp_slots", C.c_int32), ("launch", AttnPlanLaunch * 3)]
 
 
+class DecodePlanInfo(C.Structure):
+    """include/plank_hip.h pa_decode_plan_info: what pa_decode_plan (the dry run of the decode dispatch) reports."""
+    _fields_ = [("fold", C.c_int32), ("f32res", C.c_int32), ("mq", C.c_int32), ("mq_contract", C.c_int32), ("mq_self", C.c_int32),
+                ("mq_self_bf", C.c_int32), ("parts_cross", C.c_int32), ("parts_self", C.c_int32),
+                ("mq_nt", C.c_int32), ("mq_swap", C.c_int32), ("mq32_w8", C.c_int32), ("pad_", C.c_int32),
+                ("mq_sp_bytes", C.c_int64), ("ws_bytes", C.c_int64), ("scr_row", C.c_int64)]
+
+
 class GroupDesc(C.Structure):
     _fields_ = [("idx", C.c_void_p), ("rowmap", C.c_void_p),
                 ("n", C.c_int32), ("rows", C.c_int32), ("kind", C.c_int32), ("T", C.c_int32), ("dof", C.c_int32),
@@ -225,10 +233,10 @@ def lib():
             "pa_model_train_bwd": (I, [P, I, I, F, P]),
             "pa_model_grad_lag": (I, [P]),
             "pa_model_tensor": (I, [P, I, P, P]),
+            "pa_decode_plan": (I, [P, I, I, I, P]),
             "pa_decode_ws_bytes": (I64, [P, I, I, I]),
             "pa_decode_begin": (I, [P, P, I64, I, P]),
             "pa_decode_step": (I, [P, P]),
-            "pa_decode_step_pair": (I, [P, P, P, P]),
             "pa_decode_buffers": (I, [P, P, P, P, P]),
             "pa_decode_beam_ws_bytes": (I64, [P, I, I, I, I]),
             "pa_decode_beam_begin": (I, [P, I, P, I64, P]),

@@ -29,8 +29,13 @@ struct BeamCopy {
     BeamSeg seg[BEAM_MAX_SEG];
 };
 
+// What plan_decode() decides for a decode of B rows over S memory positions and Tmax steps: the fields pa_decode_plan reports
+// (include/plank_hip.h; the rule and the measurements: plan_decode) and the status pa_decode_begin / pa_decode_ws_bytes answer with.
+struct DecodePlan : pa_decode_plan_info { int status = 0; };
+
 struct DecodeLayout {
     int B = 0, S = 0, Tmax = 0;
+    DecodePlan plan{};                         // of this (B, S, Tmax): the layout, pa_decode_begin, the beam reorder and the step read it
     std::vector<void*> cross_k, cross_v, self_k, self_v;   // per decoder layer, per-head contiguous: [B][H][S|Tmax][dh]
     void* kv_tmp;                              // [B*S][2d] projection output before the per-head re-layout
     void *hid_cache, *x, *qkv, *ao, *z, *y, *q, *ff, *pfeat, *h;
@@ -39,33 +44,28 @@ struct DecodeLayout {
     uint8_t* kpm;                              // copy of input_mask: the captured step must not depend on batch tensors
     int32_t* cu;                               // copy of the packed-row offsets (NULL: dense memory + kpm)
     int32_t* cu_store;
-    std::vector<hipEvent_t> pair_ev;           // pa_decode_step_pair: [2][2 * n_dec] attention-done events (lane A's layout owns them)
     // LayerNorm folded into the Linear that consumes it (bf16; pa_gemm_norm_a): per decoder layer, for the three Linears whose
     // input is a sublayer's LayerNorm output - [0] self-attention in_proj (norm3 of the layer before), [1] the cross-attention
     // query projection (norm1), [2] linear1 (norm2): gamma-scaled weight, u, v (include/plank_hip.h)
-    bool fold = false;
     void* z2 = nullptr;                        // second pre-norm buffer (z of the cross-attention block)
     std::vector<void*> fw[3]; std::vector<float*> fu[3], fv[3];
     // f32 residual stream of the bf16 step (PLANK_DECODE_F32_RESID, default on with `fold`): x / y / z / z2 hold f32 rows, zb / z2b /
     // xb / hb their bf16 copies = the matrix operands of the Linears that read them, hf = decoder.norm's output in f32 (vocabulary head).
     // Everything else of the step - weights, Q / K / V, the caches, attention outputs, FFN hidden rows - stays bf16.
-    bool f32res = false;
     void *zb = nullptr, *z2b = nullptr, *xb = nullptr;
     float* hf = nullptr;
     // Absorbed ("multi-query") cross-attention (csrc/decode_mq.h; bf16, d_model 512, <= 8 heads, with `fold`): the step attends over a
     // copy of the encoder output rows (`mem`) instead of per-layer K / V caches.  qt / ctx: [B][H][d] query / context rows of a step;
-    // wo_t / bo_t per layer: W_o,h W_v,h as one [d][H d] bf16 matrix and b_o + W_o b_v.
-    bool mq = false;
-    bool mq_self = false;                      // exact f32: the SELF-attention absorbed too - self_k[i] caches the layer-input rows [B][Tmax][d]
+    // wo_t / bo_t per layer: W_o,h W_v,h as one [d][H d] bf16 matrix and b_o + W_o b_v; with `mq_contract` (exact f32, dh 64) W_v is its
+    // own launch in front of the ordinary out-projection instead (decode_mq.h).
+    // `mq_self` (exact f32): the SELF-attention absorbed too - self_k[i] caches the layer-input rows [B][Tmax][d]
     std::vector<void*> wvt_self;               // per layer: head-transposed W_v of the self-attention (mq_contract_v_kernel)
-    bool mq_contract = false;                  // exact f32, dh 64: W_v as its own launch + the ordinary out-projection instead of wo_t (decode_mq.h)
     void *mem = nullptr, *qt = nullptr, *ctx = nullptr;
     std::vector<void*> wo_t; std::vector<float*> bo_t;
-    // bf16 step (f32 residual stream), round 6: the SELF-attention absorbed as well - self_k[i] caches the layer-input rows (bf16), the
-    // out-projection runs on the context rows with W~o,self = W_o,h W_v,h (wo_ts / bo_ts); self_v is not read
-    bool mq_self_bf = false;
+    // `mq_self_bf` (bf16 step, f32 residual stream), round 6: the SELF-attention absorbed as well - self_k[i] caches the layer-input rows
+    // (bf16), the out-projection runs on the context rows with W~o,self = W_o,h W_v,h (wo_ts / bo_ts); self_v is not read
     std::vector<void*> wo_ts; std::vector<float*> bo_ts;
-    void* mq_sp = nullptr; int64_t mq_sp_bytes = 0;   // range blocks of the absorbed cross-attention (decode_mq.h): tickets (zero between launches) + partials
+    void* mq_sp = nullptr;                     // range blocks of the absorbed launches (decode_mq.h; plan.mq_sp_bytes): tickets (zero between launches) + partials
     // beam search (pa_decode_beam_begin; 0 = greedy): K beams per drawing over the B rows, state in the caller's beam workspace
     int beamK = 0;
     float *bm_score = nullptr, *bm_clp = nullptr;
@@ -929,21 +929,10 @@ int linear(pa_model* m, const void* A, const void* W, const float* bias, void* C
     return pa_gemm(&g, st);
 }
 
-// y = LayerNorm(R + A W^T + bias): pa_gemm into `z` followed by pa_layernorm_fwd.  PLANK_DECODE_FUSE_LN=1 swaps in the
-// one-launch row-block kernel (pa_gemm_ln; bf16, d_model 512, K = 512) to reproduce the measurement that keeps it OFF:
-// at 256 rows it is 8 blocks, each pulling the layer's whole 512 KB weight - cold, the step cycles through 38 MB of
-// them - with ~100 KB in flight: 1.317 ms / step against 1.239 for the two launches (32 blocks x 64 KB each).
+// y = LayerNorm(R + A W^T + bias): pa_gemm into `z` followed by pa_layernorm_fwd
 int linear_ln(pa_model* m, const void* A, const void* W, const float* bias, const void* R, void* z, void* y, const float* gamma,
               const float* beta, float eps, int M, int K, void* st) {
     const pa_model_cfg& c = m->cfg;
-    static const bool fuse = getenv("PLANK_DECODE_FUSE_LN") && atoi(getenv("PLANK_DECODE_FUSE_LN")) != 0;
-    if (fuse && c.dtype == PA_BF16 && c.d_model == 512 && K == 512 && M <= pa_gemm_ln_max_rows()) {
-        pa_gemm_ln_args g; memset(&g, 0, sizeof(g));
-        g.A = A; g.W = W; g.bias = bias; g.R = R; g.Z = nullptr; g.Y = y; g.gamma = gamma; g.beta = beta;
-        g.M = M; g.N = c.d_model; g.K = K; g.lda = K; g.ldw = K; g.ldr = c.d_model; g.ldz = c.d_model; g.ldy = c.d_model;
-        g.eps = eps;
-        return pa_gemm_ln(&g, st);
-    }
     RC(linear(m, A, W, bias, z, c.d_model, M, c.d_model, K, 0, R, -1, st));
     return pa_layernorm_fwd(y, z, gamma, beta, m->dec->mean, m->dec->rstd, M, c.d_model, eps, c.dtype, st);
 }
@@ -985,85 +974,75 @@ int linear_norm_a32(pa_model* m, const void* Zb, const float* Zf, const void* Wf
     return pa_gemm_norm_a(&g, &x, st);
 }
 
-// Which forms the step takes (shared by the workspace layout and pa_decode_begin).
-// fold: LayerNorm folded into its consumer Linear (bf16 decode): 17 LayerNorm launches fewer per step.
-// On the ring kernel (gemm3s_kernel's prologue statistics pass) this was MEASURED NULL on MI355X (B 256, 1024 steps, one lane:
-// 1.228 ms / step folded against 1.210 - the statistics pass pays the memory round trips the LayerNorm launch paid).  On
-// gemm_skinny_kernel the Z tile is resident in LDS and the statistics cost no round trip: 1.072 against 1.089 ms / step.  So: on by
-// default exactly where pa_gemm_norm_a takes the skinny kernel (d_model 512, at most 512 rows); PLANK_DECODE_FOLD_LN=0 / 1 forces.
-// The exact-f32 step folds too since round 4 (pa_ln_fold_weights_f32 + the f32 skinny kernel with the statistics taken from
-// the rows themselves): 17 LayerNorm launches fewer per step - measured +0.5 % only (B 256: 1.995 vs 2.005 ms / step; the folded
-// Linears re-read their rows for the statistics), token-exact against the reference in every decode test.  d_model 512, <= 512 rows.
-// f32res: f32 residual stream inside the bf16 step (see DecodeLayout::f32res): on wherever every Linear of the step takes the skinny
-// kernel (d_model 512, at most 512 rows).  tests/bf16_decode_sim.py / profiles/r04_bf16_decode_rounding_sim.txt: exact-prefix
-// agreement with the f32 tokens 0.40 -> 0.63-0.70 on 32 rows x 128 steps.  PLANK_DECODE_F32_RESID=0 restores the all-bf16 step.
-// mq: absorbed cross-attention (csrc/decode_mq.h) wherever the fold is on, with at most 8 heads; PLANK_DECODE_MQ=0 (bf16) /
-// PLANK_DECODE_MQ_F32=0 (exact f32) restore the per-layer K / V caches.
-struct DecodeModes { bool fold, f32res, mq; };
-DecodeModes decode_modes(const pa_model_cfg& c, int B, int S) {
-    const int d = c.d_model;
-    static const int fold_force = getenv("PLANK_DECODE_FOLD_LN") ? atoi(getenv("PLANK_DECODE_FOLD_LN")) : -1;
-    static const int f32res_env = getenv("PLANK_DECODE_F32_RESID") ? atoi(getenv("PLANK_DECODE_F32_RESID")) : 1;
-    static const int mq_env = getenv("PLANK_DECODE_MQ") ? atoi(getenv("PLANK_DECODE_MQ")) : 1;
-    static const int mq32_env = getenv("PLANK_DECODE_MQ_F32") ? atoi(getenv("PLANK_DECODE_MQ_F32")) : 1;
-    const bool fold_env = fold_force >= 0 ? fold_force != 0 : (d == 512 && B <= 512);
-    DecodeModes r;
-    r.fold = fold_env && c.dtype == PA_BF16 && d % 64 == 0 && c.d_ff % 32 == 0 && c.d_ff >= d && (size_t)((B + 63) / 64) * ((3 * d + 63) / 64) <= 512;
-    if (c.dtype == PA_F32) r.fold = fold_env && d == 512 && B <= 512 && c.d_ff % 32 == 0 && c.d_ff >= d;   // (N < K: pa_gemm_norm_a's f32 form cannot materialise y - ADVICE r4)
-    r.f32res = r.fold && c.dtype == PA_BF16 && f32res_env != 0 && d == 512 && B <= 512 && c.d_ff % 512 == 0;
-    r.mq = r.fold && (c.dtype == PA_BF16 ? mq_env != 0 : mq32_env != 0) && d == MQ_D && B <= 512 && c.n_head >= 1 && c.n_head <= MQ_MAXH && d % c.n_head == 0 && S <= (c.dtype == PA_F32 ? 16000 : MQ_MAXS);     // (f32: launch_cross_mq32 keeps 16 KB of partial-score slots beside the ring)
-    return r;
+// =====================================================================================================
+// Host side of the step: decode_switches() reads every switch once, plan_decode() - a pure function - turns (cfg, B, S, Tmax) into the
+// forms the step takes and the bytes it needs; the layout, pa_decode_begin, the beam reorder and the step read that one value
+// (DecodeLayout::plan).  pa_decode_plan reports it without a handle or a launch (tests/test_decode_plan_cpu.py pins it without a GPU).
+struct DecodeSwitches {
+    // step form
+    int fold_ln;           // PLANK_DECODE_FOLD_LN (unset = -1: on at d_model 512 and at most 512 rows): 0 / 1 force the LayerNorm fold off / on
+    int f32_resid;         // PLANK_DECODE_F32_RESID (1): 0 = the all-bf16 residual stream in the bf16 step
+    int mq;                // PLANK_DECODE_MQ (1): 0 = per-layer cross-attention K / V caches in the bf16 step
+    int mq_f32;            // PLANK_DECODE_MQ_F32 (1): the same for the exact-f32 step
+    int mq_contract;       // PLANK_DECODE_MQ_CONTRACT (unset = -1: exact f32 only): 0 / 1 force W_v as its own launch off / on (dh 64)
+    int mq_self;           // PLANK_DECODE_MQ_SELF (1): 0 = per-head self-attention K / V caches in the exact-f32 step
+    int mq_self_bf16;      // PLANK_DECODE_MQ_SELF_BF16 (unset = -1: B >= mq_self_minb): 0 never, 1 always absorb the bf16 self-attention
+    int mq_self_minb;      // PLANK_DECODE_MQ_SELF_MINB (200): fewest rows from which the bf16 self-attention is absorbed
+    // range blocks of the absorbed launches (decode_mq.h mq_parts)
+    int mq_parts;          // PLANK_DECODE_MQ_PARTS (0 = by rule): n > 0 forces n range blocks per row (at most 64), 1 = never
+    int mq_mint;           // PLANK_DECODE_MQ_MINT (8): fewest key tiles of a range block
+    // kernel variants of the absorbed launches
+    int mq_nt;             // PLANK_DECODE_MQ_NT (1): 0 = default-policy DMA instead of non-temporal (aux 2; measured in the step,
+                           //   B 256 x 1024: 0.958 vs 0.989 ms)
+    int mq_swap;           // PLANK_DECODE_MQ_SWAP (1): 0 = ds_bpermute row reductions instead of v_permlane*_swap
+    int mq32_w8;           // PLANK_DECODE_MQ32_W8 (1): 0 = the four-wave f32 kernel (one wave per SIMD) instead of eight waves with skewed halves
+};
+const DecodeSwitches& decode_switches() {
+    static const DecodeSwitches sw = [] {
+        auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+        DecodeSwitches s;
+        s.fold_ln = env("PLANK_DECODE_FOLD_LN", -1);
+        s.f32_resid = env("PLANK_DECODE_F32_RESID", 1);
+        s.mq = env("PLANK_DECODE_MQ", 1);
+        s.mq_f32 = env("PLANK_DECODE_MQ_F32", 1);
+        s.mq_contract = env("PLANK_DECODE_MQ_CONTRACT", -1);
+        s.mq_self = env("PLANK_DECODE_MQ_SELF", 1);
+        s.mq_self_bf16 = env("PLANK_DECODE_MQ_SELF_BF16", -1);
+        s.mq_self_minb = env("PLANK_DECODE_MQ_SELF_MINB", 200);
+        s.mq_parts = env("PLANK_DECODE_MQ_PARTS", 0);
+        s.mq_mint = env("PLANK_DECODE_MQ_MINT", 8);
+        s.mq_nt = env("PLANK_DECODE_MQ_NT", 1);
+        s.mq_swap = env("PLANK_DECODE_MQ_SWAP", 1);
+        s.mq32_w8 = env("PLANK_DECODE_MQ32_W8", 1);
+        return s;
+    }();
+    return sw;
 }
 
-// The self-attention form of the step (shared by pa_decode_begin and the beam workspace query, whose reorder copies what this form caches).
-struct StepForm { bool mq_contract, mq_self, mq_self_bf; };
-StepForm step_form(const pa_model_cfg& c, int B, int S, int Tmax) {
-    const int d = c.d_model;
-    const DecodeModes md = decode_modes(c, B, S);
-    StepForm r;
-    static const int contract_env = getenv("PLANK_DECODE_MQ_CONTRACT") ? atoi(getenv("PLANK_DECODE_MQ_CONTRACT")) : -1;
-    r.mq_contract = md.mq && d / c.n_head == 64 && (contract_env >= 0 ? contract_env != 0 : c.dtype == PA_F32);
-    // exact f32: the self-attention in the same form - the step caches the layer-input rows x_t instead of K and V (half the bytes of what is
-    // then the largest stream of the f32 step), q~ = W_k^T q, W_v behind the softmax (q . b_k cancels, b_v is added once).  PLANK_DECODE_MQ_SELF=0.
-    static const int self_env = getenv("PLANK_DECODE_MQ_SELF") ? atoi(getenv("PLANK_DECODE_MQ_SELF")) : 1;
-    r.mq_self = md.mq && r.mq_contract && c.dtype == PA_F32 && self_env != 0 && Tmax <= 16000;
-    // bf16 (round 6; needs the f32 residual stream's step form): pays from ~200 batch elements on - measured in one session, B 256 x 1024 steps:
-    // 0.969 -> 0.929 ms / step (264 k -> 276 k tokens/s; half the bytes of the self-attention stream against one more launch and a K = H d
-    // out-projection per layer); B 64: 0.557 -> 0.662, B 16: 0.476 -> 0.609 (profiles/r06_decode_self_absorbed.txt).
-    // PLANK_DECODE_MQ_SELF_BF16: 0 never, 1 always, unset = B >= PLANK_DECODE_MQ_SELF_MINB (200).
-    static const int self_bf_env = getenv("PLANK_DECODE_MQ_SELF_BF16") ? atoi(getenv("PLANK_DECODE_MQ_SELF_BF16")) : -1;
-    static const int self_bf_minb = getenv("PLANK_DECODE_MQ_SELF_MINB") ? atoi(getenv("PLANK_DECODE_MQ_SELF_MINB")) : 200;
-    r.mq_self_bf = md.mq && !r.mq_contract && c.dtype == PA_BF16 && md.f32res && d / c.n_head == 64 && Tmax <= MQ_MAXS &&
-                    (self_bf_env >= 0 ? self_bf_env != 0 : B >= self_bf_minb);
-    return r;
-}
-
-size_t dec_layout(pa_model* m, DecodeLayout* L, char* base, int B, int S, int Tmax) {
-    const pa_model_cfg& c = m->cfg;
+// The decode workspace for plan `pl`; base NULL is the size query (L then holds no pointers).
+size_t dec_layout(const pa_model_cfg& c, const DecodePlan& pl, DecodeLayout* L, char* base, int B, int S, int Tmax) {
     const size_t e = c.dtype == PA_BF16 ? 2 : 4, d = c.d_model, ff = c.d_ff;
-    const DecodeModes md = decode_modes(c, B, S);
     Arena a{base, 0};
     L->B = B; L->S = S; L->Tmax = Tmax;
     L->cross_k.assign(c.n_dec, nullptr); L->cross_v.assign(c.n_dec, nullptr); L->self_k.resize(c.n_dec); L->self_v.resize(c.n_dec);
     L->wo_t.assign(c.n_dec, nullptr); L->bo_t.assign(c.n_dec, nullptr);
     for (int i = 0; i < c.n_dec; ++i) {
-        if (!md.mq) { L->cross_k[i] = a.take((size_t)B * S * d * e); L->cross_v[i] = a.take((size_t)B * S * d * e); }
+        if (!pl.mq) { L->cross_k[i] = a.take((size_t)B * S * d * e); L->cross_v[i] = a.take((size_t)B * S * d * e); }
         L->self_k[i] = a.take((size_t)B * Tmax * d * e); L->self_v[i] = a.take((size_t)B * Tmax * d * e);
     }
-    L->mem = L->qt = L->ctx = nullptr;
-    if (md.mq) {
+    L->mem = L->qt = L->ctx = L->mq_sp = nullptr;
+    if (pl.mq) {
         const size_t H = c.n_head;
         L->mem = a.take((size_t)B * S * d * e);
         L->qt = a.take((size_t)B * H * d * e); L->ctx = a.take((size_t)B * H * d * e);
-        L->mq_sp_bytes = mq_split_bytes(B, std::max(mq_parts(B, S), mq_parts(B, Tmax)));      // (cross-attention and the f32 step's self-attention form share it)
-        L->mq_sp = L->mq_sp_bytes > 0 ? a.take((size_t)L->mq_sp_bytes) : nullptr;
+        if (pl.mq_sp_bytes > 0) L->mq_sp = a.take((size_t)pl.mq_sp_bytes);
         for (int i = 0; i < c.n_dec; ++i) { L->wo_t[i] = a.take(d * H * d * e); L->bo_t[i] = (float*)a.take(d * 4); }
         L->wvt_self.assign(c.n_dec, nullptr);
         if (c.dtype == PA_F32) for (int i = 0; i < c.n_dec; ++i) L->wvt_self[i] = a.take(d * d * e);
         L->wo_ts.assign(c.n_dec, nullptr); L->bo_ts.assign(c.n_dec, nullptr);
         if (c.dtype == PA_BF16) for (int i = 0; i < c.n_dec; ++i) { L->wo_ts[i] = a.take(d * H * d * e); L->bo_ts[i] = (float*)a.take(d * 4); }
     }
-    L->kv_tmp = md.mq ? nullptr : a.take((size_t)B * S * 2 * d * e);
+    L->kv_tmp = pl.mq ? nullptr : a.take((size_t)B * S * 2 * d * e);
     L->hid_cache = a.take((size_t)B * Tmax * d * e);
     // (x / y / z / z2 are sized for f32 rows: the bf16 step keeps its residual stream in f32, `f32res`)
     L->x = a.take(B * d * 4); L->qkv = a.take(B * 3 * d * e); L->ao = a.take(B * d * e); L->z = a.take(B * d * 4);
@@ -1104,9 +1083,9 @@ int launch_attn(pa_model* m, T* out, const T* q, int ldq, T* kc, T* vc, int Lmax
     return 0;
 }
 
-// Segment table of the beam history reorder (dec_beam_copy_kernel) for `rows` hypothesis rows in step form `sf`; L may be a layout
-// without pointers (the workspace query).  Returns the scratch bytes of one row, or a negative PA_E* code.
-int64_t beam_segments(const pa_model_cfg& c, const StepForm& sf, const DecodeLayout* L, int rows, int Tmax, BeamCopy* cp) {
+// Segment table of the beam history reorder (dec_beam_copy_kernel) for `rows` hypothesis rows of a step planned as `pl`; L may be NULL
+// (the workspace query).  Returns the scratch bytes of one row, or a negative PA_E* code.
+int64_t beam_segments(const pa_model_cfg& c, const DecodePlan& pl, const DecodeLayout* L, int rows, int Tmax, BeamCopy* cp) {
     const int64_t e = c.dtype == PA_BF16 ? 2 : 4, d = c.d_model, H = c.n_head, dh = d / H;
     int n = 0;
     int64_t off = 0;
@@ -1120,7 +1099,7 @@ int64_t beam_segments(const pa_model_cfg& c, const StepForm& sf, const DecodeLay
         off += ((by_pos ? (int64_t)Tmax * unit : (int64_t)outer * Tmax * unit) + 15) / 16 * 16;
     };
     for (int i = 0; i < c.n_dec; ++i) {
-        if (sf.mq_self || sf.mq_self_bf) {      // row cache of the layer inputs [rows][Tmax][d] (self_v is not read in these forms)
+        if (pl.mq_self || pl.mq_self_bf) {      // row cache of the layer inputs [rows][Tmax][d] (self_v is not read in these forms)
             add(L ? L->self_k[i] : nullptr, Tmax * d * e, 1, 0, (int)(d * e), 0, 1);
         } else {                                // per-head K / V caches [rows][H][Tmax][dh]
             add(L ? L->self_k[i] : nullptr, H * Tmax * dh * e, (int)H, Tmax * dh * e, (int)(dh * e), 0, 1);
@@ -1135,6 +1114,60 @@ int64_t beam_segments(const pa_model_cfg& c, const StepForm& sf, const DecodeLay
     cp->scr_row = (off + 255) / 256 * 256;
     return cp->scr_row;
 }
+
+// Which forms the step takes and what it needs, from the configuration, the shape and the switches alone.
+// fold: LayerNorm folded into its consumer Linear (bf16 decode): 17 LayerNorm launches fewer per step.
+// On the ring kernel (gemm3s_kernel's prologue statistics pass) this was MEASURED NULL on MI355X (B 256, 1024 steps, one lane:
+// 1.228 ms / step folded against 1.210 - the statistics pass pays the memory round trips the LayerNorm launch paid).  On
+// gemm_skinny_kernel the Z tile is resident in LDS and the statistics cost no round trip: 1.072 against 1.089 ms / step.  So: on by
+// default exactly where pa_gemm_norm_a takes the skinny kernel (d_model 512, at most 512 rows); PLANK_DECODE_FOLD_LN=0 / 1 forces.
+// The exact-f32 step folds too since round 4 (pa_ln_fold_weights_f32 + the f32 skinny kernel with the statistics taken from
+// the rows themselves): 17 LayerNorm launches fewer per step - measured +0.5 % only (B 256: 1.995 vs 2.005 ms / step; the folded
+// Linears re-read their rows for the statistics), token-exact against the reference in every decode test.  d_model 512, <= 512 rows.
+// f32res: f32 residual stream inside the bf16 step (see DecodeLayout): on wherever every Linear of the step takes the skinny
+// kernel (d_model 512, at most 512 rows).  tests/bf16_decode_sim.py / profiles/r04_bf16_decode_rounding_sim.txt: exact-prefix
+// agreement with the f32 tokens 0.40 -> 0.63-0.70 on 32 rows x 128 steps.  PLANK_DECODE_F32_RESID=0 restores the all-bf16 step.
+// mq: absorbed cross-attention (csrc/decode_mq.h) wherever the fold is on, with at most 8 heads; PLANK_DECODE_MQ=0 (bf16) /
+// PLANK_DECODE_MQ_F32=0 (exact f32) restore the per-layer K / V caches.
+DecodePlan plan_decode(const pa_model_cfg& c, int B, int S, int Tmax, const DecodeSwitches& sw) {
+    DecodePlan r{};
+    const int d = c.d_model;
+    // (the configuration checks are pa_model_create's: no handle exists for a cfg that fails them)
+    if (d <= 0 || c.n_head <= 0 || d % c.n_head || (c.dtype != PA_F32 && c.dtype != PA_BF16)) { r.status = PA_EINVAL; return r; }
+    const int dh = d / c.n_head;
+    if ((dh != 16 && dh != 32 && dh != 64) || d % 8 || c.d_ff % 8) { r.status = PA_ESHAPE; return r; }
+    if (B <= 0 || S <= 0 || Tmax <= 0 || Tmax > MAX_T || c.n_dec < 0) { r.status = PA_EINVAL; return r; }
+    const bool f32 = c.dtype == PA_F32;
+    const bool fold_env = sw.fold_ln >= 0 ? sw.fold_ln != 0 : (d == 512 && B <= 512);
+    r.fold = fold_env && !f32 && d % 64 == 0 && c.d_ff % 32 == 0 && c.d_ff >= d && (size_t)((B + 63) / 64) * ((3 * d + 63) / 64) <= 512;
+    if (f32) r.fold = fold_env && d == 512 && B <= 512 && c.d_ff % 32 == 0 && c.d_ff >= d;   // (N < K: pa_gemm_norm_a's f32 form cannot materialise y - ADVICE r4)
+    r.f32res = r.fold && !f32 && sw.f32_resid != 0 && d == 512 && B <= 512 && c.d_ff % 512 == 0;
+    r.mq = r.fold && (f32 ? sw.mq_f32 != 0 : sw.mq != 0) && d == MQ_D && B <= 512 && c.n_head <= MQ_MAXH &&
+           S <= (f32 ? 16000 : MQ_MAXS);     // (f32: launch_cross_mq32 keeps 16 KB of partial-score slots beside the ring)
+    r.mq_contract = r.mq && dh == 64 && (sw.mq_contract >= 0 ? sw.mq_contract != 0 : f32);
+    // exact f32: the self-attention in the same form - the step caches the layer-input rows x_t instead of K and V (half the bytes of what is
+    // then the largest stream of the f32 step), q~ = W_k^T q, W_v behind the softmax (q . b_k cancels, b_v is added once).  PLANK_DECODE_MQ_SELF=0.
+    r.mq_self = r.mq && r.mq_contract && f32 && sw.mq_self != 0 && Tmax <= 16000;
+    // bf16 (round 6; needs the f32 residual stream's step form): pays from ~200 batch elements on - measured in one session, B 256 x 1024 steps:
+    // 0.969 -> 0.929 ms / step (264 k -> 276 k tokens/s; half the bytes of the self-attention stream against one more launch and a K = H d
+    // out-projection per layer); B 64: 0.557 -> 0.662, B 16: 0.476 -> 0.609 (profiles/r06_decode_self_absorbed.txt).
+    // PLANK_DECODE_MQ_SELF_BF16: 0 never, 1 always, unset = B >= PLANK_DECODE_MQ_SELF_MINB (200).
+    r.mq_self_bf = r.mq && !r.mq_contract && !f32 && r.f32res && dh == 64 && Tmax <= MQ_MAXS &&
+                   (sw.mq_self_bf16 >= 0 ? sw.mq_self_bf16 != 0 : B >= sw.mq_self_minb);
+    r.mq_nt = sw.mq_nt; r.mq_swap = sw.mq_swap; r.mq32_w8 = sw.mq32_w8;
+    if (r.mq) {
+        const int ps = mq_parts(B, S, sw.mq_parts, sw.mq_mint), pt = mq_parts(B, Tmax, sw.mq_parts, sw.mq_mint);
+        r.parts_cross = ps;
+        if (r.mq_self || r.mq_self_bf) r.parts_self = pt;
+        r.mq_sp_bytes = mq_split_bytes(B, std::max(ps, pt));      // (sized for either launch, whichever self-attention form the step takes)
+    }
+    DecodeLayout sizes;
+    BeamCopy cp;
+    r.ws_bytes = (int64_t)dec_layout(c, r, &sizes, nullptr, B, S, Tmax) + 256;
+    r.scr_row = beam_segments(c, r, nullptr, B, Tmax, &cp);    // (negative: the PA_E* code pa_decode_beam_ws_bytes answers with)
+    return r;
+}
+
 
 // Beam workspace: scores f32 [rows], finished / parent int32 [rows], candidates (f32 log p, int32 token, int32 attach) [rows][K], then
 // the reorder scratch [rows][scr_row].  The mode layouts (this one, sample_layout, prefix_layout): base NULL is the size query and
@@ -1214,7 +1247,7 @@ int sample_tail(pa_model* m, int ldv, hipStream_t s) {
 }
 
 // The end of every step, whatever the mode and the residual-stream form: the mode's choice of a token per row, then the step counter.
-// (The next step's embedding is dec_embed_kernel at its part 0.  A fused tail - embedding and counter inside dec_sample_kernel, norm3 +
+// (The next step's embedding is dec_embed_kernel at its start.  A fused tail - embedding and counter inside dec_sample_kernel, norm3 +
 // decoder.norm in one launch, PLANK_DECODE_FUSE_TAIL - was built, MEASURED NULL on MI355X in round 5 (B 256 x 1024 steps under graph
 // replay: bf16 1.0905 ms / step fused against 1.0794, f32 1.9954 against 1.9813) and removed.)
 template <typename T>
@@ -1227,253 +1260,239 @@ int end_of_step(pa_model* m, int ldv, hipStream_t s) {
     return 0;
 }
 
-// One decode step in 2 * n_dec + 1 parts, each ending right after an attention launch (part 2i: self-attention of layer i,
-// part 2i + 1: its cross-attention; the last part is the tail: final norm, heads, sampling).  The attention launches are the
-// HBM-bound third of the step (they stream the K/V caches); everything between them is a chain of latency-bound launches on B
-// rows.  pa_decode_step_pair() runs two half-batches ("lanes") on two streams and uses the part boundaries to keep the lanes
-// out of phase: `wait_ev` is waited for immediately before the attention launch, `rec_ev` recorded immediately after it.
+// ---- one decode step: the embedding, then per layer the self-attention, cross-attention and feed-forward blocks, then the tail -------
+// The attention launches are the HBM-bound third of the step (they stream the caches); everything between them is a chain of
+// latency-bound launches on B rows.
+
+// self-attention of layer i over the per-head K / V caches (the kernel appends this step's K / V rows itself)
 template <typename T>
-int step_part(pa_model* m, int part, void* st, hipEvent_t wait_ev, hipEvent_t rec_ev) {
+int self_attn(pa_model* m, int i, void* st) {
+    DecodeLayout* L = m->dec;
+    const int d = m->cfg.d_model;
+    return launch_attn<T>(m, (T*)L->ao, (const T*)L->qkv, 3 * d, (T*)L->self_k[i], (T*)L->self_v[i], L->Tmax, nullptr, 0, L->t_dev, L->B, st,
+                          nullptr, (const T*)L->qkv);
+}
+// cross-attention of layer i over the per-head K / V caches of the memory
+template <typename T>
+int cross_attn(pa_model* m, int i, void* st) {
+    DecodeLayout* L = m->dec;
+    return launch_attn<T>(m, (T*)L->ao, (const T*)L->q, m->cfg.d_model, (T*)L->cross_k[i], (T*)L->cross_v[i], L->S, L->cu ? nullptr : L->kpm,
+                          L->S, L->t_dev, L->B, st, L->cu);
+}
+
+// Absorbed attention (csrc/decode_mq.h) of the query rows in L->q over `nk` rows per element of `cache`: q~_h = scale log2e W_k,h^T q_h
+// for all heads (-> L->qt), then attention over the cached rows themselves (-> L->ctx); the caller applies W_v / W_o behind it.
+//   cross-attention: cache = the memory rows, nk = S, with the key-padding mask or the packed offsets, no t_dev, no xrow;
+//   self-attention:  cache = the layer-input rows so far, nk = Tmax of which t_dev + 1 count; the expand launch appends this step's
+//                    row from `xrow` (the residual stream's x) to the cache.
+template <typename T, typename XT>
+int absorbed_attn(pa_model* m, const T* Wk, T* cache, int nk, int nparts, const int32_t* t_dev, const uint8_t* kpm, const int32_t* cu,
+                  const XT* xrow, hipStream_t s) {
+    DecodeLayout* L = m->dec;
+    const DecodePlan& pl = L->plan;
+    const int d = m->cfg.d_model, H = m->cfg.n_head, B = L->B;
+    const float sl = LOG2E_F / sqrtf((float)(d / H));
+    const dim3 xg((B + MQ_XR - 1) / MQ_XR, H);
+    T* const xcache = xrow ? cache : nullptr;
+    const int xT = xrow ? L->Tmax : 0;
+    if (d / H == 64) PA_LAUNCH((mq_expand_q_kernel<64, T, XT>), xg, dim3(512), 0, s, (T*)L->qt, (const T*)L->q, d, Wk, B, d, H, sl, xrow, xcache, t_dev, xT);
+    else if constexpr (std::is_same<T, XT>::value) PA_LAUNCH((mq_expand_q_kernel<0, T, XT>), xg, dim3(512), 0, s, (T*)L->qt, (const T*)L->q, d, Wk, B, d, H, sl, xrow, xcache, t_dev, xT);
+    else return PA_ESHAPE;
+    if constexpr (sizeof(T) == 2)
+        return launch_cross_mq((bf16*)L->ctx, (const bf16*)L->qt, (const bf16*)cache, kpm, cu, B, nk, H, d, s, nparts, pl.mq_nt, pl.mq_swap,
+                               L->mq_sp, pl.mq_sp_bytes, t_dev);
+    else
+        return launch_cross_mq32((float*)L->ctx, (const float*)L->qt, (const float*)cache, kpm, cu, B, nk, H, d, s, nparts, pl.mq32_w8, t_dev,
+                                 L->mq_sp, pl.mq_sp_bytes);
+}
+
+// The residual stream of the folded step in its two number formats.  Pre-norm rows live in z (k = 0) / z2 (k = 1), normed rows in x / y.
+//   add:         pre-norm buffer k = A W^T + bias + R                                   (Linear + residual)
+//   norm_linear: Cout = epi(LayerNorm(pre-norm buffer k) Wf^T + v), Y = the normed rows   (pa_gemm_norm_a with the folded weights of
+//                `site` - DecodeLayout::fw - of layer i)
+template <typename T>
+struct StreamSame {        // rows in the step's dtype
+    typedef T row_t;
+    pa_model* m; void* st;
+    int row_dtype() const { return m->cfg.dtype; }
+    const void* x_operand() const { return m->dec->x; }
+    int add(const void* A, const void* W, const float* bias, const void* R, int k, int K) const {
+        DecodeLayout* L = m->dec;
+        return linear(m, A, W, bias, k ? L->z2 : L->z, m->cfg.d_model, L->B, m->cfg.d_model, K, 0, R, -1, st);
+    }
+    int norm_linear(int k, int site, int i, const float* gamma, const float* beta, void* Y, void* Cout, int N, int relu) const {
+        DecodeLayout* L = m->dec;
+        return linear_norm_a(m, k ? L->z2 : L->z, L->fw[site][i], L->fu[site][i], L->fv[site][i], gamma, beta, m->cfg.eps_layer, Y, Cout, N,
+                             L->B, N, m->cfg.d_model, relu, st);
+    }
+};
+struct StreamF32 {         // bf16 step, f32 rows: x / y / z / z2 hold f32, zb / z2b / xb their bf16 copies = the matrix operands (plan.f32res)
+    typedef float row_t;
+    pa_model* m; void* st;
+    int row_dtype() const { return PA_F32; }
+    const void* x_operand() const { return m->dec->xb; }
+    int add(const void* A, const void* W, const float* bias, const void* R, int k, int K) const {
+        DecodeLayout* L = m->dec;
+        return linear_res32(m, A, W, bias, (const float*)R, (float*)(k ? L->z2 : L->z), k ? L->z2b : L->zb, L->B, m->cfg.d_model, K, st);
+    }
+    int norm_linear(int k, int site, int i, const float* gamma, const float* beta, void* Y, void* Cout, int N, int relu) const {
+        DecodeLayout* L = m->dec;
+        return linear_norm_a32(m, k ? L->z2b : L->zb, (const float*)(k ? L->z2 : L->z), L->fw[site][i], L->fu[site][i], L->fv[site][i], gamma,
+                               beta, m->cfg.eps_layer, (float*)Y, Cout, N, L->B, N, m->cfg.d_model, relu, st);
+    }
+};
+
+// The layers of the folded step (plan.fold) over residual stream `rs`.  Every LayerNorm but the last rides in the Linear behind it:
+//   self:  q (k, v) = norm3(z of the layer before) W_in^T, x = the normed rows;  z2 = attention W_o^T + b + x
+//   cross: q = norm1(z2) W_q^T, y = the normed rows;                             z2 = attention W_o^T + b + y
+//   ffn:   ff = act(norm2(z2) W_1^T + b_1), x = the normed rows;                 z = ff W_2^T + b_2 + x
+template <typename T, typename Stream>
+int folded_layers(pa_model* m, const Stream& rs, void* st) {
     const pa_model_cfg& c = m->cfg;
     DecodeLayout* L = m->dec;
-    const int d = c.d_model, ff = c.d_ff, B = L->B, S = L->S, Tmax = L->Tmax;
+    const DecodePlan& pl = L->plan;
+    const int d = c.d_model, ff = c.d_ff, H = c.n_head, B = L->B;
     hipStream_t s = (hipStream_t)st;
     auto PF = [&](int i) { return (const float*)m->pf[i]; };
     auto PL = [&](int i) { return (const void*)m->pl[i]; };
-    void* x = L->x;
+    typedef typename Stream::row_t XT;
     // FFN activation: ReLU rides in the first Linear's epilogue (relu flag); ACTIVATION gelu is a launch of its own behind it
     const bool gelu = c.activation == 2;
-    const int act = gelu ? 0 : 1;
-    auto gelu_ff = [&]() -> int { return gelu ? pa_gelu_fwd(L->ff, L->ff, B, ff, ff, c.dtype, 0.f, 0, st) : 0; };
-    const int n_parts = 2 * c.n_dec + 1;
-    if (part < 0 || part >= n_parts) return PA_EINVAL;
-    auto fence_in = [&]() -> int { if (wait_ev) HIP_RC(hipStreamWaitEvent(s, wait_ev, 0)); return 0; };
-    auto fence_out = [&]() -> int { if (rec_ev) HIP_RC(hipEventRecord(rec_ev, s)); return 0; };
-    // absorbed cross-attention of layer i (csrc/decode_mq.h): q~_h = scale log2e W_k,h^T q_h for all heads, then attention over the
-    // memory rows themselves; the Linear behind it applies W_o,h W_v,h to the context rows (wo_t)
-    auto cross_mq = [&](pa_model* mm, int i, hipStream_t ss) -> int {
-        const int H = c.n_head, pbi = mm->dec_base(i);
-        const T* Wk = (const T*)mm->pl[pbi + D_CA_IN_W] + (size_t)d * d;
-        const float sl = LOG2E_F / sqrtf((float)(d / H));
-        const dim3 xg((B + MQ_XR - 1) / MQ_XR, H);
-        if (d / H == 64) PA_LAUNCH((mq_expand_q_kernel<64, T>), xg, dim3(512), 0, ss, (T*)L->qt, (const T*)L->q, d, Wk, B, d, H, sl);
-        else PA_LAUNCH((mq_expand_q_kernel<0, T>), xg, dim3(512), 0, ss, (T*)L->qt, (const T*)L->q, d, Wk, B, d, H, sl);
-        RC(fence_in());
-        if constexpr (sizeof(T) == 2)
-            RC(launch_cross_mq((bf16*)L->ctx, (const bf16*)L->qt, (const bf16*)L->mem, L->cu ? nullptr : L->kpm, L->cu, B, S, H, d, ss,
-                               L->mq_sp, L->mq_sp_bytes));
-        else
-            RC(launch_cross_mq32((float*)L->ctx, (const float*)L->qt, (const float*)L->mem, L->cu ? nullptr : L->kpm, L->cu, B, S, H, d, ss, nullptr,
-                                 L->mq_sp, L->mq_sp_bytes));
-        return fence_out();
-    };
-    // the step's input embedding from the token of step t - 1 (all zeros at t = 0, reference models.py:114-123 with no token yet)
-    if (part == 0) {
-        const int g1 = (B * (d / 4) + 255) / 256;
-        if (L->f32res)
-            PA_LAUNCH(dec_embed_kernel<float>, dim3(g1), dim3(256), 0, s, (float*)L->x, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
-                               L->tokens, Tmax, L->t_dev, B, d, c.out_dof, (bf16*)L->xb);
-        else
-            PA_LAUNCH(dec_embed_kernel<T>, dim3(g1), dim3(256), 0, s, (T*)L->x, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
-                               L->tokens, Tmax, L->t_dev, B, d, c.out_dof, (bf16*)nullptr);
-    }
-    // absorbed SELF-attention of layer i (exact f32): q in L->q, the layer input rows in `xin`; the row cache is self_k[i]
-    auto self_mq = [&](pa_model* mm, int i, const void* xin, hipStream_t ss) -> int {
-        if constexpr (sizeof(T) == 4) {
-            const int H = c.n_head, pbi = mm->dec_base(i);
-            const float* Wk = (const float*)mm->pl[pbi + D_SA_IN_W] + (size_t)d * d;
-            const float sl = LOG2E_F / sqrtf((float)(d / H));
-            PA_LAUNCH((mq_expand_q_kernel<64, float>), dim3((B + MQ_XR - 1) / MQ_XR, H), dim3(512), 0, ss, (float*)L->qt, (const float*)L->q, d, Wk, B, d, H, sl,
-                      (const float*)xin, (float*)L->self_k[i], (const int32_t*)L->t_dev, Tmax);
-            RC(fence_in());
-            RC(launch_cross_mq32((float*)L->ctx, (const float*)L->qt, (const float*)L->self_k[i], nullptr, nullptr, B, Tmax, H, d, ss, L->t_dev,
-                                 L->mq_sp, L->mq_sp_bytes));
-            RC(fence_out());
-            PA_LAUNCH(mq_contract_v_kernel<float>, dim3((B + MQ_XR - 1) / MQ_XR, H), dim3(512), 0, ss, (float*)L->ao, d, (const float*)L->ctx,
-                      (const float*)L->wvt_self[i], (const float*)mm->pf[pbi + D_SA_IN_B] + 2 * d, B, d, H);
-            return 0;
-        } else {
-            (void)mm; (void)i; (void)xin; (void)ss;
-            return PA_EINVAL;
-        }
-    };
-    const bool fold = L->fold;
-    if (L->f32res) {
-        // ---- bf16 step with an f32 residual stream: x / y / z / z2 are f32 rows, zb / z2b / xb their bf16 copies (matrix operands)
-        float* xf = (float*)L->x; float* yf = (float*)L->y; float* zf = (float*)L->z; float* z2f = (float*)L->z2;
-        if (part >= 2 && (part & 1) == 0) {    // feed-forward block of the previous layer
-            const int j = part / 2 - 1, pb = m->dec_base(j);
-            if (L->mq && L->mq_contract) {
-                PA_LAUNCH(mq_contract_v_kernel<bf16>, dim3((B + MQ_XR - 1) / MQ_XR, c.n_head), dim3(512), 0, s, (bf16*)L->ao, d, (const bf16*)L->ctx,
-                          (const bf16*)L->wo_t[j], PF(pb + D_CA_IN_B) + 2 * d, B, d, c.n_head);
-                RC(linear_res32(m, L->ao, PL(pb + D_CA_OUT_W), PF(pb + D_CA_OUT_B), yf, z2f, L->z2b, B, d, d, st));
-            } else if (L->mq) RC(linear_res32(m, L->ctx, L->wo_t[j], L->bo_t[j], yf, z2f, L->z2b, B, d, c.n_head * d, st));     // W_o,h W_v,h on the context rows
-            else RC(linear_res32(m, L->ao, PL(pb + D_CA_OUT_W), PF(pb + D_CA_OUT_B), yf, z2f, L->z2b, B, d, d, st));
-            RC(linear_norm_a32(m, L->z2b, z2f, L->fw[2][j], L->fu[2][j], L->fv[2][j], PF(pb + D_N2_W), PF(pb + D_N2_B), c.eps_layer, xf,
-                               L->ff, ff, B, ff, d, act, st));
-            RC(gelu_ff());
-            RC(linear_res32(m, L->ff, PL(pb + D_L2_W), PF(pb + D_L2_B), xf, zf, L->zb, B, d, ff, st));
-            if (part == n_parts - 1)
-                RC(pa_layernorm_fwd(xf, zf, PF(pb + D_N3_W), PF(pb + D_N3_B), L->mean, L->rstd, B, d, c.eps_layer, PA_F32, st));
-        }
-        if (part == n_parts - 1) {
-            RC(pa_layernorm_fwd(L->hf, xf, PF(m->dec_norm()), PF(m->dec_norm() + 1), L->mean, L->rstd, B, d, c.eps_final, PA_F32, st));
-            const int tl = m->tail(), ldv = (c.vocab + 7) / 8 * 8;
-            {   // vocabulary head in f32 on the f32 hidden rows (f32 master weight; the f32 skinny kernel)
-                pa_gemm_args g; memset(&g, 0, sizeof(g));
-                g.A = L->hf; g.B = PF(tl + T_VOCAB_W); g.C = L->vlog; g.bias = PF(tl + T_VOCAB_B);
-                g.M = B; g.N = c.vocab; g.K = d; g.lda = d; g.ldb = d; g.ldc = ldv;
-                g.batch = 1; g.a_kcontig = 1; g.b_kcontig = 1; g.in_dtype = PA_F32; g.out_dtype = PA_F32;
-                g.alpha = 1.f; g.aux_scale = 1.f; g.splitk = 1;
-                RC(pa_gemm(&g, st));
-            }
-            PA_LAUNCH(dec_cast_kernel, dim3((B * d / 4 + 255) / 256), dim3(256), 0, s, (bf16*)L->h, (const float*)L->hf, (int64_t)B * d / 4);
-            RC(linear(m, L->h, PL(tl + T_PTR_W), PF(tl + T_PTR_B), L->pfeat, d, B, d, d, 0, nullptr, -1, st));
-            return end_of_step<T>(m, ldv, s);
-        }
-        const int i = part / 2, pb = m->dec_base(i);
-        if ((part & 1) == 0 && L->mq_self_bf) {
-            // absorbed self-attention: only the query rows are projected (the first d rows of the LayerNorm-folded in_proj); the expand launch
-            // forms q~_h = scale log2e W_k,h^T q_h AND appends this step's layer-input row (f32 residual stream -> bf16) to the row cache
-            if constexpr (sizeof(T) == 2) {
-                if (i > 0) {
-                    const int pp = m->dec_base(i - 1);
-                    RC(linear_norm_a32(m, L->zb, zf, L->fw[0][i], L->fu[0][i], L->fv[0][i], PF(pp + D_N3_W), PF(pp + D_N3_B), c.eps_layer, xf,
-                                       L->q, d, B, d, d, 0, st));
-                } else {
-                    RC(linear(m, L->xb, PL(pb + D_SA_IN_W), PF(pb + D_SA_IN_B), L->q, d, B, d, d, 0, nullptr, -1, st));
-                }
-                const int H = c.n_head;
-                const bf16* Wk = (const bf16*)m->pl[pb + D_SA_IN_W] + (size_t)d * d;
-                const float sl = LOG2E_F / sqrtf((float)(d / H));
-                PA_LAUNCH((mq_expand_q_kernel<64, bf16, float>), dim3((B + MQ_XR - 1) / MQ_XR, H), dim3(512), 0, s, (bf16*)L->qt, (const bf16*)L->q, d, Wk, B, d, H, sl,
-                          (const float*)xf, (bf16*)L->self_k[i], (const int32_t*)L->t_dev, Tmax);
-                RC(fence_in());
-                RC(launch_cross_mq((bf16*)L->ctx, (const bf16*)L->qt, (const bf16*)L->self_k[i], nullptr, nullptr, B, Tmax, H, d, s, L->mq_sp, L->mq_sp_bytes,
-                                   L->t_dev));
-                RC(fence_out());
-            }
-            return 0;
-        }
-        if ((part & 1) == 0) {
-            if (i > 0) {
-                const int pp = m->dec_base(i - 1);
-                RC(linear_norm_a32(m, L->zb, zf, L->fw[0][i], L->fu[0][i], L->fv[0][i], PF(pp + D_N3_W), PF(pp + D_N3_B), c.eps_layer, xf,
-                                   L->qkv, 3 * d, B, 3 * d, d, 0, st));
-            } else {
-                RC(linear(m, L->xb, PL(pb + D_SA_IN_W), PF(pb + D_SA_IN_B), L->qkv, 3 * d, B, 3 * d, d, 0, nullptr, -1, st));
-            }
-            RC(fence_in());
-            RC(launch_attn<T>(m, (T*)L->ao, (const T*)L->qkv, 3 * d, (T*)L->self_k[i], (T*)L->self_v[i], Tmax, nullptr, 0,
-                              L->t_dev, B, st, nullptr, (const T*)L->qkv));
-            RC(fence_out());
-        } else {
-            if (L->mq_self_bf) RC(linear_res32(m, L->ctx, L->wo_ts[i], L->bo_ts[i], xf, z2f, L->z2b, B, d, c.n_head * d, st));   // W_o,h W_v,h on the context rows
-            else RC(linear_res32(m, L->ao, PL(pb + D_SA_OUT_W), PF(pb + D_SA_OUT_B), xf, z2f, L->z2b, B, d, d, st));
-            RC(linear_norm_a32(m, L->z2b, z2f, L->fw[1][i], L->fu[1][i], L->fv[1][i], PF(pb + D_N1_W), PF(pb + D_N1_B), c.eps_layer, yf,
-                               L->q, d, B, d, d, 0, st));
-            if (L->mq) { RC(cross_mq(m, i, s)); return 0; }
-            RC(fence_in());
-            RC(launch_attn<T>(m, (T*)L->ao, (const T*)L->q, d, (T*)L->cross_k[i], (T*)L->cross_v[i], S, L->cu ? nullptr : L->kpm, S,
-                              L->t_dev, B, st, L->cu));
-            RC(fence_out());
-        }
-        return 0;
-    }
-    if (part >= 2 && (part & 1) == 0) {
-        // the feed-forward block of the previous layer (everything after its cross-attention)
-        const int j = part / 2 - 1, pb = m->dec_base(j);
-        if (fold) {
-            // z2 = ao Wo^T + b + y1;  ff = relu(norm2(z2) W1^T + b1), y2 -> x;  z3 = ff W2^T + b2 + y2 -> z
-            if (L->mq && L->mq_contract) {
-                PA_LAUNCH(mq_contract_v_kernel<T>, dim3((B + MQ_XR - 1) / MQ_XR, c.n_head), dim3(512), 0, s, (T*)L->ao, d, (const T*)L->ctx,
-                          (const T*)L->wo_t[j], PF(pb + D_CA_IN_B) + 2 * d, B, d, c.n_head);
-                RC(linear(m, L->ao, PL(pb + D_CA_OUT_W), PF(pb + D_CA_OUT_B), L->z2, d, B, d, d, 0, L->y, -1, st));
-            } else if (L->mq) RC(linear(m, L->ctx, L->wo_t[j], L->bo_t[j], L->z2, d, B, d, c.n_head * d, 0, L->y, -1, st));
-            else RC(linear(m, L->ao, PL(pb + D_CA_OUT_W), PF(pb + D_CA_OUT_B), L->z2, d, B, d, d, 0, L->y, -1, st));
-            RC(linear_norm_a(m, L->z2, L->fw[2][j], L->fu[2][j], L->fv[2][j], PF(pb + D_N2_W), PF(pb + D_N2_B), c.eps_layer, L->x,
-                             L->ff, ff, B, ff, d, act, st));
-            RC(gelu_ff());
-            RC(linear(m, L->ff, PL(pb + D_L2_W), PF(pb + D_L2_B), L->z, d, B, d, ff, 0, L->x, -1, st));
-            if (part == n_parts - 1)          // the last layer's norm3 has no Linear behind it: explicit
-                RC(pa_layernorm_fwd(L->x, L->z, PF(pb + D_N3_W), PF(pb + D_N3_B), L->mean, L->rstd, B, d, c.eps_layer, c.dtype, st));
-        } else {
-            RC(linear_ln(m, L->ao, PL(pb + D_CA_OUT_W), PF(pb + D_CA_OUT_B), L->y, L->z, L->x, PF(pb + D_N2_W), PF(pb + D_N2_B), c.eps_layer, B, d, st));
-            RC(linear(m, L->x, PL(pb + D_L1_W), PF(pb + D_L1_B), L->ff, ff, B, ff, d, act, nullptr, -1, st));
-            RC(gelu_ff());
-            RC(linear_ln(m, L->ff, PL(pb + D_L2_W), PF(pb + D_L2_B), L->x, L->z, L->x, PF(pb + D_N3_W), PF(pb + D_N3_B), c.eps_layer, B, ff, st));
-        }
-    }
-    if (part == n_parts - 1) {
-        RC(pa_layernorm_fwd(L->h, L->x, PF(m->dec_norm()), PF(m->dec_norm() + 1), L->mean, L->rstd, B, d, c.eps_final, c.dtype, st));
-        const int tl = m->tail(), ldv = (c.vocab + 7) / 8 * 8;
-        RC(linear(m, L->h, PL(tl + T_VOCAB_W), PF(tl + T_VOCAB_B), L->vlog, ldv, B, c.vocab, d, 0, nullptr, PA_F32, st));
-        RC(linear(m, L->h, PL(tl + T_PTR_W), PF(tl + T_PTR_B), L->pfeat, d, B, d, d, 0, nullptr, -1, st));
-        return end_of_step<T>(m, ldv, s);
-    }
-    const int i = part / 2;
-    const int pb = m->dec_base(i);
-    if ((part & 1) == 0) {
-        if (L->mq_self) {                      // only the query rows are projected; K / V never exist (self_mq)
-            if (fold && i > 0) {
-                const int pp = m->dec_base(i - 1);
-                RC(linear_norm_a(m, L->z, L->fw[0][i], L->fu[0][i], L->fv[0][i], PF(pp + D_N3_W), PF(pp + D_N3_B), c.eps_layer, L->x,
-                                 L->q, d, B, d, d, 0, st));
-            } else {
-                RC(linear(m, x, PL(pb + D_SA_IN_W), PF(pb + D_SA_IN_B), L->q, d, B, d, d, 0, nullptr, -1, st));
-            }
-            return self_mq(m, i, L->x, s);
-        }
-        if (fold && i > 0) {                   // x = norm3(z) of the layer before, materialised by this launch for the residual add
+    const bool self_abs = pl.mq_self || pl.mq_self_bf;       // only the query rows are projected; K / V never exist
+    void* const qout = self_abs ? L->q : L->qkv;
+    const int nq = self_abs ? d : 3 * d;
+    const dim3 vg((B + MQ_XR - 1) / MQ_XR, H);
+    for (int i = 0; i < c.n_dec; ++i) {
+        const int pb = m->dec_base(i);
+        if (i > 0) {
             const int pp = m->dec_base(i - 1);
-            RC(linear_norm_a(m, L->z, L->fw[0][i], L->fu[0][i], L->fv[0][i], PF(pp + D_N3_W), PF(pp + D_N3_B), c.eps_layer, L->x,
-                             L->qkv, 3 * d, B, 3 * d, d, 0, st));
-        } else {
-            RC(linear(m, x, PL(pb + D_SA_IN_W), PF(pb + D_SA_IN_B), L->qkv, 3 * d, B, 3 * d, d, 0, nullptr, -1, st));
+            RC(rs.norm_linear(0, 0, i, PF(pp + D_N3_W), PF(pp + D_N3_B), L->x, qout, nq, 0));
+        } else {                                // the first layer's input is the embedding: nothing to fold
+            RC(linear(m, rs.x_operand(), PL(pb + D_SA_IN_W), PF(pb + D_SA_IN_B), qout, nq, B, nq, d, 0, nullptr, -1, st));
         }
-        // (the attention kernel appends this step's K / V rows to the caches itself)
-        RC(fence_in());
-        RC(launch_attn<T>(m, (T*)L->ao, (const T*)L->qkv, 3 * d, (T*)L->self_k[i], (T*)L->self_v[i], Tmax, nullptr, 0,
-                          L->t_dev, B, st, nullptr, (const T*)L->qkv));
-        RC(fence_out());
-    } else {
-        if (fold) {                            // z1 = ao Wo^T + b + x -> z2;  q = norm1(z1) Wq^T + bq, y1 -> y
-            RC(linear(m, L->ao, PL(pb + D_SA_OUT_W), PF(pb + D_SA_OUT_B), L->z2, d, B, d, d, 0, x, -1, st));
-            RC(linear_norm_a(m, L->z2, L->fw[1][i], L->fu[1][i], L->fv[1][i], PF(pb + D_N1_W), PF(pb + D_N1_B), c.eps_layer, L->y,
-                             L->q, d, B, d, d, 0, st));
-            if (L->mq) { RC(cross_mq(m, i, s)); return 0; }
+        if (self_abs) {
+            RC((absorbed_attn<T, XT>(m, (const T*)PL(pb + D_SA_IN_W) + (size_t)d * d, (T*)L->self_k[i], L->Tmax, pl.parts_self, L->t_dev, nullptr,
+                                     nullptr, (const XT*)L->x, s)));
+            if (pl.mq_self)
+                PA_LAUNCH(mq_contract_v_kernel<float>, vg, dim3(512), 0, s, (float*)L->ao, d, (const float*)L->ctx, (const float*)L->wvt_self[i],
+                          PF(pb + D_SA_IN_B) + 2 * d, B, d, H);
         } else {
-            RC(linear_ln(m, L->ao, PL(pb + D_SA_OUT_W), PF(pb + D_SA_OUT_B), x, L->z, L->y, PF(pb + D_N1_W), PF(pb + D_N1_B), c.eps_layer, B, d, st));
-            RC(linear(m, L->y, PL(pb + D_CA_IN_W), PF(pb + D_CA_IN_B), L->q, d, B, d, d, 0, nullptr, -1, st));
+            RC(self_attn<T>(m, i, st));
         }
-        RC(fence_in());
-        RC(launch_attn<T>(m, (T*)L->ao, (const T*)L->q, d, (T*)L->cross_k[i], (T*)L->cross_v[i], S, L->cu ? nullptr : L->kpm, S,
-                          L->t_dev, B, st, L->cu));
-        RC(fence_out());
+        if (pl.mq_self_bf) RC(rs.add(L->ctx, L->wo_ts[i], L->bo_ts[i], L->x, 1, H * d));   // W_o,h W_v,h on the context rows
+        else RC(rs.add(L->ao, PL(pb + D_SA_OUT_W), PF(pb + D_SA_OUT_B), L->x, 1, d));
+        RC(rs.norm_linear(1, 1, i, PF(pb + D_N1_W), PF(pb + D_N1_B), L->y, L->q, d, 0));
+        if (pl.mq) {
+            RC((absorbed_attn<T, T>(m, (const T*)PL(pb + D_CA_IN_W) + (size_t)d * d, (T*)L->mem, L->S, pl.parts_cross, nullptr,
+                                    L->cu ? nullptr : L->kpm, L->cu, (const T*)nullptr, s)));
+        } else {
+            RC(cross_attn<T>(m, i, st));
+        }
+        if (pl.mq && pl.mq_contract) {
+            PA_LAUNCH(mq_contract_v_kernel<T>, vg, dim3(512), 0, s, (T*)L->ao, d, (const T*)L->ctx, (const T*)L->wo_t[i], PF(pb + D_CA_IN_B) + 2 * d,
+                      B, d, H);
+            RC(rs.add(L->ao, PL(pb + D_CA_OUT_W), PF(pb + D_CA_OUT_B), L->y, 1, d));
+        } else if (pl.mq) RC(rs.add(L->ctx, L->wo_t[i], L->bo_t[i], L->y, 1, H * d));      // W_o,h W_v,h on the context rows
+        else RC(rs.add(L->ao, PL(pb + D_CA_OUT_W), PF(pb + D_CA_OUT_B), L->y, 1, d));
+        RC(rs.norm_linear(1, 2, i, PF(pb + D_N2_W), PF(pb + D_N2_B), L->x, L->ff, ff, gelu ? 0 : 1));
+        if (gelu) RC(pa_gelu_fwd(L->ff, L->ff, B, ff, ff, c.dtype, 0.f, 0, st));
+        RC(rs.add(L->ff, PL(pb + D_L2_W), PF(pb + D_L2_B), L->x, 0, ff));
+    }
+    if (c.n_dec < 1) return 0;
+    const int pb = m->dec_base(c.n_dec - 1);   // the last layer's norm3 has no Linear behind it: explicit
+    return pa_layernorm_fwd(L->x, L->z, PF(pb + D_N3_W), PF(pb + D_N3_B), L->mean, L->rstd, B, d, c.eps_layer, rs.row_dtype(), st);
+}
+
+// The layers of the un-folded step: every LayerNorm a launch of its own (linear_ln), per-head K / V caches
+template <typename T>
+int plain_layers(pa_model* m, void* st) {
+    const pa_model_cfg& c = m->cfg;
+    DecodeLayout* L = m->dec;
+    const int d = c.d_model, ff = c.d_ff, B = L->B;
+    auto PF = [&](int i) { return (const float*)m->pf[i]; };
+    auto PL = [&](int i) { return (const void*)m->pl[i]; };
+    const bool gelu = c.activation == 2;
+    for (int i = 0; i < c.n_dec; ++i) {
+        const int pb = m->dec_base(i);
+        RC(linear(m, L->x, PL(pb + D_SA_IN_W), PF(pb + D_SA_IN_B), L->qkv, 3 * d, B, 3 * d, d, 0, nullptr, -1, st));
+        RC(self_attn<T>(m, i, st));
+        RC(linear_ln(m, L->ao, PL(pb + D_SA_OUT_W), PF(pb + D_SA_OUT_B), L->x, L->z, L->y, PF(pb + D_N1_W), PF(pb + D_N1_B), c.eps_layer, B, d, st));
+        RC(linear(m, L->y, PL(pb + D_CA_IN_W), PF(pb + D_CA_IN_B), L->q, d, B, d, d, 0, nullptr, -1, st));
+        RC(cross_attn<T>(m, i, st));
+        RC(linear_ln(m, L->ao, PL(pb + D_CA_OUT_W), PF(pb + D_CA_OUT_B), L->y, L->z, L->x, PF(pb + D_N2_W), PF(pb + D_N2_B), c.eps_layer, B, d, st));
+        RC(linear(m, L->x, PL(pb + D_L1_W), PF(pb + D_L1_B), L->ff, ff, B, ff, d, gelu ? 0 : 1, nullptr, -1, st));
+        if (gelu) RC(pa_gelu_fwd(L->ff, L->ff, B, ff, ff, c.dtype, 0.f, 0, st));
+        RC(linear_ln(m, L->ff, PL(pb + D_L2_W), PF(pb + D_L2_B), L->x, L->z, L->x, PF(pb + D_N3_W), PF(pb + D_N3_B), c.eps_layer, B, ff, st));
     }
     return 0;
 }
 
 template <typename T>
-int step_impl(pa_model* m, void* st) {
-    for (int part = 0; part <= 2 * m->cfg.n_dec; ++part) RC(step_part<T>(m, part, st, nullptr, nullptr));
-    return 0;
-}
-
-int step_part_any(pa_model* m, int part, void* st, hipEvent_t w, hipEvent_t r) {
-    return m->cfg.dtype == PA_BF16 ? step_part<bf16>(m, part, st, w, r) : step_part<float>(m, part, st, w, r);
+int decode_step(pa_model* m, void* st) {
+    const pa_model_cfg& c = m->cfg;
+    DecodeLayout* L = m->dec;
+    const DecodePlan& pl = L->plan;
+    const int d = c.d_model, B = L->B;
+    hipStream_t s = (hipStream_t)st;
+    auto PF = [&](int i) { return (const float*)m->pf[i]; };
+    auto PL = [&](int i) { return (const void*)m->pl[i]; };
+    // the step's input embedding from the token of step t - 1 (all zeros at t = 0, reference models.py:114-123 with no token yet)
+    const int g1 = (B * (d / 4) + 255) / 256;
+    if (pl.f32res)
+        PA_LAUNCH(dec_embed_kernel<float>, dim3(g1), dim3(256), 0, s, (float*)L->x, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
+                           L->tokens, L->Tmax, L->t_dev, B, d, c.out_dof, (bf16*)L->xb);
+    else
+        PA_LAUNCH(dec_embed_kernel<T>, dim3(g1), dim3(256), 0, s, (T*)L->x, PF(P_IN_VALUE), PF(P_Q_COORD), PF(P_Q_POS),
+                           L->tokens, L->Tmax, L->t_dev, B, d, c.out_dof, (bf16*)nullptr);
+    if (pl.f32res) {
+        if constexpr (sizeof(T) == 2) RC((folded_layers<T, StreamF32>(m, StreamF32{m, st}, st)));
+        else return PA_EINVAL;
+    } else if (pl.fold) {
+        RC((folded_layers<T, StreamSame<T>>(m, StreamSame<T>{m, st}, st)));
+    } else {
+        RC(plain_layers<T>(m, st));
+    }
+    // the tail: decoder.norm, the vocabulary and pointer heads, the mode's choice of a token
+    const int tl = m->tail(), ldv = (c.vocab + 7) / 8 * 8;
+    if (pl.f32res) {
+        RC(pa_layernorm_fwd(L->hf, L->x, PF(m->dec_norm()), PF(m->dec_norm() + 1), L->mean, L->rstd, B, d, c.eps_final, PA_F32, st));
+        {   // vocabulary head in f32 on the f32 hidden rows (f32 master weight; the f32 skinny kernel)
+            pa_gemm_args g; memset(&g, 0, sizeof(g));
+            g.A = L->hf; g.B = PF(tl + T_VOCAB_W); g.C = L->vlog; g.bias = PF(tl + T_VOCAB_B);
+            g.M = B; g.N = c.vocab; g.K = d; g.lda = d; g.ldb = d; g.ldc = ldv;
+            g.batch = 1; g.a_kcontig = 1; g.b_kcontig = 1; g.in_dtype = PA_F32; g.out_dtype = PA_F32;
+            g.alpha = 1.f; g.aux_scale = 1.f; g.splitk = 1;
+            RC(pa_gemm(&g, st));
+        }
+        PA_LAUNCH(dec_cast_kernel, dim3((B * d / 4 + 255) / 256), dim3(256), 0, s, (bf16*)L->h, (const float*)L->hf, (int64_t)B * d / 4);
+    } else {
+        RC(pa_layernorm_fwd(L->h, L->x, PF(m->dec_norm()), PF(m->dec_norm() + 1), L->mean, L->rstd, B, d, c.eps_final, c.dtype, st));
+        RC(linear(m, L->h, PL(tl + T_VOCAB_W), PF(tl + T_VOCAB_B), L->vlog, ldv, B, c.vocab, d, 0, nullptr, PA_F32, st));
+    }
+    RC(linear(m, L->h, PL(tl + T_PTR_W), PF(tl + T_PTR_B), L->pfeat, d, B, d, d, 0, nullptr, -1, st));
+    return end_of_step<T>(m, ldv, s);
 }
 
 }  // namespace
 
 void pa_decode_free_layout(pa_model* m) {
-    if (m && m->dec) { for (hipEvent_t e : m->dec->pair_ev) (void)hipEventDestroy(e); delete m->dec; m->dec = nullptr; }
+    if (m && m->dec) { delete m->dec; m->dec = nullptr; }
 }
 
 extern "C" int64_t pa_decode_ws_bytes(pa_model* m, int32_t B, int32_t S, int32_t Tmax) {
-    if (!m || B <= 0 || S <= 0 || Tmax <= 0 || Tmax > MAX_T) return PA_EINVAL;
-    DecodeLayout tmp;
-    return (int64_t)dec_layout(m, &tmp, nullptr, B, S, Tmax) + 256;
+    if (!m) return PA_EINVAL;
+    const DecodePlan pl = plan_decode(m->cfg, B, S, Tmax, decode_switches());
+    return pl.status ? pl.status : pl.ws_bytes;
+}
+
+static_assert(sizeof(pa_decode_plan_info) == 72, "pa_decode_plan_info is 72 bytes (plankassembly_amd/_lib.py mirrors it)");
+// The dry run of pa_decode_begin / pa_decode_ws_bytes / pa_decode_beam_ws_bytes (include/plank_hip.h): no handle, no device, no launch.
+extern "C" int pa_decode_plan(const pa_model_cfg* cfg, int32_t B, int32_t S, int32_t Tmax, pa_decode_plan_info* out) {
+    if (!cfg || !out) return PA_EINVAL;
+    *out = pa_decode_plan_info();
+    const DecodePlan pl = plan_decode(*cfg, B, S, Tmax, decode_switches());
+    if (!pl.status) *out = pl;
+    return pl.status;
 }
 
 // Requires a preceding encoder-only pa_model_train_fwd (batch.output_value == NULL) on the same stream:
@@ -1481,28 +1500,27 @@ extern "C" int64_t pa_decode_ws_bytes(pa_model* m, int32_t B, int32_t S, int32_t
 extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t Tmax, void* stream) {
     if (!m || !m->bound || !ws || m->B <= 0 || Tmax <= 0 || Tmax > MAX_T) return PA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return PA_EALIGN;
+    const pa_model_cfg& c = m->cfg;
+    const DecodePlan pl = plan_decode(c, m->B, m->S, Tmax, decode_switches());
+    if (pl.status) return pl.status;
+    if (pl.ws_bytes - 256 > ws_bytes) return PA_EINVAL;
     if (!m->dec) m->dec = new (std::nothrow) DecodeLayout();
     if (!m->dec) return PA_EINVAL;
     DecodeLayout* L = m->dec;
-    const size_t need = dec_layout(m, L, (char*)ws, m->B, m->S, Tmax);
-    if ((int64_t)need > ws_bytes) return PA_EINVAL;
-    const pa_model_cfg& c = m->cfg;
+    L->plan = pl;
+    dec_layout(c, pl, L, (char*)ws, m->B, m->S, Tmax);
     const int d = c.d_model, B = m->B, S = m->S;
     const size_t e = c.dtype == PA_BF16 ? 2 : 4;
     const void* memory = c.has_enc_norm ? m->memory : m->X[c.n_enc];
     hipStream_t s = (hipStream_t)stream;
-    const DecodeModes md = decode_modes(c, B, S);
-    const StepForm sf = step_form(c, B, S, Tmax);
-    L->fold = md.fold; L->f32res = md.f32res; L->mq = md.mq;           // (what each is and where it was measured: decode_modes)
-    L->mq_contract = sf.mq_contract; L->mq_self = sf.mq_self; L->mq_self_bf = sf.mq_self_bf;   // (step_form)
     L->beamK = 0; L->sampleN = 0;                               // greedy until pa_decode_beam_begin / pa_decode_sample_begin
     L->px_on = false;                                           // and no forced prefix until pa_decode_prefix_begin
     L->cs_on = false;                                           // and no constraint until pa_decode_constraint_set
-    if (L->mq) {
+    if (pl.mq) {
         // absorbed cross-attention: the step reads the encoder output rows themselves - no K / V projection of the memory at all
         HIP_RC(hipMemcpyAsync(L->mem, memory, (size_t)m->NE * d * e, hipMemcpyDeviceToDevice, s));
     }
-    for (int i = 0; i < c.n_dec && !L->mq; ++i) {       // cross-attention K/V of the memory: once per sequence, not per step
+    for (int i = 0; i < c.n_dec && !pl.mq; ++i) {       // cross-attention K/V of the memory: once per sequence, not per step
         const int pb = m->dec_base(i);
         RC(linear(m, memory, (const char*)m->pl[pb + D_CA_IN_W] + (size_t)d * d * e, (const float*)m->pf[pb + D_CA_IN_B] + d,
                   L->kv_tmp, 2 * d, m->NE, 2 * d, d, 0, nullptr, -1, stream));
@@ -1513,8 +1531,8 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
             PA_LAUNCH(dec_split_heads_kernel<float>, dim3(2048), dim3(256), 0, s, (float*)L->cross_k[i], (float*)L->cross_v[i],
                       (const float*)L->kv_tmp, (int64_t)m->NE, S, d, c.n_head, m->batch.cu_in, m->batch.rowmap);
     }
-    const bool fold32 = L->fold && c.dtype == PA_F32;
-    if (L->fold) {
+    const bool fold32 = pl.fold && c.dtype == PA_F32;
+    if (pl.fold) {
         for (int i = 0; i < c.n_dec; ++i) {
             const int pb = m->dec_base(i);
             auto F = [&](int idx) { return (const float*)m->pf[idx]; };
@@ -1527,18 +1545,18 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
                 RC(foldw(L->fw[0][i], L->fu[0][i], L->fv[0][i], F(pb + D_SA_IN_W), F(pb + D_SA_IN_B), F(pp + D_N3_W), F(pp + D_N3_B), 3 * d));
             }
             RC(foldw(L->fw[1][i], L->fu[1][i], L->fv[1][i], F(pb + D_CA_IN_W), F(pb + D_CA_IN_B), F(pb + D_N1_W), F(pb + D_N1_B), d));
-            if (L->mq && L->mq_contract) {     // the head-transposed copy of W_v for mq_contract_v_kernel (in the wo_t buffer, unused in this form)
+            if (pl.mq && pl.mq_contract) {     // the head-transposed copy of W_v for mq_contract_v_kernel (in the wo_t buffer, unused in this form)
                 if (c.dtype == PA_BF16)
                     PA_LAUNCH(mq_transpose_v_kernel<bf16>, dim3(1024), dim3(256), 0, s, (bf16*)L->wo_t[i], (const bf16*)m->pl[pb + D_CA_IN_W] + (size_t)2 * d * d, d, c.n_head);
                 else
                     PA_LAUNCH(mq_transpose_v_kernel<float>, dim3(1024), dim3(256), 0, s, (float*)L->wo_t[i], (const float*)m->pl[pb + D_CA_IN_W] + (size_t)2 * d * d, d, c.n_head);
             }
-            if (L->mq_self)
+            if (pl.mq_self)
                 PA_LAUNCH(mq_transpose_v_kernel<float>, dim3(1024), dim3(256), 0, s, (float*)L->wvt_self[i], (const float*)m->pl[pb + D_SA_IN_W] + (size_t)2 * d * d, d, c.n_head);
-            if (L->mq_self_bf)
+            if (pl.mq_self_bf)
                 PA_LAUNCH(mq_absorb_o_kernel<bf16>, dim3(d), dim3(256), 0, s, (bf16*)L->wo_ts[i], L->bo_ts[i], F(pb + D_SA_OUT_W), F(pb + D_SA_OUT_B),
                           F(pb + D_SA_IN_W), F(pb + D_SA_IN_B), d, c.n_head);
-            if (L->mq && !L->mq_contract) {    // W~o = W_o,h W_v,h, b~o = b_o + W_o b_v for the Linear behind the absorbed attention (csrc/decode_mq.h)
+            if (pl.mq && !pl.mq_contract) {    // W~o = W_o,h W_v,h, b~o = b_o + W_o b_v for the Linear behind the absorbed attention (csrc/decode_mq.h)
                 if (c.dtype == PA_BF16)
                     PA_LAUNCH(mq_absorb_o_kernel<bf16>, dim3(d), dim3(256), 0, s, (bf16*)L->wo_t[i], L->bo_t[i], F(pb + D_CA_OUT_W), F(pb + D_CA_OUT_B),
                               F(pb + D_CA_IN_W), F(pb + D_CA_IN_B), d, c.n_head);
@@ -1568,40 +1586,11 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
 
 extern "C" int pa_decode_step(pa_model* m, void* stream) {
     if (!m || !m->dec || m->dec->B <= 0) return PA_EINVAL;
-    return m->cfg.dtype == PA_BF16 ? step_impl<bf16>(m, stream) : step_impl<float>(m, stream);
+    return m->cfg.dtype == PA_BF16 ? decode_step<bf16>(m, stream) : decode_step<float>(m, stream);
 }
 
-// Two half-batches of one decode ("lanes" A and B: two handles over the same parameters, each with its own pa_decode_begin
-// state) advance one step on two streams with their attention launches strictly alternating: A's k-th attention, B's k-th,
-// A's (k+1)-th ...  While one lane streams its K/V caches, the other runs the latency-bound launches between two attentions;
-// without the alternation both lanes reach their attention launches together and only share the HBM bandwidth
-// (measured: 6.6 % overlap, +1 %).  MEASURED SLOWER than the unsynchronised lanes on MI355X / ROCm 7.2 (B 256: 2.15 ms per step
-// against 1.23): the 24 cross-queue event edges per step cost more than the overlap they arrange, so the host side keeps it
-// behind PLANK_DECODE_ALTERNATE=1.  Works eagerly and under stream capture (stream_b must already be forked from stream_a's
-// capture; the caller joins them afterwards).  No reference counterpart (models.py:267-323 decodes one batch serially).
-extern "C" int pa_decode_step_pair(pa_model* a, pa_model* b, void* stream_a, void* stream_b) {
-    if (!a || !b || !a->dec || !b->dec || a->dec->B <= 0 || b->dec->B <= 0) return PA_EINVAL;
-    if (a->cfg.n_dec != b->cfg.n_dec || a->cfg.dtype != b->cfg.dtype) return PA_EINVAL;
-    if (a->dec->beamK > 0 || b->dec->beamK > 0) return PA_EINVAL;     // beams run as one lane
-    if (a->dec->sampleN > 0 || b->dec->sampleN > 0) return PA_EINVAL; // so does sampling
-    if (a->dec->px_on || b->dec->px_on) return PA_EINVAL;             // and a decode with a forced prefix
-    if (a->dec->cs_on || b->dec->cs_on) return PA_EINVAL;             // or a constraint
-    const int n = 2 * a->cfg.n_dec;
-    std::vector<hipEvent_t>& ev = a->dec->pair_ev;
-    if ((int)ev.size() != 2 * n) {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        ev.assign(2 * n, nullptr);
-        for (int i = 0; i < 2 * n; ++i)
-            if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) { ev.clear(); return PA_EINVAL; }
-    }
-    for (int k = 0; k < n; ++k) {
-        RC(step_part_any(a, k, stream_a, k > 0 ? ev[n + k - 1] : nullptr, ev[k]));      // after B's attention k - 1
-        RC(step_part_any(b, k, stream_b, ev[k], ev[n + k]));                              // after A's attention k
-    }
-    RC(step_part_any(a, n, stream_a, nullptr, nullptr));
-    RC(step_part_any(b, n, stream_b, nullptr, nullptr));
-    return 0;
-}
+// range blocks of a stand-alone absorbed launch: what the step would take for (B, S)
+static int standalone_parts(int B, int S) { return mq_parts(B, S, decode_switches().mq_parts, decode_switches().mq_mint); }
 
 // The absorbed cross-attention launch on its own (csrc/decode_mq.h; kernel tests / tools): ctx [B][H][512] (bf16) = per head the
 // softmax(qt_h . m_s)-weighted sum of the memory rows m_s; qt [B][H][512] carries scale * log2 e; mem [rows][512] bf16 - dense
@@ -1610,39 +1599,42 @@ extern "C" int pa_dec_cross_mq(void* ctx, const void* qt, const void* mem, const
                                int32_t S, int32_t H, int32_t d, void* stream) {
     if (!ctx || !qt || !mem) return PA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(qt) | reinterpret_cast<uintptr_t>(mem)) & 15) return PA_EALIGN;
-    return launch_cross_mq((bf16*)ctx, (const bf16*)qt, (const bf16*)mem, kpm, cu, B, S, H, d, (hipStream_t)stream);
+    return launch_cross_mq((bf16*)ctx, (const bf16*)qt, (const bf16*)mem, kpm, cu, B, S, H, d, (hipStream_t)stream, 1, decode_switches().mq_nt,
+                           decode_switches().mq_swap);
 }
 
 // The same launch with scratch for range blocks (decode_mq.h: at small batches a batch element's keys are walked by several blocks so
 // that the launch uses the whole chip).  ws: pa_dec_cross_mq_ws_bytes(B, S) bytes, 256-byte aligned, its first ceil(4 B / 256) * 256
 // bytes zero before the first launch (launches leave them zero); with ws = NULL or too small it is pa_dec_cross_mq.
-extern "C" int64_t pa_dec_cross_mq_ws_bytes(int32_t B, int32_t S) { return (B > 0 && S > 0) ? mq_split_bytes(B, mq_parts(B, S)) : 0; }
+extern "C" int64_t pa_dec_cross_mq_ws_bytes(int32_t B, int32_t S) { return (B > 0 && S > 0) ? mq_split_bytes(B, standalone_parts(B, S)) : 0; }
 extern "C" int pa_dec_cross_mq_ws(void* ctx, const void* qt, const void* mem, const uint8_t* kpm, const int32_t* cu, int32_t B,
                                   int32_t S, int32_t H, int32_t d, void* ws, int64_t ws_bytes, void* stream) {
     if (!ctx || !qt || !mem) return PA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(qt) | reinterpret_cast<uintptr_t>(mem)) & 15) return PA_EALIGN;
-    return launch_cross_mq((bf16*)ctx, (const bf16*)qt, (const bf16*)mem, kpm, cu, B, S, H, d, (hipStream_t)stream, ws, ws_bytes);
+    return launch_cross_mq((bf16*)ctx, (const bf16*)qt, (const bf16*)mem, kpm, cu, B, S, H, d, (hipStream_t)stream, standalone_parts(B, S),
+                           decode_switches().mq_nt, decode_switches().mq_swap, ws, ws_bytes);
 }
 
 extern "C" int pa_dec_cross_mq32(float* ctx, const float* qt, const float* mem, const uint8_t* kpm, const int32_t* cu, int32_t B,
                                  int32_t S, int32_t H, int32_t d, void* stream) {
     if (!ctx || !qt || !mem) return PA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(qt) | reinterpret_cast<uintptr_t>(mem) | reinterpret_cast<uintptr_t>(ctx)) & 15) return PA_EALIGN;
-    return launch_cross_mq32(ctx, qt, mem, kpm, cu, B, S, H, d, (hipStream_t)stream);
+    return launch_cross_mq32(ctx, qt, mem, kpm, cu, B, S, H, d, (hipStream_t)stream, 1, decode_switches().mq32_w8);
 }
 
 extern "C" int pa_dec_cross_mq32_ws(float* ctx, const float* qt, const float* mem, const uint8_t* kpm, const int32_t* cu, int32_t B,
                                     int32_t S, int32_t H, int32_t d, void* ws, int64_t ws_bytes, void* stream) {
     if (!ctx || !qt || !mem) return PA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(qt) | reinterpret_cast<uintptr_t>(mem) | reinterpret_cast<uintptr_t>(ctx)) & 15) return PA_EALIGN;
-    return launch_cross_mq32(ctx, qt, mem, kpm, cu, B, S, H, d, (hipStream_t)stream, nullptr, ws, ws_bytes);
+    return launch_cross_mq32(ctx, qt, mem, kpm, cu, B, S, H, d, (hipStream_t)stream, standalone_parts(B, S), decode_switches().mq32_w8, nullptr, ws,
+                             ws_bytes);
 }
 
 extern "C" int pa_dec_self_mq32(float* ctx, const float* qt, const float* xcache, const int32_t* t_dev, int32_t B, int32_t Tmax,
                                 int32_t H, int32_t d, void* stream) {
     if (!ctx || !qt || !xcache || !t_dev) return PA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(qt) | reinterpret_cast<uintptr_t>(xcache) | reinterpret_cast<uintptr_t>(ctx)) & 15) return PA_EALIGN;
-    return launch_cross_mq32(ctx, qt, xcache, nullptr, nullptr, B, Tmax, H, d, (hipStream_t)stream, t_dev);
+    return launch_cross_mq32(ctx, qt, xcache, nullptr, nullptr, B, Tmax, H, d, (hipStream_t)stream, 1, decode_switches().mq32_w8, t_dev);
 }
 
 extern "C" int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void** first_end, void** t_dev) {
@@ -1653,11 +1645,10 @@ extern "C" int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void
 
 // Beam search over a begun decode (include/plank_hip.h).
 extern "C" int64_t pa_decode_beam_ws_bytes(pa_model* m, int32_t rows, int32_t S, int32_t Tmax, int32_t K) {
-    if (!m || K < 1 || K > PA_BEAM_MAX || rows <= 0 || rows % K != 0 || S <= 0 || Tmax <= 0 || Tmax > MAX_T) return PA_EINVAL;
-    BeamCopy cp;
-    const int64_t scr = beam_segments(m->cfg, step_form(m->cfg, rows, S, Tmax), nullptr, rows, Tmax, &cp);
-    if (scr < 0) return scr;
-    return (int64_t)beam_layout(nullptr, nullptr, rows, K, scr) + 256;
+    if (!m || K < 1 || K > PA_BEAM_MAX || rows <= 0 || rows % K != 0) return PA_EINVAL;
+    const DecodePlan pl = plan_decode(m->cfg, rows, S, Tmax, decode_switches());
+    if (pl.status || pl.scr_row < 0) return pl.status ? pl.status : pl.scr_row;
+    return (int64_t)beam_layout(nullptr, nullptr, rows, K, pl.scr_row) + 256;
 }
 
 extern "C" int pa_decode_beam_begin(pa_model* m, int32_t K, void* ws, int64_t ws_bytes, void* stream) {
@@ -1665,8 +1656,7 @@ extern "C" int pa_decode_beam_begin(pa_model* m, int32_t K, void* ws, int64_t ws
     if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return PA_EALIGN;
     DecodeLayout* L = m->dec;
     const int rows = L->B;
-    const StepForm sf{L->mq_contract, L->mq_self, L->mq_self_bf};
-    const int64_t scr = beam_segments(m->cfg, sf, L, rows, L->Tmax, &L->bm_copy);
+    const int64_t scr = beam_segments(m->cfg, L->plan, L, rows, L->Tmax, &L->bm_copy);
     if (scr < 0) return (int)scr;
     if ((int64_t)beam_layout(nullptr, nullptr, rows, K, scr) > ws_bytes) { L->beamK = 0; return PA_EINVAL; }
     beam_layout(L, (char*)ws, rows, K, scr);

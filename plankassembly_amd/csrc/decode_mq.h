@@ -740,11 +740,9 @@ __global__ __launch_bounds__(256) void mq_absorb_o_kernel(T* Wt, float* bt, cons
     }
 }
 
-// range blocks per batch element for a launch of B elements with up to S keys: enough blocks to fill the chip, at least
-// PLANK_DECODE_MQ_MINT (8) key tiles each; PLANK_DECODE_MQ_PARTS=<n> forces, 1 = never
-int mq_parts(int B, int S) {
-    static const int force = getenv("PLANK_DECODE_MQ_PARTS") ? atoi(getenv("PLANK_DECODE_MQ_PARTS")) : 0;
-    static const int mint = getenv("PLANK_DECODE_MQ_MINT") ? atoi(getenv("PLANK_DECODE_MQ_MINT")) : 8;
+// range blocks per batch element for a launch of B elements with up to S keys: enough blocks to fill the chip, at least `mint` key
+// tiles each (DecodeSwitches::mq_mint); `force` > 0 (DecodeSwitches::mq_parts) replaces the rule, at most 64 either way
+int mq_parts(int B, int S, int force, int mint) {
     if (force > 0) return force > 64 ? 64 : force;
     const int ntiles = (S + MQ_KT - 1) / MQ_KT;
     int p = 256 / (B > 0 ? B : 1);
@@ -753,13 +751,12 @@ int mq_parts(int B, int S) {
 }
 int64_t mq_split_bytes(int B, int nparts) { return nparts > 1 ? (((int64_t)B * 4 + 255) / 256) * 256 + (int64_t)B * nparts * MQ_SP_BYTES : 0; }
 
+// The two launches take their choices from the caller: `nparts` range blocks per element (1 when the scratch `sp` cannot hold them),
+// `nt` / `swap` / `w8` the kernel variants (DecodeSwitches).
 int launch_cross_mq(bf16* ctx, const bf16* qt, const bf16* mem, const uint8_t* kpm, const int32_t* cu, int B, int S, int H, int d,
-                    hipStream_t s, void* sp = nullptr, int64_t sp_bytes = 0, const int32_t* t_dev = nullptr) {
+                    hipStream_t s, int nparts, int nt, int swap, void* sp = nullptr, int64_t sp_bytes = 0, const int32_t* t_dev = nullptr) {
     if (d != MQ_D || H < 1 || H > MQ_MAXH || B <= 0 || S <= 0 || S > MQ_MAXS) return PA_ESHAPE;
     const int lds = MQ_NS * MQ_TILE + ((!cu && kpm) ? (S + 31) / 16 * 16 : 0);
-    // PLANK_DECODE_MQ_NT=0: default-policy DMA instead of non-temporal (aux 2; measured in the step, B 256 x 1024: 0.958 vs 0.989 ms); PLANK_DECODE_MQ_SWAP=0: ds_bpermute row reductions instead of v_permlane*_swap
-    static const int nt = getenv("PLANK_DECODE_MQ_NT") ? atoi(getenv("PLANK_DECODE_MQ_NT")) : 1;
-    static const int swap = getenv("PLANK_DECODE_MQ_SWAP") ? atoi(getenv("PLANK_DECODE_MQ_SWAP")) : 1;
     static bool attr_done = false;
     constexpr int MAXLDS = MQ_NS * MQ_TILE + MQ_MAXS + 32;
     typedef void (*KernT)(bf16*, const bf16*, const bf16*, const uint8_t*, const int32_t*, int, int, int, char*, const int32_t*);
@@ -774,20 +771,17 @@ int launch_cross_mq(bf16* ctx, const bf16* qt, const bf16* mem, const uint8_t* k
         attr_done = true;
     }
     const bool mask = !cu && kpm;
-    int nparts = sp ? mq_parts(B, S) : 1;
-    if (nparts > 1 && (mq_split_bytes(B, nparts) > sp_bytes || (reinterpret_cast<uintptr_t>(sp) & 255))) nparts = 1;
+    if (nparts < 1 || !sp || mq_split_bytes(B, nparts) > sp_bytes || (reinterpret_cast<uintptr_t>(sp) & 255)) nparts = 1;
     PA_LAUNCH(ks[(nt ? 4 : 0) + (swap ? 2 : 0) + (mask ? 1 : 0)], dim3(B * nparts), dim3(256), lds, s, ctx, qt, mem, kpm, cu, S, H, nparts,
               static_cast<char*>(sp), t_dev);
     return 0;
 }
 
 int launch_cross_mq32(float* ctx, const float* qt, const float* mem, const uint8_t* kpm, const int32_t* cu, int B, int S, int H, int d,
-                      hipStream_t s, const int32_t* t_dev = nullptr, void* sp = nullptr, int64_t sp_bytes = 0) {
+                      hipStream_t s, int nparts, int w8, const int32_t* t_dev = nullptr, void* sp = nullptr, int64_t sp_bytes = 0) {
     constexpr int MAXS32 = 16000;                 // (ring + partial-score slots + mask bytes within 160 KB)
     if (d != MQ_D || H < 1 || H > MQ_MAXH || B <= 0 || S <= 0 || S > MAXS32) return PA_ESHAPE;
     const bool mask = !cu && kpm;
-    // PLANK_DECODE_MQ32_W8=0: the four-wave kernel (one wave per SIMD) instead of eight waves with skewed halves
-    static const int w8 = getenv("PLANK_DECODE_MQ32_W8") ? atoi(getenv("PLANK_DECODE_MQ32_W8")) : 1;
     static bool attr_done = false;
     if (!attr_done) {
         constexpr int MAXLDS = MQF_NS * MQF_TILE + MQ8_SCR + MAXS32 + 32;
@@ -802,8 +796,7 @@ int launch_cross_mq32(float* ctx, const float* qt, const float* mem, const uint8
     const int mbytes = mask ? (S + 31) / 16 * 16 : 0;
     if (w8) {
         const int lds = MQF_NS * MQF_TILE + MQ8_SCR + mbytes;
-        int nparts = sp ? mq_parts(B, S) : 1;
-        if (nparts > 1 && (mq_split_bytes(B, nparts) > sp_bytes || (reinterpret_cast<uintptr_t>(sp) & 255))) nparts = 1;
+        if (nparts < 1 || !sp || mq_split_bytes(B, nparts) > sp_bytes || (reinterpret_cast<uintptr_t>(sp) & 255)) nparts = 1;
         if (mask) PA_LAUNCH(dec_cross_mq32w8_kernel<true>, dim3(B * nparts), dim3(512), lds, s, ctx, qt, mem, kpm, cu, S, H, t_dev, nparts, static_cast<char*>(sp));
         else PA_LAUNCH(dec_cross_mq32w8_kernel<false>, dim3(B * nparts), dim3(512), lds, s, ctx, qt, mem, kpm, cu, S, H, t_dev, nparts, static_cast<char*>(sp));
     } else {

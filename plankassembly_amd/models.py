@@ -482,17 +482,20 @@ class PlankModel(nn.Module):
     def _pa_activation(self):
         return {"relu": 1, "gelu": 2}[self.activation]
 
+    def _cfg_struct(self):
+        """The pa_model_cfg of this model (pa_model_create; pa_decode_plan takes the same block)."""
+        rows = (C.c_int32 * 5)(*[self._shapes[f"input_embeddings.{k}.weight"][0] for k in INPUT_KEYS])
+        return _ModelCfg(self.num_model, self.num_head, self.num_feedforward, self.num_encoder_layers,
+                         self.num_decoder_layers, self.vocab_size, self.num_output_dof, rows, self.eps_layer, 1e-5,
+                         int(self.has_enc_norm), self.dropout, int(self.token.PAD), int(self.token.END),
+                         self._pa_dtype(), self._pa_activation())
+
     def _ensure_handle(self):
         self._require_gpu()
         if self._handle is not None:
             return
-        rows = (C.c_int32 * 5)(*[self._shapes[f"input_embeddings.{k}.weight"][0] for k in INPUT_KEYS])
-        cfg = _ModelCfg(self.num_model, self.num_head, self.num_feedforward, self.num_encoder_layers,
-                        self.num_decoder_layers, self.vocab_size, self.num_output_dof, rows, self.eps_layer, 1e-5,
-                        int(self.has_enc_norm), self.dropout, int(self.token.PAD), int(self.token.END),
-                        self._pa_dtype(), self._pa_activation())
         h = C.c_void_p()
-        L.check(L.lib().pa_model_create(C.byref(cfg), C.byref(h)), "pa_model_create")
+        L.check(L.lib().pa_model_create(C.byref(self._cfg_struct()), C.byref(h)), "pa_model_create")
         self._handle = h
         self._rebind()
 
@@ -501,13 +504,8 @@ class PlankModel(nn.Module):
         two halves of a decode batch run as independent kernel streams (decode.GreedyDecoder lanes).  The caller owns it
         (pa_model_destroy)."""
         self._ensure_handle()
-        rows = (C.c_int32 * 5)(*[self._shapes[f"input_embeddings.{k}.weight"][0] for k in INPUT_KEYS])
-        cfg = _ModelCfg(self.num_model, self.num_head, self.num_feedforward, self.num_encoder_layers,
-                        self.num_decoder_layers, self.vocab_size, self.num_output_dof, rows, self.eps_layer, 1e-5,
-                        int(self.has_enc_norm), self.dropout, int(self.token.PAD), int(self.token.END), self._pa_dtype(),
-                        self._pa_activation())
         h = C.c_void_p()
-        L.check(L.lib().pa_model_create(C.byref(cfg), C.byref(h)), "pa_model_create")
+        L.check(L.lib().pa_model_create(C.byref(self._cfg_struct()), C.byref(h)), "pa_model_create")
         pf = self._ptr_table(self._flat, 4)
         pl = self._ptr_table(self._shadow, 2) if self.compute_dtype == "bf16" else pf
         L.check(L.lib().pa_model_bind(h, pf, pl, None), "pa_model_bind")
