@@ -501,6 +501,35 @@ int pa_mixture_nll_bwd_up(void* dvocab, void* dptr, int32_t out_dtype, float* ds
                        const float* row_lse, const float* vocab, int32_t ldv, const float* ptr, const float* sw,
                        const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad, float gscale,
                        const float* upstream, void* stream);
+/* The EXTENDED objective: label smoothing, a weight per drawing or per token, and the plain -log p(label) per token (reference
+ * plankassembly/models.py:219-227 is the case smoothing 0, no weight).  Row (b, i), label y, log p the training distribution of the
+ * entries above (pointer logits j >= i hold the VALUE 1e-6 and stay in lse_p):
+ *   plain  = -log p_y
+ *   smooth = -(1 / C_i) sum over the ALLOWED classes {k < V} and {V + j : j < i} of log p_c,  C_i = V + i  (the filled pointers get no mass)
+ *   ell    = (1 - eps) plain + eps smooth              (eps == 0: smooth is never formed)
+ *   loss   = sum over non-PAD rows of w ell / N,       N = #non-PAD labels, w = weight[b] or weight[b][i] (1 without weights; any finite f32;
+ *            a row of weight 0 adds exactly 0 and gets exactly zero gradients)
+ * stats8 as pa_mixture_nll_fwd_fin, with [0] / [4] / [6..7] the objective sum w ell, the loss and its fixed-point word; count, hits and the
+ * accuracy are unweighted and unsmoothed.  ext_stats receives the plain sum of -log p_y and its mean over N; token_nll the per-row plain value.
+ * With smoothing 0 and weight NULL every stats8 / row_lse / gradient bit is that of pa_mixture_nll_fwd_fin / pa_mixture_nll_bwd_up.
+ * The backward needs row_lse and stats8 only: G = gscale upstream / N w, and with eps > 0 BOTH parts of a row get a gradient
+ * (d x_k = G [(1 - eps) ([y < V] softmax_v(k) - [k == y]) + eps / C_i (V softmax_v(k) - 1)], likewise the pointers j < i with i in place of V).
+ * PA_EINVAL, nothing launched: smoothing outside [0, 1) or NaN, ext_stats NULL or not 8-byte aligned, weight_per_token not 0 / 1. */
+typedef struct {
+    float smoothing;            /* eps in [0, 1) */
+    int32_t weight_per_token;   /* 0: weight is f32 [B];  1: f32 [B][T] */
+    const float* weight;        /* NULL: every weight 1 */
+    float* token_nll;           /* NULL, or f32 [B][T]: -log p(label), 0 at PAD rows */
+    float* ext_stats;           /* f32[4], 8-byte aligned, zeroed by the launch: [0..1] int64 plain NLL sum in 2^-30 units, [2] plain mean, [3] 0 */
+} pa_loss_ext;
+int64_t pa_loss_ext_bytes(void);
+int pa_mixture_nll_fwd_ext(float* stats8, float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
+                           const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
+                           const pa_loss_ext* e, void* stream);
+int pa_mixture_nll_bwd_ext(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, const float* stats,
+                           const float* row_lse, const float* vocab, int32_t ldv, const float* ptr, const float* sw,
+                           const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad, float gscale,
+                           const float* upstream, const pa_loss_ext* e, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Adam (torch.optim.Adam defaults; reference trainer_complete.py:127-129), fused over one flat
@@ -680,6 +709,10 @@ int pa_model_train_fwd(pa_model* m, const pa_batch* batch, void* ws, int64_t ws_
  * last segment) - the host can launch their all-reduce on a side stream. */
 /* d(loss) of the next pa_model_train_bwd calls is read from `upstream` (device f32 scalar; NULL = the stats block's own slot). */
 int pa_model_set_upstream(pa_model* m, const float* upstream);
+/* The objective of the next pa_model_train_fwd / pa_model_train_bwd calls: the block is COPIED (its pointers must stay valid until the
+ * backward has been enqueued) and holds until set again; NULL = off, the calls of pa_mixture_nll_fwd_fin / pa_mixture_nll_bwd_up.  stats[4]
+ * is then the extended loss.  PA_EINVAL for a block the _ext entries would reject. */
+int pa_model_set_loss(pa_model* m, const pa_loss_ext* e);
 int pa_model_train_num_segments(const pa_model* m);
 int pa_model_train_bwd(pa_model* m, int32_t seg_lo, int32_t seg_hi, float gscale, void* stream);
 /* Gradient finality lag in segments.  With PA_SIDE_STREAM=1 (experimental, off by default: slower on MI355X) the model

@@ -116,6 +116,13 @@ class AdamExtArgs(C.Structure):
                 ("clip_value", C.c_float), ("weight_decay", C.c_float), ("ema_decay", C.c_float),
                 ("step", C.c_int32), ("ema_warmup", C.c_int32), ("ctl", C.c_void_p)]
 
+
+class LossExt(C.Structure):
+    """include/plank_hip.h pa_loss_ext (pa_mixture_nll_fwd_ext / _bwd_ext, pa_model_set_loss); sizeof == pa_loss_ext_bytes()."""
+    _fields_ = [("smoothing", C.c_float), ("weight_per_token", C.c_int32), ("weight", C.c_void_p), ("token_nll", C.c_void_p),
+                ("ext_stats", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -209,6 +216,10 @@ def lib():
             "pa_mixture_nll_bwd": (I, [P, P, I, P, P, P, P, I, P, P, P, I, I, I, I, F, P]),
             "pa_mixture_nll_fwd_fin": (I, [P, P, P, I, P, P, P, I, I, I, I, P]),
             "pa_mixture_nll_bwd_up": (I, [P, P, I, P, P, P, P, I, P, P, P, I, I, I, I, F, P, P]),
+            "pa_loss_ext_bytes": (I64, []),
+            "pa_mixture_nll_fwd_ext": (I, [P, P, P, I, P, P, P, I, I, I, I, P, P]),
+            "pa_mixture_nll_bwd_ext": (I, [P, P, I, P, P, P, P, I, P, P, P, I, I, I, I, F, P, P, P]),
+            "pa_model_set_loss": (I, [P, P]),
             "pa_model_set_upstream": (I, [P, P]),
             "pa_adam_step": (I, [P, P, P, P, P, I64, F, F, F, F, I, F, P]),
             "pa_grad_guard_ws_bytes": (I64, []),

@@ -59,6 +59,7 @@ struct pa_model {
     // words are zeroed whenever the region moved or changed size (pa_model_train_fwd)
     void* attn_ws = nullptr; int64_t attn_ws_bytes = 0; void* attn_ws_zeroed = nullptr; int64_t attn_ws_zeroed_bytes = 0;
     const float* upstream = nullptr;      // d(loss) of the caller's autograd (pa_model_set_upstream), or nullptr = stats[3]
+    bool loss_on = false; pa_loss_ext loss{};   // the extended objective (pa_model_set_loss); off = the calls of the reference-parity step
     // backward temporaries
     void *gA, *gB, *gC, *gD, *gE, *gF, *gQ3, *gKV, *dmem, *dvlog, *dplog; float *dsw, *delta, *partial, *splitws;
     void* gPre = nullptr;                        // ACTIVATION gelu: the FFN pre-activation, recomputed by the backward pass (rows x d_ff)

@@ -849,6 +849,168 @@ __global__ __launch_bounds__(256) void mixture_nll_bwd_kernel(TO* dvocab, TO* dp
     }
 }
 
+// ---- extended objective (include/plank_hip.h pa_loss_ext): label smoothing over the ALLOWED classes of a row
+// (the V vocabulary entries and the i pointers j < i - the filled pointers get no mass), a weight per drawing or per token, and the
+// plain -log p(label) per token next to the objective.  Same shape as the pair above: one wave per row, NLL_ROWS rows per block, the
+// slot arrays when V <= 1024 && T <= 256.  No load sits under a range test here: row, label, weight and logit indices are clamped, every
+// load is issued, and what is out of range is discarded in the arithmetic.  With eps == 0 and no weight every operation that reaches an
+// output is the one the kernels above do, so the outputs are theirs bit for bit (tests/test_loss_ext_gpu.py).
+__global__ __launch_bounds__(256) void mixture_nll_ext_fwd_kernel(float* stats, float* row_lse, const float* vocab, int ldv,
+                                                                  const float* ptr, const float* sw, const int64_t* label,
+                                                                  int B, int Tn, int V, int pad, float eps, const float* weight,
+                                                                  int per_token, float* token_nll, float* ext_stats) {
+    __shared__ float red[4][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t n = (int64_t)B * Tn;
+    float a_obj = 0.f, a_cnt = 0.f, a_hit = 0.f, a_nll = 0.f;
+    for (int rr = wave; rr < NLL_ROWS; rr += 4) {
+        const int64_t row_raw = (int64_t)blockIdx.x * NLL_ROWS + rr;
+        const bool in_rows = row_raw < n;
+        const int64_t row = in_rows ? row_raw : n - 1;
+        const int i = (int)(row % Tn);
+        const float* vr = vocab + row * ldv;
+        const float* pr = ptr + row * Tn;
+        const int64_t lab = label[row];
+        const float w = weight ? weight[per_token ? row : row / Tn] : 1.f;
+        const int kl = (int)(lab < 0 ? 0 : (lab < V ? lab : V - 1));
+        const int64_t jl64 = lab - V;
+        const int jl = (int)(jl64 < 0 ? 0 : (jl64 < Tn ? jl64 : Tn - 1));
+        const float x_lab = vr[kl], z_lab = pr[jl], s_row = sw[row];
+        RowStat sv{-INFINITY, 0.f, 0x7fffffff}, sp{-INFINITY, 0.f, 0x7fffffff};
+        float sum_x = 0.f, sum_z = 0.f;                          // sum_k x_k and sum_{j<i} z_j of this lane's entries (smoothing)
+        if (V <= 64 * NLL_VSLOTS && Tn <= 64 * NLL_PSLOTS) {
+            float xv[NLL_VSLOTS], xp[NLL_PSLOTS];
+#pragma unroll
+            for (int q = 0; q < NLL_VSLOTS; ++q) xv[q] = vr[min(lane + 64 * q, V - 1)];
+#pragma unroll
+            for (int q = 0; q < NLL_PSLOTS; ++q) xp[q] = pr[min(lane + 64 * q, Tn - 1)];
+#pragma unroll
+            for (int q = 0; q < NLL_VSLOTS; ++q) { const int k = lane + 64 * q; if (k < V) { online(sv, xv[q], k); sum_x += xv[q]; } }
+#pragma unroll
+            for (int q = 0; q < NLL_PSLOTS; ++q) {
+                const int j = lane + 64 * q;
+                if (j < Tn) { online(sp, (j >= i) ? 1e-6f : xp[q], j); sum_z += (j >= i) ? 0.f : xp[q]; }
+            }
+        } else {
+            for (int k = lane; k < V; k += 64) { const float x = vr[k]; online(sv, x, k); sum_x += x; }
+            for (int j = lane; j < Tn; j += 64) { const float z = pr[j]; online(sp, (j >= i) ? 1e-6f : z, j); sum_z += (j >= i) ? 0.f : z; }
+        }
+        sv = wave_merge(sv);
+        sp = wave_merge(sp);
+        const float lse_v = sv.m + logf(sv.s), lse_p = sp.m + logf(sp.s);
+        const float prob = 1.0f / (1.0f + expf(-s_row));
+        const float lv = logf(fmaxf(1.0f - prob, 1e-6f)), lp = logf(fmaxf(prob, 1e-6f));
+        float smooth = 0.f;
+        if (eps > 0.f) {                                         // (eps == 0 never forms it: 0 * inf would poison a row that is fine without)
+            sum_x = wave_sum(sum_x);
+            sum_z = wave_sum(sum_z);
+            const float Vf = (float)V, If = (float)i;
+            const float av = (sum_x - Vf * lse_v) + Vf * lv, ap = (sum_z - If * lse_p) + If * lp;
+            smooth = -(av + ap) / (Vf + If);
+        }
+        const bool valid = in_rows && lab != pad;
+        float logp;
+        if (lab < V) logp = x_lab - lse_v + lv;
+        else { const int j = (int)(lab - V); logp = ((j >= i) ? 1e-6f : z_lab) - lse_p + lp; }
+        if (lane == 0 && in_rows) {
+            row_lse[row * 2] = lse_v; row_lse[row * 2 + 1] = lse_p;
+            if (token_nll) token_nll[row] = valid ? -logp : 0.f;
+            if (valid) {
+                const float best_v = sv.m - lse_v + lv, best_p = sp.m - lse_p + lp;
+                const int64_t pred = (best_p > best_v) ? (int64_t)V + sp.arg : (int64_t)sv.arg;
+                const float ell = (eps > 0.f) ? (1.0f - eps) * -logp + eps * smooth : -logp;
+                if (!weight) a_obj += ell;
+                else if (w != 0.f) a_obj += w * ell;             // (a zero weight masks the row out whatever its logits hold)
+                a_nll -= logp; a_cnt += 1.0f;
+                if (pred == lab) a_hit += 1.0f;
+            }
+        }
+    }
+    if (lane == 0) { red[wave][0] = a_obj; red[wave][1] = a_cnt; red[wave][2] = a_hit; red[wave][3] = a_nll; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const float v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+        const bool fixed = (threadIdx.x == 0 || threadIdx.x == 3) && fabsf(v) < 4294967296.f;          // (false for a NaN)
+        // objective: stats[6..7], fall-back stats[0]; plain sum: ext_stats[0..1], fall-back ext_stats[2] (the finish turns it into the mean)
+        float* word = threadIdx.x == 0 ? stats + 6 : ext_stats;
+        float* slot = threadIdx.x == 3 ? ext_stats + 2 : stats + threadIdx.x;
+        if (fixed) {
+            if (v != 0.f) atomicAdd(reinterpret_cast<unsigned long long*>(word), (unsigned long long)__float2ll_rn(v * NLL_FIXED_ONE));
+        } else if (v != 0.f) atomicAdd(slot, v);
+    }
+}
+// mixture_nll_finish_kernel, and the plain mean ext_stats[2] = (plain NLL sum) / count behind it in the same one-wave launch.
+__global__ void mixture_nll_ext_finish_kernel(float* stats, float* ext_stats) {
+    if (threadIdx.x == 0) {
+        const long long q = *reinterpret_cast<const long long*>(stats + 6);
+        const float s0 = stats[0] + (float)((double)q * (1.0 / (double)NLL_FIXED_ONE)), s1 = stats[1], s2 = stats[2];
+        stats[0] = s0;
+        stats[4] = s0 / s1; stats[5] = s2 / (s1 + 1e-10f); stats[3] = 1.0f;
+        const long long qn = *reinterpret_cast<const long long*>(ext_stats);
+        const float n0 = ext_stats[2] + (float)((double)qn * (1.0 / (double)NLL_FIXED_ONE));
+        ext_stats[2] = n0 / s1;
+    }
+}
+
+template <typename TO>
+__global__ __launch_bounds__(256) void mixture_nll_ext_bwd_kernel(TO* dvocab, TO* dptr, float* dsw, const float* stats,
+                                                                  const float* row_lse, const float* vocab, int ldv,
+                                                                  const float* ptr, const float* sw, const int64_t* label,
+                                                                  int B, int Tn, int V, int pad, float gscale, const float* upstream,
+                                                                  float eps, const float* weight, int per_token) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (int64_t)B * Tn) return;                          // (the whole wave leaves: nothing is loaded or stored for it)
+    const int i = (int)(row % Tn);
+    const int64_t lab = label[row];
+    const float w = weight ? weight[per_token ? row : row / Tn] : 1.f;
+    const float s_row = sw[row], lse_v = row_lse[row * 2], lse_p = row_lse[row * 2 + 1];
+    TO* dv = dvocab + row * ldv;
+    TO* dp = dptr + row * Tn;
+    if (lab == pad || (weight && w == 0.f)) {                    // PAD row, or a row masked out by a zero weight: exact zeros
+        for (int k = lane; k < ldv; k += 64) st1<TO>(dv + k, 0.f);
+        for (int j = lane; j < Tn; j += 64) st1<TO>(dp + j, 0.f);
+        if (lane == 0) dsw[row] = 0.f;
+        return;
+    }
+    float g = gscale * (upstream ? *upstream : stats[3]) / stats[1];
+    if (weight) g *= w;
+    const float prob = 1.0f / (1.0f + expf(-s_row));
+    const float* vr = vocab + row * ldv;
+    const float* pr = ptr + row * Tn;
+    if (eps > 0.f) {
+        // both parts of the row: the label's part carries (1 - eps) of the plain gradient, every allowed class eps / C_i of the smoothing's
+        const float Vf = (float)V, If = (float)i, ec = eps / (Vf + If), om = 1.0f - eps;
+        const bool in_v = lab < V;
+        const int js = in_v ? -1 : (int)(lab - V);
+        for (int k = lane; k < ldv; k += 64) {
+            const float E = expf(vr[min(k, V - 1)] - lse_v);
+            const float plain = in_v ? E - (k == lab ? 1.f : 0.f) : 0.f;
+            st1<TO>(dv + k, (k < V) ? g * (om * plain + ec * (Vf * E - 1.f)) : 0.f);
+        }
+        for (int j = lane; j < Tn; j += 64) {
+            const float E = expf(pr[j] - lse_p);
+            const float plain = in_v ? 0.f : E - (j == js ? 1.f : 0.f);
+            st1<TO>(dp + j, (j < i) ? g * (om * plain + ec * (If * E - 1.f)) : 0.f);
+        }
+        if (lane == 0) {
+            const float dlv = (1.0f - prob >= 1e-6f) ? -prob : 0.f, dlp = (prob >= 1e-6f) ? 1.0f - prob : 0.f;
+            dsw[row] = g * (-om * (in_v ? dlv : dlp) - ec * (Vf * dlv + If * dlp));
+        }
+    } else if (lab < V) {                                        // eps == 0: mixture_nll_bwd_kernel's two branches, only the label's part is read
+        for (int k = lane; k < ldv; k += 64)
+            st1<TO>(dv + k, (k < V) ? g * (expf(vr[min(k, V - 1)] - lse_v) - (k == lab ? 1.f : 0.f)) : 0.f);
+        for (int j = lane; j < Tn; j += 64) st1<TO>(dp + j, 0.f);
+        if (lane == 0) dsw[row] = (1.0f - prob >= 1e-6f) ? g * prob : 0.f;
+    } else {
+        const int js = (int)(lab - V);
+        for (int k = lane; k < ldv; k += 64) st1<TO>(dv + k, 0.f);
+        for (int j = lane; j < Tn; j += 64)
+            st1<TO>(dp + j, (j < i) ? g * (expf(pr[j] - lse_p) - (j == js ? 1.f : 0.f)) : 0.f);
+        if (lane == 0) dsw[row] = (prob >= 1e-6f) ? -g * (1.0f - prob) : 0.f;
+    }
+}
+
 // ================================================================================ Adam / cast
 __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, bf16* pb, int64_t n,
                                                    float step_size, float b1, float b2, float eps, float inv_sqrt_bc2,
@@ -1524,6 +1686,38 @@ extern "C" int pa_mixture_nll_bwd(void* dvocab, void* dptr, int32_t out_dtype, f
                                   const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
                                   float gscale, void* stream) {
     return pa_mixture_nll_bwd_up(dvocab, dptr, out_dtype, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, nullptr, stream);
+}
+
+// ---- extended objective (pa_loss_ext): one check of the block for both entries, before anything is enqueued
+extern "C" int64_t pa_loss_ext_bytes(void) { return (int64_t)sizeof(pa_loss_ext); }
+static bool loss_ext_ok(const pa_loss_ext* e) {
+    if (!e || !(e->smoothing >= 0.f && e->smoothing < 1.f)) return false;                  // (false for a NaN)
+    if (e->weight_per_token != 0 && e->weight_per_token != 1) return false;
+    return e->ext_stats && !(reinterpret_cast<uintptr_t>(e->ext_stats) & 7);               // ext_stats[0..1] is one 64-bit word
+}
+extern "C" int pa_mixture_nll_fwd_ext(float* stats8, float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
+                                      const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
+                                      const pa_loss_ext* e, void* stream) {
+    if (!stats8 || !row_lse || !vocab || !ptr || !sw || !label || B <= 0 || T <= 0 || V <= 0 || ldv < V) return PA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(stats8) & 7) || !loss_ext_ok(e)) return PA_EINVAL;
+    const int grid = (int)(((int64_t)B * T + NLL_ROWS - 1) / NLL_ROWS);
+    if (hipMemsetAsync(stats8, 0, 8 * sizeof(float), ST(stream)) != hipSuccess) return PA_EINVAL;
+    if (hipMemsetAsync(e->ext_stats, 0, 4 * sizeof(float), ST(stream)) != hipSuccess) return PA_EINVAL;
+    PA_LAUNCH(mixture_nll_ext_fwd_kernel, dim3(grid), dim3(256), 0, ST(stream), stats8, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad,
+              e->smoothing, e->weight, e->weight_per_token, e->token_nll, e->ext_stats);
+    PA_LAUNCH(mixture_nll_ext_finish_kernel, dim3(1), dim3(64), 0, ST(stream), stats8, e->ext_stats);
+    return 0;
+}
+extern "C" int pa_mixture_nll_bwd_ext(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, const float* stats,
+                                      const float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
+                                      const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
+                                      float gscale, const float* upstream, const pa_loss_ext* e, void* stream) {
+    if (!dvocab || !dptr || !dsw || !stats || !row_lse || !vocab || !ptr || !sw || !label) return PA_EINVAL;
+    if (B <= 0 || T <= 0 || V <= 0 || ldv < V || !loss_ext_ok(e)) return PA_EINVAL;
+    const int grid = (int)(((int64_t)B * T + 3) / 4);
+    if (out_dtype == PA_BF16) PA_LAUNCH(mixture_nll_ext_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, ST(stream), (bf16*)dvocab, (bf16*)dptr, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream, e->smoothing, e->weight, e->weight_per_token);
+    else PA_LAUNCH(mixture_nll_ext_bwd_kernel<float>, dim3(grid), dim3(256), 0, ST(stream), (float*)dvocab, (float*)dptr, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream, e->smoothing, e->weight, e->weight_per_token);
+    return 0;
 }
 
 extern "C" int pa_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float b1,

@@ -374,7 +374,10 @@ int pa_train_forward_impl(pa_model* m, void* st) {
     RC(pa_switch_fwd(m->sw, m->hid, c.dtype, PF(tl + T_SW_W), PF(tl + T_SW_B), (int64_t)BT, d, st));
     // (one memset inside; loss, accuracy and the upstream 1.0 are written by the kernel's last block: stats is 8 floats)
     m->upstream = nullptr;
-    RC(pa_mixture_nll_fwd_fin(m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw, m->batch.output_label, B, T, c.vocab, c.pad, st));
+    if (m->loss_on)
+        RC(pa_mixture_nll_fwd_ext(m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw, m->batch.output_label, B, T, c.vocab, c.pad, &m->loss, st));
+    else
+        RC(pa_mixture_nll_fwd_fin(m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw, m->batch.output_label, B, T, c.vocab, c.pad, st));
     return 0;
 }
 namespace {
@@ -387,8 +390,12 @@ int bwd_heads(pa_model* m, float gscale, void* st) {
     Ctx k{m, st};
     const int d = c.d_model, B = m->B, T = m->T, BT = B * T, tl = m->tail();
     auto G = [&](int i) { return (float*)m->gr[i]; };
-    RC(pa_mixture_nll_bwd_up(m->dvlog, m->dplog, c.dtype, m->dsw, m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw,
-                             m->batch.output_label, B, T, c.vocab, c.pad, gscale, m->upstream, st));
+    if (m->loss_on)
+        RC(pa_mixture_nll_bwd_ext(m->dvlog, m->dplog, c.dtype, m->dsw, m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw,
+                                  m->batch.output_label, B, T, c.vocab, c.pad, gscale, m->upstream, &m->loss, st));
+    else
+        RC(pa_mixture_nll_bwd_up(m->dvlog, m->dplog, c.dtype, m->dsw, m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw,
+                                 m->batch.output_label, B, T, c.vocab, c.pad, gscale, m->upstream, st));
     // vocab head
     if (m->plT[tl + T_VOCAB_W])       // padded W^T shadow [d][ldv] (pad columns zero): contraction over the padded width, both k-contiguous
         RC(k.linear_dx(m->dvlog, m->ldv, m->pl[tl + T_VOCAB_W], d, m->gA, d, BT, m->ldv, d, nullptr, 0, nullptr, 0, 1.f,
@@ -817,6 +824,15 @@ extern "C" int pa_model_train_fwd(pa_model* m, const pa_batch* batch, void* ws, 
 extern "C" int pa_model_set_upstream(pa_model* m, const float* upstream) {
     if (!m) return PA_EINVAL;
     m->upstream = upstream;
+    return 0;
+}
+extern "C" int pa_model_set_loss(pa_model* m, const pa_loss_ext* e) {
+    if (!m) return PA_EINVAL;
+    if (!e) { m->loss_on = false; return 0; }
+    if (!(e->smoothing >= 0.f && e->smoothing < 1.f) || (e->weight_per_token != 0 && e->weight_per_token != 1)) return PA_EINVAL;
+    if (!e->ext_stats || (reinterpret_cast<uintptr_t>(e->ext_stats) & 7)) return PA_EINVAL;
+    m->loss = *e;
+    m->loss_on = true;
     return 0;
 }
 extern "C" int32_t pa_model_stats_floats(void) { return PA_MODEL_STATS_FLOATS; }

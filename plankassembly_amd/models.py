@@ -136,8 +136,13 @@ class PlankModel(nn.Module):
                  normalize_before=True, num_encoder_layers=6, num_decoder_layers=6, num_view=3, num_type=2,
                  num_input_dof=4, num_output_dof=6, max_input_length=400, max_output_length=128, vocab_size=514,
                  token=None, compute_dtype=None, beam_size=1, length_penalty=0.0, num_samples=0, temperature=1.0, top_k=0,
-                 top_p=1.0, sample_seed=0, constraint=None, sample_select=None):
+                 top_p=1.0, sample_seed=0, constraint=None, sample_select=None, label_smoothing=0.0):
         super().__init__()
+        # train_step's objective: eps of the label smoothing over a row's allowed classes; 0 = the reference's loss
+        if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)) or not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"LABEL_SMOOTHING must be a number in [0, 1), got {label_smoothing!r}")
+        self.label_smoothing = float(label_smoothing)
+        self._loss_set = False                                 # whether the runtime handle holds a loss block (pa_model_set_loss)
         # the reference hands the string to torch's Transformer layers (models.py:60-61,66-67), which take "relu" or "gelu"
         if activation not in ("relu", "gelu"):
             raise ValueError(f"ACTIVATION must be 'relu' or 'gelu' (torch's _get_activation_fn), got {activation!r}")
@@ -337,6 +342,7 @@ class PlankModel(nn.Module):
         self._ws = None
         self._decoder = None
         self._mode_decoders = {}
+        self._loss_set = False
         self._drop_x3_cache()
 
     def _drop_x3_cache(self):
@@ -737,6 +743,8 @@ class PlankModel(nn.Module):
         self._require_gpu()
         dev = self._flat.device
         out = {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
+        if out.get("loss_weight") is not None:                 # checked and cast here, so train_step finds it ready (f32, contiguous)
+            out["loss_weight"] = self._loss_weight(out)
         if self.unpad:
             msk = out["input_mask"].contiguous()
             msk = msk.view(torch.uint8) if msk.dtype == torch.bool else msk.to(torch.uint8)
@@ -798,11 +806,37 @@ class PlankModel(nn.Module):
         return self._ws
 
     # ---------------------------------------------------------------------------------- train step
-    def train_step(self, batch):
-        """reference models.py:190-233."""
+    def _loss_weight(self, batch):
+        """batch["loss_weight"] ([B] per drawing or [B, T] per token) as f32 on the model's device, or None; ValueError for another shape."""
+        w = batch.get("loss_weight")
+        if w is None:
+            return None
+        w = torch.as_tensor(w)
+        from .ops import loss_weight_layout
+        loss_weight_layout(w, *batch["output_label"].shape)
+        return w.to(device=self._flat.device, dtype=torch.float32).contiguous()
+
+    def train_step(self, batch, token_nll=False):
+        """reference models.py:190-233.  With ``label_smoothing`` > 0, a ``batch["loss_weight"]`` or ``token_nll=True`` the objective is
+        the extended one (include/plank_hip.h pa_loss_ext): ``loss`` = sum w ell / #non-PAD, and the dict also holds ``nll`` (the plain
+        mean -log p(label)) and, on request, ``token_nll`` [B, T].  Without any of the three: the reference's loss, through the calls of
+        the reference-parity step."""
+        weight = self._loss_weight(batch)                      # (a bad shape raises before anything touches the device)
         self._ensure_handle()
         self._refresh_shadow()
         b, keep = self._make_batch(batch, True)
+        ext = None
+        if self.label_smoothing > 0.0 or weight is not None or token_nll:
+            from .ops import loss_ext_block
+            ext = torch.empty(4, dtype=torch.float32, device=self._flat.device)
+            tok = torch.empty(b.B, b.T, dtype=torch.float32, device=self._flat.device) if token_nll else None
+            keep += [t for t in (weight, tok, ext) if t is not None]          # alive until the backward has been enqueued
+            blk = loss_ext_block(self.label_smoothing, weight, b.B, b.T, tok, ext)
+            L.check(L.lib().pa_model_set_loss(self._handle, C.byref(blk)), "pa_model_set_loss")
+            self._loss_set = True
+        elif self._loss_set:
+            L.check(L.lib().pa_model_set_loss(self._handle, None), "pa_model_set_loss")
+            self._loss_set = False
         ws = self._workspace(b.B, b.S, b.T)
         base = (ws.data_ptr() + 255) // 256 * 256
         stats = torch.empty(L.lib().pa_model_stats_floats(), dtype=torch.float32, device=self._flat.device)   # include/plank_hip.h: f32[8]
@@ -822,7 +856,12 @@ class PlankModel(nn.Module):
             loss = _TrainStepFn.apply(self._hook_leaf, self, stats)
         else:
             loss = stats[4]
-        return {"loss": loss, "accuracy": stats[5]}
+        if ext is None:
+            return {"loss": loss, "accuracy": stats[5]}
+        out = {"loss": loss, "accuracy": stats[5], "nll": ext[2]}
+        if tok is not None:
+            out["token_nll"] = tok
+        return out
 
     def _run_backward(self, gloss):
         self._ensure_grads()
@@ -1081,7 +1120,7 @@ def build_model(cfg):
     (bool, default off): eval_step decodes - in whichever mode - under the plank grammar of DESIGN.md section 15, with
     ``MIN_PLANKS`` (default 1) and ``MAX_PLANKS`` (default: the last plank boundary of the decode).  ``SAMPLE_SELECT``
     (``consensus``; default none): which of the NUM_SAMPLES samples eval_step returns (PlankModel.sample); it needs NUM_SAMPLES
-    >= 1.  A bad value, SAMPLE_SELECT without samples, or
+    >= 1.  ``LABEL_SMOOTHING`` (a number in [0, 1), default 0): eps of train_step's label smoothing.  A bad value, SAMPLE_SELECT without samples, or
     NUM_SAMPLES >= 1 together with BEAM_SIZE > 1, raises ValueError."""
     model_cfg = cfg.MODEL
 
@@ -1102,4 +1141,5 @@ def build_model(cfg):
         cfg.DATA.NUM_OUTPUT_DOF, cfg.DATA.MAX_INPUT_LENGTH, cfg.DATA.MAX_OUTPUT_LENGTH, cfg.DATA.VOCAB_SIZE,
         cfg.TOKEN, compute_dtype=dtype, beam_size=opt("BEAM_SIZE", 1), length_penalty=float(opt("LENGTH_PENALTY", 0.0)),
         num_samples=opt("NUM_SAMPLES", 0), temperature=opt("TEMPERATURE", 1.0), top_k=opt("TOP_K", 0), top_p=opt("TOP_P", 1.0),
-        sample_seed=opt("SAMPLE_SEED", 0), constraint=grammar, sample_select=opt("SAMPLE_SELECT"))
+        sample_seed=opt("SAMPLE_SEED", 0), constraint=grammar, sample_select=opt("SAMPLE_SELECT"),
+        label_smoothing=opt("LABEL_SMOOTHING", 0.0))

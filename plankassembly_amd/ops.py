@@ -380,6 +380,54 @@ def mixture_nll_bwd(stats, row_lse, vocab, ptr, sw, label, V, pad, gscale=1.0, o
     return dvocab, dptr, dsw
 
 
+def loss_weight_layout(weight, B, T):
+    """0 for a per-drawing weight [B], 1 for a per-token weight [B, T] (pa_loss_ext.weight_per_token); ValueError for anything else."""
+    if not torch.is_tensor(weight) or not weight.is_floating_point() or tuple(weight.shape) not in ((B,), (B, T)):
+        shape = tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__
+        raise ValueError(f"loss_weight must be a float tensor of shape [{B}] or [{B}, {T}], got {shape}")
+    return weight.dim() - 1
+
+
+def loss_ext_block(smoothing, weight, B, T, token_nll, ext_stats):
+    """The pa_loss_ext of one call; ``weight`` f32 contiguous on the device (or None), ``token_nll`` f32 [B, T] (or None)."""
+    per_token = 0 if weight is None else loss_weight_layout(weight, B, T)
+    return L.LossExt(float(smoothing), per_token, L.ptr(weight).value if weight is not None else None,
+                     L.ptr(token_nll).value if token_nll is not None else None, L.ptr(ext_stats).value)
+
+
+def mixture_nll_ext_fwd(vocab, ptr, sw, label, V, pad, smoothing=0.0, weight=None, token_nll=False, out=None):
+    """The extended objective (include/plank_hip.h pa_loss_ext).  Operands as mixture_nll_fwd; ``weight`` f32 [B] or [B, T] or None.
+    Returns (stats8, row_lse, ext_stats, token_nll or None): stats8[4] the loss, ext_stats[2] the plain mean NLL.  ``out``: buffers to
+    write into instead of fresh ones, by the same names (``token_nll`` included)."""
+    B, T = label.shape
+    out = out or {}
+    dev = vocab.device
+    stats = out["stats8"] if "stats8" in out else torch.empty(8, dtype=torch.float32, device=dev)
+    row_lse = out["row_lse"] if "row_lse" in out else _f32(B * T, 2, device=dev)
+    ext = out["ext_stats"] if "ext_stats" in out else torch.empty(4, dtype=torch.float32, device=dev)
+    tok = out["token_nll"] if "token_nll" in out else (_f32(B, T, device=dev) if token_nll else None)
+    e = loss_ext_block(smoothing, weight, B, T, tok, ext)
+    L.check(L.lib().pa_mixture_nll_fwd_ext(L.ptr(stats), L.ptr(row_lse), L.ptr(vocab), vocab.stride(-2), L.ptr(ptr), L.ptr(sw),
+                                           L.ptr(label), B, T, V, pad, C.byref(e), L.stream()), "pa_mixture_nll_fwd_ext")
+    return stats, row_lse, ext, tok
+
+
+def mixture_nll_ext_bwd(stats, row_lse, ext_stats, vocab, ptr, sw, label, V, pad, smoothing=0.0, weight=None, gscale=1.0,
+                        out_dtype=torch.float32, upstream=None, out=None):
+    """Gradients of the extended objective from the forward's stats8 and row_lse: (dvocab, dptr, dsw).  ``upstream``: device f32
+    scalar d(loss), None = stats8[3]."""
+    B, T = label.shape
+    out = out or {}
+    dvocab = out["dvocab"] if "dvocab" in out else torch.empty(vocab.shape, dtype=out_dtype, device=vocab.device)
+    dptr = out["dptr"] if "dptr" in out else torch.empty(ptr.shape, dtype=out_dtype, device=vocab.device)
+    dsw = out["dsw"] if "dsw" in out else torch.empty_like(sw)
+    e = loss_ext_block(smoothing, weight, B, T, None, ext_stats)
+    L.check(L.lib().pa_mixture_nll_bwd_ext(L.ptr(dvocab), L.ptr(dptr), L.dt(dvocab), L.ptr(dsw), L.ptr(stats), L.ptr(row_lse),
+                                           L.ptr(vocab), vocab.stride(-2), L.ptr(ptr), L.ptr(sw), L.ptr(label), B, T, V, pad,
+                                           C.c_float(gscale), L.ptr(upstream), C.byref(e), L.stream()), "pa_mixture_nll_bwd_ext")
+    return dvocab, dptr, dsw
+
+
 def adam_step(p, g, m, v, step, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, p_bf16=None):
     L.check(L.lib().pa_adam_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(p_bf16), C.c_int64(p.numel()),
                                  C.c_float(lr), C.c_float(b1), C.c_float(b2), C.c_float(eps), int(step),

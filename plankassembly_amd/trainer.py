@@ -154,6 +154,8 @@ class Trainer(torch.nn.Module):
         outputs = self.model(batch)
         loss = torch.mean(outputs["loss"])
         self._train_stats = (loss.detach(), torch.mean(outputs["accuracy"]).detach())
+        # the plain mean NLL next to a smoothed / weighted loss (the model returns it only then; batch["loss_weight"] reaches it as is)
+        self._train_nll = outputs["nll"].detach() if "nll" in outputs else None
         return loss
 
     def _valid_pred(self, pred):
@@ -544,6 +546,8 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
                 break
         l, a = module._train_stats
         module.log("train/loss", l); module.log("train/accuracy", a)
+        if getattr(module, "_train_nll", None) is not None:
+            module.log("train/nll", module._train_nll)
         module.log("train/lr", opt.param_groups[0]["lr"])      # the rate of the epoch's last step
         torch.cuda.synchronize()
         if getattr(opt, "guarded", False):                 # the guard's one read-back, where the loop synchronises anyway
