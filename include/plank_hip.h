@@ -965,6 +965,69 @@ int pa_plank_match(const int64_t* seq_a, int64_t stride_a, int32_t len_a, const 
                    const int32_t* pair_a, const int32_t* pair_b, int32_t n_pairs, int32_t end_token, int32_t dof,
                    int32_t filter_a, int32_t filter_b, double threshold, int32_t* out, void* stream);
 
+/* ---- sequence-level training batches (csrc/seqtrain.hip; PlankModel.sequence_batch / seq_train_step) ----
+ * One launch, one block per output row, grid (G, B): the N samples of each of B drawings, as the sample decoder left them in HBM
+ * (pa_decode_buffers / pa_decode_sample_buffers, rows b*N + n, read in place), and the match counts of those rows against the
+ * drawing's ground truth (pa_plank_match) become the teacher-forced batch of pa_model_train_fwd with one loss weight per row
+ * (pa_loss_ext.weight, weight_per_token 0).  Restates plankassembly_amd/metric.py `prf_from_counts` (HungarianMatcher's
+ * precision / recall / F1; reference third_party/matcher.py:57-61) and the output-sequence contract of plankassembly_amd/datasets.py
+ * `prepare_output_sequence` (reference line_data.py:85-109: label = vocab_size + attach at a pointer, PAD behind END, mask = PAD).
+ *   tokens / attach int64 [B*N] rows of Tmax, row r at + r * sample_stride (elements, >= 0); first_end int32 [B*N] (-1: the row never
+ *     ended); scores f32 [B*N] (log-likelihood of each sample; read under objective 1 only);
+ *   counts int32 [B*N][4] = tp, n_a (sample planks), n_b (ground-truth planks), ties of row b*N + n against drawing b;
+ *   base_counts int32 [B][4] or NULL: the same for a greedy decode of drawing b (baseline 2);
+ *   gt_value / gt_label int64 [B] rows of T, row b at + b * gt_stride; T >= Tmax;
+ *   objective 0 = reinforce, 1 = risk; baseline 0 = none, 1 = mean of the others, 2 = greedy (the baseline enters objective 0 only,
+ *     its argument rules hold under both); alpha (objective 1), nll_weight; vocab_size, pad_token; end_token is not read - a row is
+ *     cut by first_end, never searched.
+ * G = N + (nll_weight != 0) rows per drawing, row b*G + g:
+ *   out_value / out_label int64 [B*G][T], out_mask uint8 [B*G][T], out_weight f32 [B*G], reward f32 [B][N].
+ *   g < N, with L = first_end + 1 (Tmax for -1; clamped to Tmax): t < L: value = tokens[t], label = attach[t] >= 0 ? vocab_size +
+ *     attach[t] : tokens[t], mask 0; t >= L: value = label = pad_token, mask 1.  A row that never ended trains on all Tmax tokens and
+ *     has no END label.
+ *   g == N (only with nll_weight != 0): value / label = the drawing's gt_value / gt_label, mask = (value == pad_token), weight =
+ *     nll_weight.
+ * reward[b][n] = F1 of counts[b*N + n], bit for bit prf_from_counts: prec = (f32)((f64)tp / n_a), rec = (f32)((f64)tp / n_b), 0
+ *   where the denominator is 0; f1 = ((prec * rec) * 2) / ((prec + rec) + 1e-10f) in f32, every operation rounded on its own (no
+ *   contraction).  tp is used as pa_plank_match reports it: pairs at IoU == threshold exactly (ties) are no edges and count for
+ *   nothing, and no row is re-scored on the host - unlike DevicePlankScorer, a training reward does not chase scipy's tie-breaking.
+ * out_weight[b*G + n], formed in double from the f32 rewards r_m in this order and rounded to f32 once:
+ *   objective 0: w_n = (r_n - b_n) / N with b_n = 0 (baseline 0); b_n = (sum over m != n, m ascending, of r_m) / (N - 1)
+ *     (baseline 1; a drawing whose rewards are all equal gets exact +0.0 weights: the sum of N - 1 <= 63 equal f32 values is exact
+ *     in double); b_n = the F1 of base_counts[b] (baseline 2);
+ *   objective 1: s_m = (f64)alpha * (f64)scores[m]; mx = max s_m; e_m = exp(s_m - mx); z = sum e_m (m ascending); q_m = e_m / z;
+ *     A_n = sum of (q_m * (r_n - r_m)) (m ascending, each difference and product rounded) = r_n - sum_m q_m r_m without the
+ *     cancellation of two nearly equal numbers - equal rewards give an exact +0.0 here too; w_n = (alpha * q_n) * A_n - minus the
+ *     derivative of the expected risk sum_m q_m (1 - r_m) with respect to log p_n, as a weight on -log p_n.  Scores must be finite.
+ * PA_EINVAL, nothing launched: a null pointer (base_counts may be NULL unless baseline == 2), N outside [1, PA_SEQ_MAX_SAMPLES],
+ * baseline 1 with N < 2, baseline 2 without base_counts, Tmax > T, a negative B / Tmax / T / stride, objective or baseline out of range,
+ * nll_weight not finite, alpha not finite or <= 0 under objective 1.  B above 65535: PA_ESHAPE.  B == 0 launches nothing and returns 0.
+ * pa_seq_batch_args_bytes: sizeof(pa_seq_batch_args), for bindings to check their layout against. */
+#define PA_SEQ_MAX_SAMPLES 64
+typedef struct {
+    const int64_t* tokens;
+    const int64_t* attach;
+    const int32_t* first_end;
+    const float* scores;
+    const int32_t* counts;
+    const int32_t* base_counts;
+    const int64_t* gt_value;
+    const int64_t* gt_label;
+    int64_t* out_value;
+    int64_t* out_label;
+    uint8_t* out_mask;
+    float* out_weight;
+    float* reward;
+    int64_t sample_stride;
+    int64_t gt_stride;
+    int32_t B, N, Tmax, T;
+    int32_t objective, baseline;
+    float alpha, nll_weight;
+    int32_t vocab_size, end_token, pad_token, pad_;
+} pa_seq_batch_args;
+int64_t pa_seq_batch_args_bytes(void);
+int pa_sequence_batch(const pa_seq_batch_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

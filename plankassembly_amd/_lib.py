@@ -123,6 +123,17 @@ class LossExt(C.Structure):
                 ("ext_stats", C.c_void_p)]
 
 
+class SeqBatchArgs(C.Structure):
+    """include/plank_hip.h pa_seq_batch_args (pa_sequence_batch); sizeof == pa_seq_batch_args_bytes()."""
+    _fields_ = [("tokens", C.c_void_p), ("attach", C.c_void_p), ("first_end", C.c_void_p), ("scores", C.c_void_p),
+                ("counts", C.c_void_p), ("base_counts", C.c_void_p), ("gt_value", C.c_void_p), ("gt_label", C.c_void_p),
+                ("out_value", C.c_void_p), ("out_label", C.c_void_p), ("out_mask", C.c_void_p), ("out_weight", C.c_void_p),
+                ("reward", C.c_void_p), ("sample_stride", C.c_int64), ("gt_stride", C.c_int64),
+                ("B", C.c_int32), ("N", C.c_int32), ("Tmax", C.c_int32), ("T", C.c_int32),
+                ("objective", C.c_int32), ("baseline", C.c_int32), ("alpha", C.c_float), ("nll_weight", C.c_float),
+                ("vocab_size", C.c_int32), ("end_token", C.c_int32), ("pad_token", C.c_int32), ("pad_", C.c_int32)]
+
+
 _lib = None
 
 
@@ -270,6 +281,8 @@ def lib():
             "pa_tokenise_drawings": (I, [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, D, D, D, U, U,
                                          P, P, P, P, P, P, P, P, P, P, P]),
             "pa_plank_match": (I, [P, I64, I, P, I64, I, P, P, I, I, I, I, I, D, P, P]),
+            "pa_seq_batch_args_bytes": (I64, []),
+            "pa_sequence_batch": (I, [P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(_lib, name)

@@ -607,6 +607,26 @@ class SampleDecoder(GreedyDecoder):
         self._loop(Tmax, early_stop, lambda: bool((first_end >= 0).all().cpu()))
         return _ranked("sample", tokens, attach, first_end, scores, first_end >= 0, B, N, Tmax, self.length_penalty, pbuf)
 
+    def run_device(self, batch, max_len=None, early_stop=True, seed=None, constraint=None):
+        """``run`` up to and including the stepping loop, for callers that go on working on the device (PlankModel.sequence_batch;
+        DESIGN.md section 24): the same begin, seed, constraint and steps, then the decoder's own buffers as they are - unranked,
+        not cut to the longest row, nothing copied to the host beyond the loop's early-stop look.  Returns ``tokens`` / ``attach``
+        int64 [rows, Tmax], ``first_end`` int32 [rows] (-1: the row never ended) and ``scores`` f32 [rows], rows = B * N with row
+        b * N + n sample n of drawing b.  They are views into the decoder's workspaces: valid until this decoder's next ``begin``
+        (its next ``run`` / ``run_device``), which overwrites them in place or moves them."""
+        grammar = self._check_constraint(constraint)
+        rows, Tmax = self.begin(batch, max_len)
+        self._prefix_begin(None, self.num_samples, rows, Tmax)
+        self._constraint_begin(grammar)
+        if seed is not None:
+            p = self.params
+            q = sample_params(self.num_samples, p.temperature, p.top_k, p.top_p, seed)
+            L.check(L.lib().pa_decode_sample_set(self._lanes[0].h(), C.byref(q), L.stream()), "pa_decode_sample_set")
+        tokens, attach, first_end = self._lanes[0].buffers(rows, Tmax)
+        scores = self._scores(rows)
+        self._loop(Tmax, early_stop, lambda: bool((first_end >= 0).all().cpu()))
+        return tokens, attach, first_end, scores
+
 
 @functools.lru_cache(maxsize=8)
 def _consensus_pairs(B, N, device):

@@ -157,6 +157,7 @@ class PlankModel(nn.Module):
             raise ValueError(f"BEAM_SIZE must be an integer in [1, 16], got {beam_size!r}")
         self.beam_size, self.length_penalty = int(beam_size), float(length_penalty)
         self._mode_decoders = {}                               # beam / sampling decoders by their settings (_decoder_for)
+        self._seq_pair_cache = {}                              # plank_match pair lists of sequence_batch by (B, N, device)
         # or sampling with this many samples per drawing (decode.SampleDecoder, 1 <= N <= 64; 0 = off)
         from .decode import sample_params
         off = num_samples == 0 and isinstance(num_samples, int) and not isinstance(num_samples, bool)
@@ -1080,6 +1081,85 @@ class PlankModel(nn.Module):
         out = self._decode_dict(batch, r, prefix, parse)
         if select == "consensus":
             out.update(pick)
+        return out
+
+    # ---------------------------------------------------------------------------------- sequence-level training
+    _SEQ_OWN_KEYS = ("output_value", "output_label", "output_mask", "loss_weight")
+
+    def _seq_pairs(self, B, N, device):
+        """The (sample row b*N + n, ground-truth row b) list of ops.plank_match, int32 [B*N, 2] on the device; cached per (B, N)."""
+        key = (B, N, str(device))
+        pairs = self._seq_pair_cache.get(key)
+        if pairs is None:
+            rows = torch.arange(B * N, dtype=torch.int32)
+            pairs = self._seq_pair_cache[key] = torch.stack([rows, rows // N], 1).to(device)
+        return pairs
+
+    def sequence_batch(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, objective="reinforce", baseline="mean",
+                       alpha=1.0, nll_weight=0.0, constraint=None, threshold=0.5):
+        """The training batch of one sequence-level step on plank F1, built on the device under no_grad:
+        ``num_samples`` seeded samples per drawing (decode.SampleDecoder.run_device), one ops.plank_match of the sample rows against
+        ``batch["output_value"]`` (zero-extent sample planks dropped, edges at IoU > ``threshold``, ties no edges), then one
+        ops.sequence_batch launch: every sample cut at its END as a teacher-forced row whose loss weight is the policy-gradient
+        weight of its F1 - ``objective`` ``reinforce`` with ``baseline`` ``none`` / ``mean`` (of the drawing's other samples) /
+        ``greedy`` (the F1 of ``eval_step``'s decode, run before the sampling), or ``risk`` (expected 1 - F1 under the softmax of
+        ``alpha`` * the samples' log-likelihoods) - and, with ``nll_weight`` != 0, the ground-truth row of each drawing with that
+        weight.  ``constraint``: as in eval_step, for the sampling and the greedy baseline.
+
+        Returns a batch for ``train_step``: the input keys with every drawing repeated G = num_samples + (nll_weight != 0) times,
+        ``output_value`` / ``output_label`` / ``output_mask`` [B*G, T] and ``loss_weight`` [B*G], plus ``reward`` f32 [B, N],
+        ``sample_scores`` f32 [B, N] (the samples' log-likelihoods, a copy) and ``counts`` int32 [B*N, 4]; nothing is read back
+        beyond the decoders' early-stop looks.  The loss divides by the batch's non-PAD tokens (pa_loss_ext), not by the rows.
+        ValueError when ``num_output_dof`` != 6 (planks are compared as six coordinates)."""
+        from . import ops
+        from .decode import SampleDecoder, _repeat_batch
+        if self.num_output_dof != 6:
+            raise ValueError("sequence_batch compares planks of six output DOF")
+        if objective not in ops.SEQ_OBJECTIVES:
+            raise ValueError(f"objective must be one of {ops.SEQ_OBJECTIVES}, got {objective!r}")
+        if baseline not in ops.SEQ_BASELINES:
+            raise ValueError(f"baseline must be one of {ops.SEQ_BASELINES}, got {baseline!r}")
+        N, end = int(num_samples), self.token.END
+        with torch.no_grad():
+            self._require_gpu()
+            dev = self._flat.device
+            truth = batch["output_value"].to(device=dev, dtype=torch.int64)
+            label = batch["output_label"].to(device=dev, dtype=torch.int64)
+            B = truth.shape[0]
+            base_counts = None
+            if baseline == "greedy":
+                # before the sampling: eval_step may run on the very decoder that samples (a model built with NUM_SAMPLES), and a
+                # decoder's buffers hold only until its next begin
+                greedy = self.eval_step(batch, constraint=constraint, parse=False)["samples"]
+                base_counts = ops.plank_match(greedy, truth, end_token=end, filter_a=True, filter_b=False, threshold=threshold)
+            key = ("sample", N, float(temperature), int(top_k), float(top_p), 0.0)
+            dec = self._decoder_for(key, lambda: SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, 0.0))
+            tokens, attach, first_end, scores = dec.run_device(batch, seed=seed, constraint=self._grammar(constraint))
+            counts = ops.plank_match(tokens, truth, self._seq_pairs(B, N, dev), end_token=end, filter_a=True, filter_b=False,
+                                     threshold=threshold, check_pairs=False)
+            value, lab, mask, weight, reward = ops.sequence_batch(
+                tokens, attach, first_end, scores, counts, truth, label, num_samples=N, vocab_size=self.vocab_size, end_token=end,
+                pad_token=self.token.PAD, objective=objective, baseline=baseline, alpha=alpha, nll_weight=nll_weight,
+                base_counts=base_counts)
+            G = value.shape[0] // B if B else N + (1 if float(nll_weight) != 0.0 else 0)
+            out = _repeat_batch({k: v for k, v in batch.items() if k not in self._SEQ_OWN_KEYS}, G)
+            out.update(output_value=value, output_label=lab, output_mask=mask, loss_weight=weight, reward=reward,
+                       sample_scores=scores.view(B, N).clone(), counts=counts)
+            if self.unpad:
+                pack = batch.get("_pack")
+                if pack is not None:                    # a prepared batch knows its valid rows on the host: G times as many now
+                    out["_n_valid"] = pack[2] * G
+                out = self.prepare_batch(out)
+        return out
+
+    def seq_train_step(self, batch, num_samples, **kw):
+        """``sequence_batch(batch, num_samples, **kw)`` followed by ``train_step`` on it: the train_step dict (``loss``: the weighted
+        objective to call backward on, ``accuracy``, ``nll``) plus ``reward``, the mean F1 of the samples as a device scalar, and
+        ``batch``, the sequence batch the step trained on."""
+        sb = self.sequence_batch(batch, num_samples, **kw)
+        out = self.train_step(sb)
+        out["reward"] = sb["reward"].mean()
+        out["batch"] = sb
         return out
 
     def forward(self, batch):

@@ -602,3 +602,86 @@ def plank_match(seq_a, seq_b, pairs=None, *, end_token, filter_a, filter_b, thre
                                        int(seq_b.shape[1]), L.ptr(pa), L.ptr(pb), int(n), int(end_token), 6, int(bool(filter_a)),
                                        int(bool(filter_b)), float(threshold), L.ptr(out), L.stream()), "pa_plank_match")
     return out
+
+
+SEQ_OBJECTIVES = ("reinforce", "risk")
+SEQ_BASELINES = ("none", "mean", "greedy")
+
+
+def sequence_batch(tokens, attach, first_end, scores, counts, output_value, output_label, *, num_samples, vocab_size, end_token,
+                   pad_token, objective="reinforce", baseline="mean", alpha=1.0, nll_weight=0.0, base_counts=None):
+    """The sample decoder's buffers and their match counts -> a teacher-forced, weighted training batch, one launch, nothing read
+    back (pa_sequence_batch, csrc/seqtrain.hip; include/plank_hip.h has the row and weight rules).
+
+    tokens / attach int64 [B*N, Tmax] (last dimension contiguous, the same row stride), first_end int32 [B*N], scores f32 [B*N],
+    counts int32 [B*N, 4] (``plank_match`` of the sample rows against their drawing's ground truth), base_counts int32 [B, 4]
+    (baseline ``greedy``), output_value / output_label int64 [B, T] with T >= Tmax; all on one device.  ``objective``
+    ``reinforce`` | ``risk``; ``baseline`` ``none`` | ``mean`` | ``greedy``.  TypeError for a wrong dtype or device, ValueError for
+    a wrong shape or value, before the call.  Returns (output_value, output_label int64 [B*G, T], output_mask bool [B*G, T],
+    loss_weight f32 [B*G], reward f32 [B, N]) with G = N + (nll_weight != 0)."""
+    N = num_samples
+    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= 64:
+        raise ValueError(f"num_samples must be an integer in [1, 64], got {N!r}")
+    if objective not in SEQ_OBJECTIVES:
+        raise ValueError(f"objective must be one of {SEQ_OBJECTIVES}, got {objective!r}")
+    if baseline not in SEQ_BASELINES:
+        raise ValueError(f"baseline must be one of {SEQ_BASELINES}, got {baseline!r}")
+    for name, v in (("alpha", alpha), ("nll_weight", nll_weight)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    if objective == "risk" and not alpha > 0:
+        raise ValueError(f"alpha must be > 0 under objective 'risk', got {alpha!r}")
+    if baseline == "mean" and N < 2:
+        raise ValueError("baseline 'mean' needs num_samples >= 2")
+    if (base_counts is None) != (baseline != "greedy"):
+        raise ValueError("base_counts goes with baseline 'greedy', and only with it")
+    spec = [("tokens", tokens, torch.int64, 2), ("attach", attach, torch.int64, 2), ("first_end", first_end, torch.int32, 1),
+            ("scores", scores, torch.float32, 1), ("counts", counts, torch.int32, 2), ("output_value", output_value, torch.int64, 2),
+            ("output_label", output_label, torch.int64, 2)]
+    if base_counts is not None:
+        spec.append(("base_counts", base_counts, torch.int32, 2))
+    for name, t, dtype, dim in spec:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype):
+            raise TypeError(f"{name} must be a {dtype} device tensor")
+        if t.device != tokens.device:
+            raise TypeError(f"{name} must be on the device of tokens ({tokens.device}), got {t.device}")
+        if t.dim() != dim:
+            raise ValueError(f"{name} must have {dim} dimension(s), got shape {tuple(t.shape)}")
+    rows, Tmax = tokens.shape
+    B, T = output_value.shape
+    if rows != B * N:
+        raise ValueError(f"tokens has {rows} rows for {B} drawings of {N} samples")
+    if attach.shape != tokens.shape or output_label.shape != output_value.shape:
+        raise ValueError("attach / output_label must have the shape of tokens / output_value")
+    if first_end.shape != (rows,) or scores.shape != (rows,) or counts.shape != (rows, 4):
+        raise ValueError(f"first_end / scores / counts must be [{rows}] / [{rows}] / [{rows}, 4]")
+    if base_counts is not None and base_counts.shape != (B, 4):
+        raise ValueError(f"base_counts must be [{B}, 4], got {tuple(base_counts.shape)}")
+    if Tmax > T:
+        raise ValueError(f"the samples are longer (Tmax {Tmax}) than the ground-truth rows (T {T})")
+
+    def strided(a, b):                                 # two row-major views with one row stride: read in place when they are that
+        ok = all(t.shape[1] <= 1 or t.stride(1) == 1 for t in (a, b)) and (a.shape[0] <= 1 or a.stride(0) == b.stride(0))
+        if not ok:
+            a, b = a.contiguous(), b.contiguous()
+        return a, b, (a.stride(0) if a.shape[0] > 1 else a.shape[1])
+    tokens, attach, s_stride = strided(tokens, attach)
+    output_value, output_label, g_stride = strided(output_value, output_label)
+    first_end, scores, counts = first_end.contiguous(), scores.contiguous(), counts.contiguous()
+    base_counts = None if base_counts is None else base_counts.contiguous()
+    dev = tokens.device
+    G = N + (1 if float(nll_weight) != 0.0 else 0)
+    out_value = torch.empty(B * G, T, dtype=torch.int64, device=dev)
+    out_label = torch.empty(B * G, T, dtype=torch.int64, device=dev)
+    out_mask = torch.empty(B * G, T, dtype=torch.uint8, device=dev)
+    out_weight = torch.empty(B * G, dtype=torch.float32, device=dev)
+    reward = torch.empty(B, N, dtype=torch.float32, device=dev)
+    a = L.SeqBatchArgs(tokens.data_ptr(), attach.data_ptr(), first_end.data_ptr(), scores.data_ptr(), counts.data_ptr(),
+                       None if base_counts is None else base_counts.data_ptr(), output_value.data_ptr(), output_label.data_ptr(),
+                       out_value.data_ptr(), out_label.data_ptr(), out_mask.data_ptr(), out_weight.data_ptr(), reward.data_ptr(),
+                       s_stride, g_stride, B, N, Tmax, T, SEQ_OBJECTIVES.index(objective), SEQ_BASELINES.index(baseline),
+                       float(alpha), float(nll_weight), int(vocab_size), int(end_token), int(pad_token), 0)
+    if B > 0:
+        with torch.cuda.device(dev):
+            L.check(L.lib().pa_sequence_batch(C.byref(a), L.stream()), "pa_sequence_batch")
+    return out_value, out_label, out_mask.view(torch.bool), out_weight, reward

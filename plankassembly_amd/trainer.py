@@ -86,6 +86,8 @@ class Trainer(torch.nn.Module):
         self._logged = {}
         self.optimizer_kwargs = {}             # FusedAdam's guard arguments, from the `trainer:` block (optimizer_options)
         self.recipe = recipe_options(self.hparams_dict)  # weight decay / LR schedule / EMA keys of the hparams, validated
+        self.seq_train = seq_train_options(self.hparams_dict)   # the SEQ_TRAIN block, validated; None: plain NLL steps only
+        self._train_reward = None
 
     # ------------------------------------------------------------------ logging (self.log of Lightning)
     def log(self, name, value, **kw):
@@ -151,7 +153,15 @@ class Trainer(torch.nn.Module):
 
     # ------------------------------------------------------------------ steps
     def training_step(self, batch, batch_idx):
-        outputs = self.model(batch)
+        st = self.seq_train
+        if st is not None and self.global_step >= st["start_step"]:
+            # sequence-level step: sample, score and re-weight on the device, then the usual train_step
+            rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
+            outputs = self.model.seq_train_step(batch, seed=seq_train_seed(st["seed"], self.global_step, rank),
+                                                threshold=self.cfg.THRESHOLD, **st["step"])
+            self._train_reward = outputs["reward"].detach()
+        else:
+            outputs = self.model(batch)
         loss = torch.mean(outputs["loss"])
         self._train_stats = (loss.detach(), torch.mean(outputs["accuracy"]).detach())
         # the plain mean NLL next to a smoothed / weighted loss (the model returns it only then; batch["loss_weight"] reaches it as is)
@@ -446,6 +456,69 @@ def recipe_options(hparams):
             "eval_ema": eval_ema}
 
 
+SEQ_TRAIN_KEYS = ("NUM_SAMPLES", "TEMPERATURE", "TOP_K", "TOP_P", "OBJECTIVE", "BASELINE", "ALPHA", "NLL_WEIGHT", "CONSTRAIN_PLANKS",
+                  "START_STEP", "SEED")
+
+
+def seq_train_options(hparams):
+    """The optional ``SEQ_TRAIN`` block of the hparams (sequence-level training on plank F1), validated ->
+    None when the block is absent (the feature is off), else {"step": PlankModel.seq_train_step keyword arguments without the
+    seed, "start_step": int, "seed": int}.  Every bad value raises a ValueError that names its key.
+
+    ``NUM_SAMPLES`` (required, 1 .. 64), ``TEMPERATURE`` (1), ``TOP_K`` (0 = off), ``TOP_P`` (1 = off): the sampling;
+    ``OBJECTIVE`` ``reinforce`` (default) / ``risk`` with ``BASELINE`` ``none`` / ``mean`` (default; NUM_SAMPLES >= 2) / ``greedy``
+    and ``ALPHA`` (1; > 0, the sharpness of the risk's softmax); ``NLL_WEIGHT`` (0): the weight of each drawing's ground-truth row,
+    0 = no such row; ``CONSTRAIN_PLANKS`` (null: the model's own MODEL.CONSTRAIN_PLANKS; true: the default grammar; false: none);
+    ``START_STEP`` (0): the first global step trained this way, the steps before it are plain NLL steps; ``SEED`` (0): see
+    ``seq_train_seed``."""
+    from .decode import sample_params
+    from .ops import SEQ_BASELINES, SEQ_OBJECTIVES
+    blk = hparams.get("SEQ_TRAIN")
+    if blk is None:
+        return None
+    if not isinstance(blk, dict):
+        raise ValueError(f"SEQ_TRAIN must be a mapping of {SEQ_TRAIN_KEYS}, got {blk!r}")
+    unknown = sorted(set(blk) - set(SEQ_TRAIN_KEYS))
+    if unknown:
+        raise ValueError(f"SEQ_TRAIN has unknown key(s) {unknown}; known: {SEQ_TRAIN_KEYS}")
+    get = lambda k, d=None: d if blk.get(k) is None else blk.get(k)
+    if blk.get("NUM_SAMPLES") is None:
+        raise ValueError("SEQ_TRAIN needs NUM_SAMPLES (an integer in [1, 64])")
+    n, temp, top_k, top_p = blk["NUM_SAMPLES"], get("TEMPERATURE", 1.0), get("TOP_K", 0), get("TOP_P", 1.0)
+    sample_params(n, temp, top_k, top_p, 0)                        # ValueError naming NUM_SAMPLES / TEMPERATURE / TOP_K / TOP_P
+    seed = get("SEED", 0)
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"SEED must be an integer in [0, 2^32), got {seed!r}")
+    objective = get("OBJECTIVE", "reinforce")
+    if objective not in SEQ_OBJECTIVES:
+        raise ValueError(f"OBJECTIVE must be one of {SEQ_OBJECTIVES}, got {objective!r}")
+    baseline = get("BASELINE", "mean")
+    if baseline not in SEQ_BASELINES:
+        raise ValueError(f"BASELINE must be one of {SEQ_BASELINES}, got {baseline!r}")
+    if baseline == "mean" and n < 2:
+        raise ValueError(f"BASELINE 'mean' needs NUM_SAMPLES >= 2, got {n!r}")
+    alpha = _number("ALPHA", get("ALPHA", 1.0), 0.0, float("inf"), hi_open=True)
+    if alpha <= 0.0:
+        raise ValueError(f"ALPHA must be a number > 0, got {alpha!r}")
+    nll_weight = _number("NLL_WEIGHT", get("NLL_WEIGHT", 0.0), float("-inf"), float("inf"), hi_open=True)
+    if nll_weight == float("-inf"):
+        raise ValueError(f"NLL_WEIGHT must be a finite number, got {nll_weight!r}")
+    constrain = blk.get("CONSTRAIN_PLANKS")
+    if constrain is not None:
+        constrain = _bool("CONSTRAIN_PLANKS", constrain)
+    start = _count("START_STEP", get("START_STEP", 0))
+    return {"step": {"num_samples": n, "temperature": float(temp), "top_k": top_k, "top_p": float(top_p), "objective": objective,
+                     "baseline": baseline, "alpha": alpha, "nll_weight": nll_weight, "constraint": constrain},
+            "start_step": start, "seed": seed}
+
+
+def seq_train_seed(seed, global_step, rank):
+    """The sampling seed of a sequence-level training step: (SEED + 4096 * global_step + rank) mod 2^32 - a pure function of its
+    arguments, so a resumed run draws what the uninterrupted one would have drawn; distinct for every (step, rank) with rank < 4096
+    within any 2^20 consecutive steps.  (The sampler hashes the seed - pa_decode_sample_begin - so neighbouring seeds share nothing.)"""
+    return (int(seed) + 4096 * int(global_step) + int(rank)) % 2 ** 32
+
+
 def ema_checkpoint(ck):
     """A copy of checkpoint dict ``ck`` whose ``state_dict`` is the EMA: the file to hand to the reference, which knows no
     ``ema_state_dict`` key.  The raw weights are dropped from the copy, so it is for evaluation, not for an exact resume."""
@@ -548,6 +621,8 @@ def run(trainer_cls, subcommand, config, ckpt_path=None, overrides=None):
         module.log("train/loss", l); module.log("train/accuracy", a)
         if getattr(module, "_train_nll", None) is not None:
             module.log("train/nll", module._train_nll)
+        if getattr(module, "_train_reward", None) is not None:     # mean sample F1 of the epoch's last sequence-level step
+            module.log("train/reward", module._train_reward)
         module.log("train/lr", opt.param_groups[0]["lr"])      # the rate of the epoch's last step
         torch.cuda.synchronize()
         if getattr(opt, "guarded", False):                 # the guard's one read-back, where the loop synchronises anyway
