@@ -764,6 +764,29 @@ typedef struct {
 } pa_decode_plan_info;
 int pa_decode_plan(const pa_model_cfg* cfg, int32_t B, int32_t S, int32_t Tmax, pa_decode_plan_info* out);
 int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void** first_end, void** t_dev);
+/* Decode groups: a decode of B * G rows over an encoder batch of B drawings - row r belongs to drawing r / G
+ * (the layout of the beam and sampling modes below: row b*G + g).  The encoder runs ONCE on the B drawings (step 1 above, not on a
+ * batch with every drawing repeated); pa_decode_group_begin keeps one copy of the memory rows, the key-padding mask and the packed
+ * offsets - or, in the K / V-cache form, one set of cross-attention caches per layer - per DRAWING and sizes everything else for the
+ * B * G rows.  From there on the decode is one of B * G rows: pa_decode_step, pa_decode_buffers and the beam, sampling, prefix and
+ * constraint entries work on `rows` = B * G unchanged.  1 <= G <= PA_SAMPLE_MAX (PA_EINVAL otherwise).  pa_decode_begin /
+ * pa_decode_ws_bytes are the G = 1 calls.
+ * In the absorbed form two rows of a drawing share a block of the cross-attention launch where G is even and 2 * n_head <= 16 (the
+ * block's 16 head slots; PLANK_DECODE_MQ_PAIR=0: never), which streams the drawing's memory once for both.
+ *   pa_decode_group_plan: the dry run (pa_decode_plan for G = 1, field for field): `out` for B * G rows - the decisions that depend
+ *     on the row count use B * G, parts_cross counts range blocks per UNIT (block of rows_per_block rows), ws_bytes is
+ *     pa_decode_group_ws_bytes - and the group itself in `g`. */
+typedef struct {
+    int32_t rows;               /* B * G */
+    int32_t rows_per_block;     /* rows of a drawing per block of the absorbed cross-attention launch: 1 or 2 (1 without that launch) */
+    int32_t units;              /* rows / rows_per_block: the blocks of that launch before range blocks */
+    int32_t pad_;
+    int64_t mem_rows;           /* B * S: the memory rows (and mask bytes) the workspace keeps - one set per drawing */
+} pa_decode_group_info;
+int64_t pa_decode_group_ws_bytes(pa_model* m, int32_t B, int32_t G, int32_t S, int32_t Tmax);
+int pa_decode_group_begin(pa_model* m, int32_t G, void* ws, int64_t ws_bytes, int32_t Tmax, void* stream);
+int pa_decode_group_plan(const pa_model_cfg* cfg, int32_t B, int32_t G, int32_t S, int32_t Tmax, pa_decode_plan_info* out,
+                         pa_decode_group_info* g);
 /* Beam search over the same step.  K beams per drawing, 1 <= K <= PA_BEAM_MAX: the caller runs the encoder and
  * pa_decode_begin on the batch with every drawing repeated K times (row b*K + k is beam k of drawing b), then switches the decode to
  * beam mode.  pa_decode_step then ends each step with the beam selection instead of the greedy arg-max:
@@ -904,6 +927,16 @@ int pa_dec_cross_mq32_ws(float* ctx, const float* qt, const float* mem, const ui
                          int32_t S, int32_t H, int32_t d, void* ws, int64_t ws_bytes, void* stream);    /* the exact-f32 form (same scratch size) */
 int pa_dec_cross_mq32(float* ctx, const float* qt, const float* mem, const uint8_t* kpm, const int32_t* cu, int32_t B, int32_t S,
                       int32_t H, int32_t d, void* stream);
+/* The same launches for a decode group: mem / kpm / cu of B drawings, qt / ctx [B * G][H][512], row r attends over drawing r / G.
+ * rows_per_block 1 or 2 rows of a drawing per block (2: G even and 2 H <= 16, PA_EINVAL otherwise).  nparts 0: range blocks by the
+ * rule, for the launch's units = B * G / rows_per_block; n > 0: n per unit, or 1 where ws cannot hold them.  ws: 256-byte aligned,
+ * ceil(4 units / 256) * 256 zero ticket bytes + units * nparts * 40 KB.  G 1, rows_per_block 1, nparts 0 is pa_dec_cross_mq_ws. */
+int pa_dec_cross_mq_group(void* ctx, const void* qt, const void* mem, const uint8_t* kpm, const int32_t* cu, int32_t B, int32_t G,
+                          int32_t S, int32_t H, int32_t d, int32_t rows_per_block, int32_t nparts, void* ws, int64_t ws_bytes,
+                          void* stream);
+int pa_dec_cross_mq32_group(float* ctx, const float* qt, const float* mem, const uint8_t* kpm, const int32_t* cu, int32_t B, int32_t G,
+                            int32_t S, int32_t H, int32_t d, int32_t rows_per_block, int32_t nparts, void* ws, int64_t ws_bytes,
+                            void* stream);
 /* The self-attention form of the same launch (exact f32; what the token-exact decode step runs on its cache of layer-input rows):
  * rows [B][Tmax][512], of which element b attends over rows 0 .. *t_dev (the key count t + 1 is read on the device, so the launch can
  * sit in a captured graph). */

@@ -90,6 +90,11 @@ class DecodePlanInfo(C.Structure):
                 ("mq_sp_bytes", C.c_int64), ("ws_bytes", C.c_int64), ("scr_row", C.c_int64)]
 
 
+class DecodeGroupInfo(C.Structure):
+    """include/plank_hip.h pa_decode_group_info: the decode group pa_decode_group_plan reports beside the plan."""
+    _fields_ = [("rows", C.c_int32), ("rows_per_block", C.c_int32), ("units", C.c_int32), ("pad_", C.c_int32), ("mem_rows", C.c_int64)]
+
+
 class GroupDesc(C.Structure):
     _fields_ = [("idx", C.c_void_p), ("rowmap", C.c_void_p),
                 ("n", C.c_int32), ("rows", C.c_int32), ("kind", C.c_int32), ("T", C.c_int32), ("dof", C.c_int32),
@@ -258,6 +263,9 @@ def lib():
             "pa_decode_plan": (I, [P, I, I, I, P]),
             "pa_decode_ws_bytes": (I64, [P, I, I, I]),
             "pa_decode_begin": (I, [P, P, I64, I, P]),
+            "pa_decode_group_plan": (I, [P, I, I, I, I, P, P]),
+            "pa_decode_group_ws_bytes": (I64, [P, I, I, I, I]),
+            "pa_decode_group_begin": (I, [P, I, P, I64, I, P]),
             "pa_decode_step": (I, [P, P]),
             "pa_decode_buffers": (I, [P, P, P, P, P]),
             "pa_decode_beam_ws_bytes": (I64, [P, I, I, I, I]),
@@ -277,6 +285,8 @@ def lib():
             "pa_dec_cross_mq_ws": (I, [P, P, P, P, P, I, I, I, I, P, I64, P]),
             "pa_dec_cross_mq_ws_bytes": (I64, [I, I]),
             "pa_dec_cross_mq32_ws": (I, [P, P, P, P, P, I, I, I, I, P, I64, P]),
+            "pa_dec_cross_mq_group": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, I64, P]),
+            "pa_dec_cross_mq32_group": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, I64, P]),
             "pa_dec_self_mq32": (I, [P, P, P, P, I, I, I, I, P]),
             "pa_tokenise_drawings": (I, [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, D, D, D, U, U,
                                          P, P, P, P, P, P, P, P, P, P, P]),

@@ -31,10 +31,12 @@ struct BeamCopy {
 
 // What plan_decode() decides for a decode of B rows over S memory positions and Tmax steps: the fields pa_decode_plan reports
 // (include/plank_hip.h; the rule and the measurements: plan_decode) and the status pa_decode_begin / pa_decode_ws_bytes answer with.
-struct DecodePlan : pa_decode_plan_info { int status = 0; };
+// `group`: the decode group (pa_decode_group_plan) - rows = B drawings x G, rows_per_block / units of the absorbed cross launch.
+struct DecodePlan : pa_decode_plan_info { int status = 0; pa_decode_group_info group{}; };
 
 struct DecodeLayout {
-    int B = 0, S = 0, Tmax = 0;
+    int B = 0, S = 0, Tmax = 0;                // B: the decode's ROWS (drawings x G); S: memory positions per drawing
+    int G = 1, Bd = 0;                         // decode group (pa_decode_group_begin): G rows per drawing, Bd = B / G drawings - mem, kpm, cu, cross_k / cross_v are per drawing
     DecodePlan plan{};                         // of this (B, S, Tmax): the layout, pa_decode_begin, the beam reorder and the step read it
     std::vector<void*> cross_k, cross_v, self_k, self_v;   // per decoder layer, per-head contiguous: [B][H][S|Tmax][dh]
     void* kv_tmp;                              // [B*S][2d] projection output before the per-head re-layout
@@ -146,21 +148,22 @@ __global__ __launch_bounds__(256) void dec_split_heads_kernel(T* kc, T* vc, cons
 // `newkv` (self-attention): the step's in_proj output [B][3d]; key t = Lk - 1 is not in the cache yet - its K / V head
 // slices are taken from there (per-lane source select, no read-after-write through memory) and appended to the caches by
 // this block for the later steps.  That is the whole of what a separate append launch did (6 launches per step).
+// `G` (cross-attention of a decode group; 1 elsewhere): row b attends over the caches, mask and offsets of drawing b / G.
 template <typename T, int DH>
 __global__ __launch_bounds__(256) void dec_attn_kernel(T* out, const T* q, int ldq, T* kc, T* vc, int Lmax,
                                                        const uint8_t* kpm, int fixed_lk, const int32_t* t_dev,
-                                                       int d, float scale, const int32_t* cu, const T* newkv) {
+                                                       int d, float scale, const int32_t* cu, const T* newkv, int G) {
     constexpr int EB = ET<T>::EB;
     constexpr int LPR = DH / EB;             // lanes per key row
     constexpr int KPW = 64 / LPR;            // keys per wave step
     constexpr int NG = 4 * KPW;              // partial groups per block
     __shared__ float part[NG * (DH + 2)];
-    const int h = blockIdx.x, b = blockIdx.y;
+    const int h = blockIdx.x, b = blockIdx.y, bk = b / G;         // bk: whose keys (the self-attention caches are per row: G 1)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane % LPR, slot = lane / LPR;
-    const int Lk = cu ? (cu[b + 1] - cu[b]) : (fixed_lk > 0 ? fixed_lk : (*t_dev + 1));
+    const int Lk = cu ? (cu[bk + 1] - cu[bk]) : (fixed_lk > 0 ? fixed_lk : (*t_dev + 1));
     constexpr int ldkv = DH;                                     // per-head contiguous cache
-    const int64_t bh = ((int64_t)b * gridDim.x + h) * Lmax * DH + c * EB;
+    const int64_t bh = ((int64_t)bk * gridDim.x + h) * Lmax * DH + c * EB;
     const T* kb = kc + bh;
     const T* vb = vc + bh;
     const T* nk = newkv ? newkv + (int64_t)b * 3 * d + d + h * DH + c * EB : nullptr;        // this lane's chunk of the new K row
@@ -170,7 +173,7 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(T* out, const T* q, int l
         *reinterpret_cast<u32x4*>(kc + dst) = *reinterpret_cast<const u32x4*>(nk);
         *reinterpret_cast<u32x4*>(vc + dst) = *reinterpret_cast<const u32x4*>(nv);
     }
-    const uint8_t* mk = kpm ? kpm + (int64_t)b * Lmax : nullptr;
+    const uint8_t* mk = kpm ? kpm + (int64_t)bk * Lmax : nullptr;
     float qv[EB];
     {
         const T* qp = q + (int64_t)b * ldq + h * DH + c * EB;
@@ -991,6 +994,7 @@ struct DecodeSwitches {
     // range blocks of the absorbed launches (decode_mq.h mq_parts)
     int mq_parts;          // PLANK_DECODE_MQ_PARTS (0 = by rule): n > 0 forces n range blocks per row (at most 64), 1 = never
     int mq_mint;           // PLANK_DECODE_MQ_MINT (8): fewest key tiles of a range block
+    int mq_pair;           // PLANK_DECODE_MQ_PAIR (1): 0 = one row per block in the absorbed cross launch of a decode group (even G, 2 H <= 16 slots)
     // kernel variants of the absorbed launches
     int mq_nt;             // PLANK_DECODE_MQ_NT (1): 0 = default-policy DMA instead of non-temporal (aux 2; measured in the step,
                            //   B 256 x 1024: 0.958 vs 0.989 ms)
@@ -1011,6 +1015,7 @@ const DecodeSwitches& decode_switches() {
         s.mq_self_minb = env("PLANK_DECODE_MQ_SELF_MINB", 200);
         s.mq_parts = env("PLANK_DECODE_MQ_PARTS", 0);
         s.mq_mint = env("PLANK_DECODE_MQ_MINT", 8);
+        s.mq_pair = env("PLANK_DECODE_MQ_PAIR", 1);
         s.mq_nt = env("PLANK_DECODE_MQ_NT", 1);
         s.mq_swap = env("PLANK_DECODE_MQ_SWAP", 1);
         s.mq32_w8 = env("PLANK_DECODE_MQ32_W8", 1);
@@ -1020,20 +1025,21 @@ const DecodeSwitches& decode_switches() {
 }
 
 // The decode workspace for plan `pl`; base NULL is the size query (L then holds no pointers).
-size_t dec_layout(const pa_model_cfg& c, const DecodePlan& pl, DecodeLayout* L, char* base, int B, int S, int Tmax) {
+// B rows over Bd drawings (B = Bd x G): what the cross-attention reads - mem, kpm, cu_store, cross_k / cross_v, kv_tmp - is per drawing.
+size_t dec_layout(const pa_model_cfg& c, const DecodePlan& pl, DecodeLayout* L, char* base, int Bd, int B, int S, int Tmax) {
     const size_t e = c.dtype == PA_BF16 ? 2 : 4, d = c.d_model, ff = c.d_ff;
     Arena a{base, 0};
-    L->B = B; L->S = S; L->Tmax = Tmax;
+    L->B = B; L->S = S; L->Tmax = Tmax; L->Bd = Bd; L->G = B / Bd;
     L->cross_k.assign(c.n_dec, nullptr); L->cross_v.assign(c.n_dec, nullptr); L->self_k.resize(c.n_dec); L->self_v.resize(c.n_dec);
     L->wo_t.assign(c.n_dec, nullptr); L->bo_t.assign(c.n_dec, nullptr);
     for (int i = 0; i < c.n_dec; ++i) {
-        if (!pl.mq) { L->cross_k[i] = a.take((size_t)B * S * d * e); L->cross_v[i] = a.take((size_t)B * S * d * e); }
+        if (!pl.mq) { L->cross_k[i] = a.take((size_t)Bd * S * d * e); L->cross_v[i] = a.take((size_t)Bd * S * d * e); }
         L->self_k[i] = a.take((size_t)B * Tmax * d * e); L->self_v[i] = a.take((size_t)B * Tmax * d * e);
     }
     L->mem = L->qt = L->ctx = L->mq_sp = nullptr;
     if (pl.mq) {
         const size_t H = c.n_head;
-        L->mem = a.take((size_t)B * S * d * e);
+        L->mem = a.take((size_t)Bd * S * d * e);
         L->qt = a.take((size_t)B * H * d * e); L->ctx = a.take((size_t)B * H * d * e);
         if (pl.mq_sp_bytes > 0) L->mq_sp = a.take((size_t)pl.mq_sp_bytes);
         for (int i = 0; i < c.n_dec; ++i) { L->wo_t[i] = a.take(d * H * d * e); L->bo_t[i] = (float*)a.take(d * 4); }
@@ -1042,7 +1048,7 @@ size_t dec_layout(const pa_model_cfg& c, const DecodePlan& pl, DecodeLayout* L, 
         L->wo_ts.assign(c.n_dec, nullptr); L->bo_ts.assign(c.n_dec, nullptr);
         if (c.dtype == PA_BF16) for (int i = 0; i < c.n_dec; ++i) { L->wo_ts[i] = a.take(d * H * d * e); L->bo_ts[i] = (float*)a.take(d * 4); }
     }
-    L->kv_tmp = pl.mq ? nullptr : a.take((size_t)B * S * 2 * d * e);
+    L->kv_tmp = pl.mq ? nullptr : a.take((size_t)Bd * S * 2 * d * e);
     L->hid_cache = a.take((size_t)B * Tmax * d * e);
     // (x / y / z / z2 are sized for f32 rows: the bf16 step keeps its residual stream in f32, `f32res`)
     L->x = a.take(B * d * 4); L->qkv = a.take(B * 3 * d * e); L->ao = a.take(B * d * e); L->z = a.take(B * d * 4);
@@ -1053,8 +1059,8 @@ size_t dec_layout(const pa_model_cfg& c, const DecodePlan& pl, DecodeLayout* L, 
     L->mean = (float*)a.take(B * 4); L->rstd = (float*)a.take(B * 4);
     L->tokens = (int64_t*)a.take((size_t)B * Tmax * 8); L->attach = (int64_t*)a.take((size_t)B * Tmax * 8);
     L->first_end = (int32_t*)a.take(B * 4); L->t_dev = (int32_t*)a.take(256);
-    L->kpm = (uint8_t*)a.take((size_t)B * S);
-    L->cu_store = (int32_t*)a.take((size_t)(B + 1) * 4);
+    L->kpm = (uint8_t*)a.take((size_t)Bd * S);
+    L->cu_store = (int32_t*)a.take((size_t)(Bd + 1) * 4);
     L->z2 = a.take(B * d * 4);
     for (int k = 0; k < 3; ++k) { L->fw[k].resize(c.n_dec); L->fu[k].resize(c.n_dec); L->fv[k].resize(c.n_dec); }
     for (int i = 0; i < c.n_dec; ++i) {
@@ -1069,15 +1075,15 @@ size_t dec_layout(const pa_model_cfg& c, const DecodePlan& pl, DecodeLayout* L, 
 
 template <typename T>
 int launch_attn(pa_model* m, T* out, const T* q, int ldq, T* kc, T* vc, int Lmax, const uint8_t* kpm,
-                int fixed_lk, const int32_t* t_dev, int B, void* st, const int32_t* cu = nullptr, const T* newkv = nullptr) {
+                int fixed_lk, const int32_t* t_dev, int B, void* st, const int32_t* cu = nullptr, const T* newkv = nullptr, int G = 1) {
     const int d = m->cfg.d_model, H = m->cfg.n_head, dh = d / H;
     const float scale = 1.0f / sqrtf((float)dh);
     dim3 grid(H, B);
     hipStream_t s = (hipStream_t)st;
     switch (dh) {
-        case 16: PA_LAUNCH((dec_attn_kernel<T, 16>), grid, dim3(256), 0, s, out, q, ldq, kc, vc, Lmax, kpm, fixed_lk, t_dev, d, scale, cu, newkv); break;
-        case 32: PA_LAUNCH((dec_attn_kernel<T, 32>), grid, dim3(256), 0, s, out, q, ldq, kc, vc, Lmax, kpm, fixed_lk, t_dev, d, scale, cu, newkv); break;
-        case 64: PA_LAUNCH((dec_attn_kernel<T, 64>), grid, dim3(256), 0, s, out, q, ldq, kc, vc, Lmax, kpm, fixed_lk, t_dev, d, scale, cu, newkv); break;
+        case 16: PA_LAUNCH((dec_attn_kernel<T, 16>), grid, dim3(256), 0, s, out, q, ldq, kc, vc, Lmax, kpm, fixed_lk, t_dev, d, scale, cu, newkv, G); break;
+        case 32: PA_LAUNCH((dec_attn_kernel<T, 32>), grid, dim3(256), 0, s, out, q, ldq, kc, vc, Lmax, kpm, fixed_lk, t_dev, d, scale, cu, newkv, G); break;
+        case 64: PA_LAUNCH((dec_attn_kernel<T, 64>), grid, dim3(256), 0, s, out, q, ldq, kc, vc, Lmax, kpm, fixed_lk, t_dev, d, scale, cu, newkv, G); break;
         default: return PA_ESHAPE;
     }
     return 0;
@@ -1129,14 +1135,21 @@ int64_t beam_segments(const pa_model_cfg& c, const DecodePlan& pl, const DecodeL
 // agreement with the f32 tokens 0.40 -> 0.63-0.70 on 32 rows x 128 steps.  PLANK_DECODE_F32_RESID=0 restores the all-bf16 step.
 // mq: absorbed cross-attention (csrc/decode_mq.h) wherever the fold is on, with at most 8 heads; PLANK_DECODE_MQ=0 (bf16) /
 // PLANK_DECODE_MQ_F32=0 (exact f32) restore the per-layer K / V caches.
-DecodePlan plan_decode(const pa_model_cfg& c, int B, int S, int Tmax, const DecodeSwitches& sw) {
+// Decode groups (G > 1): Bd drawings x G rows.  Everything that depends on the row count - fold, f32res, mq_self_bf,
+// the 512-row limits, the self launches' range blocks - is decided for B = Bd G rows; the memory side of the layout is Bd drawings'.  The
+// absorbed cross launch puts two rows of a drawing into one block (group.rows_per_block 2: the 16 head slots of the score tile hold
+// 2 x 8 heads, decode_mq.h) when G is even and 2 n_head <= 16; PLANK_DECODE_MQ_PAIR=0 keeps one row per block.  Its range blocks are
+// per unit (block of rows).  With G 1 the plan is the ungrouped one, field for field.
+DecodePlan plan_decode(const pa_model_cfg& c, int Bd, int G, int S, int Tmax, const DecodeSwitches& sw) {
     DecodePlan r{};
     const int d = c.d_model;
     // (the configuration checks are pa_model_create's: no handle exists for a cfg that fails them)
     if (d <= 0 || c.n_head <= 0 || d % c.n_head || (c.dtype != PA_F32 && c.dtype != PA_BF16)) { r.status = PA_EINVAL; return r; }
     const int dh = d / c.n_head;
     if ((dh != 16 && dh != 32 && dh != 64) || d % 8 || c.d_ff % 8) { r.status = PA_ESHAPE; return r; }
-    if (B <= 0 || S <= 0 || Tmax <= 0 || Tmax > MAX_T || c.n_dec < 0) { r.status = PA_EINVAL; return r; }
+    if (Bd <= 0 || S <= 0 || Tmax <= 0 || Tmax > MAX_T || c.n_dec < 0 || G < 1 || G > PA_SAMPLE_MAX) { r.status = PA_EINVAL; return r; }
+    if (Bd > INT32_MAX / G) { r.status = PA_EINVAL; return r; }
+    const int B = Bd * G;                      // rows
     const bool f32 = c.dtype == PA_F32;
     const bool fold_env = sw.fold_ln >= 0 ? sw.fold_ln != 0 : (d == 512 && B <= 512);
     r.fold = fold_env && !f32 && d % 64 == 0 && c.d_ff % 32 == 0 && c.d_ff >= d && (size_t)((B + 63) / 64) * ((3 * d + 63) / 64) <= 512;
@@ -1156,14 +1169,19 @@ DecodePlan plan_decode(const pa_model_cfg& c, int B, int S, int Tmax, const Deco
                    (sw.mq_self_bf16 >= 0 ? sw.mq_self_bf16 != 0 : B >= sw.mq_self_minb);
     r.mq_nt = sw.mq_nt; r.mq_swap = sw.mq_swap; r.mq32_w8 = sw.mq32_w8;
     if (r.mq) {
-        const int ps = mq_parts(B, S, sw.mq_parts, sw.mq_mint), pt = mq_parts(B, Tmax, sw.mq_parts, sw.mq_mint);
+        r.group.rows_per_block = (sw.mq_pair != 0 && G % 2 == 0 && 2 * c.n_head <= MQ_SLOTS) ? 2 : 1;
+        r.group.units = B / r.group.rows_per_block;
+        const int ps = mq_parts(r.group.units, S, sw.mq_parts, sw.mq_mint), pt = mq_parts(B, Tmax, sw.mq_parts, sw.mq_mint);
         r.parts_cross = ps;
         if (r.mq_self || r.mq_self_bf) r.parts_self = pt;
-        r.mq_sp_bytes = mq_split_bytes(B, std::max(ps, pt));      // (sized for either launch, whichever self-attention form the step takes)
+        // (sized for either launch, whichever self-attention form the step takes; one ticket area, of the B rows - mq_split_bytes)
+        r.mq_sp_bytes = std::max(mq_split_bytes(r.group.units, ps, B), mq_split_bytes(B, pt, B));
     }
+    if (!r.mq) { r.group.rows_per_block = 1; r.group.units = B; }
+    r.group.rows = B; r.group.mem_rows = (int64_t)Bd * S;
     DecodeLayout sizes;
     BeamCopy cp;
-    r.ws_bytes = (int64_t)dec_layout(c, r, &sizes, nullptr, B, S, Tmax) + 256;
+    r.ws_bytes = (int64_t)dec_layout(c, r, &sizes, nullptr, Bd, B, S, Tmax) + 256;
     r.scr_row = beam_segments(c, r, nullptr, B, Tmax, &cp);    // (negative: the PA_E* code pa_decode_beam_ws_bytes answers with)
     return r;
 }
@@ -1272,12 +1290,12 @@ int self_attn(pa_model* m, int i, void* st) {
     return launch_attn<T>(m, (T*)L->ao, (const T*)L->qkv, 3 * d, (T*)L->self_k[i], (T*)L->self_v[i], L->Tmax, nullptr, 0, L->t_dev, L->B, st,
                           nullptr, (const T*)L->qkv);
 }
-// cross-attention of layer i over the per-head K / V caches of the memory
+// cross-attention of layer i over the per-head K / V caches of the memory (one set per drawing: the G rows of a group share it)
 template <typename T>
 int cross_attn(pa_model* m, int i, void* st) {
     DecodeLayout* L = m->dec;
     return launch_attn<T>(m, (T*)L->ao, (const T*)L->q, m->cfg.d_model, (T*)L->cross_k[i], (T*)L->cross_v[i], L->S, L->cu ? nullptr : L->kpm,
-                          L->S, L->t_dev, L->B, st, L->cu);
+                          L->S, L->t_dev, L->B, st, L->cu, (const T*)nullptr, L->G);
 }
 
 // Absorbed attention (csrc/decode_mq.h) of the query rows in L->q over `nk` rows per element of `cache`: q~_h = scale log2e W_k,h^T q_h
@@ -1285,9 +1303,10 @@ int cross_attn(pa_model* m, int i, void* st) {
 //   cross-attention: cache = the memory rows, nk = S, with the key-padding mask or the packed offsets, no t_dev, no xrow;
 //   self-attention:  cache = the layer-input rows so far, nk = Tmax of which t_dev + 1 count; the expand launch appends this step's
 //                    row from `xrow` (the residual stream's x) to the cache.
+//   G / rpb (cross-attention of a decode group): G rows share a drawing's `cache` rows, rpb of them a block (decode_mq.h mq_units).
 template <typename T, typename XT>
 int absorbed_attn(pa_model* m, const T* Wk, T* cache, int nk, int nparts, const int32_t* t_dev, const uint8_t* kpm, const int32_t* cu,
-                  const XT* xrow, hipStream_t s) {
+                  const XT* xrow, hipStream_t s, int G = 1, int rpb = 1) {
     DecodeLayout* L = m->dec;
     const DecodePlan& pl = L->plan;
     const int d = m->cfg.d_model, H = m->cfg.n_head, B = L->B;
@@ -1300,10 +1319,10 @@ int absorbed_attn(pa_model* m, const T* Wk, T* cache, int nk, int nparts, const 
     else return PA_ESHAPE;
     if constexpr (sizeof(T) == 2)
         return launch_cross_mq((bf16*)L->ctx, (const bf16*)L->qt, (const bf16*)cache, kpm, cu, B, nk, H, d, s, nparts, pl.mq_nt, pl.mq_swap,
-                               L->mq_sp, pl.mq_sp_bytes, t_dev);
+                               L->mq_sp, pl.mq_sp_bytes, t_dev, G, rpb, B);
     else
         return launch_cross_mq32((float*)L->ctx, (const float*)L->qt, (const float*)cache, kpm, cu, B, nk, H, d, s, nparts, pl.mq32_w8, t_dev,
-                                 L->mq_sp, pl.mq_sp_bytes);
+                                 L->mq_sp, pl.mq_sp_bytes, G, rpb, B);
 }
 
 // The residual stream of the folded step in its two number formats.  Pre-norm rows live in z (k = 0) / z2 (k = 1), normed rows in x / y.
@@ -1384,7 +1403,7 @@ int folded_layers(pa_model* m, const Stream& rs, void* st) {
         RC(rs.norm_linear(1, 1, i, PF(pb + D_N1_W), PF(pb + D_N1_B), L->y, L->q, d, 0));
         if (pl.mq) {
             RC((absorbed_attn<T, T>(m, (const T*)PL(pb + D_CA_IN_W) + (size_t)d * d, (T*)L->mem, L->S, pl.parts_cross, nullptr,
-                                    L->cu ? nullptr : L->kpm, L->cu, (const T*)nullptr, s)));
+                                    L->cu ? nullptr : L->kpm, L->cu, (const T*)nullptr, s, L->G, pl.group.rows_per_block)));
         } else {
             RC(cross_attn<T>(m, i, st));
         }
@@ -1479,37 +1498,47 @@ void pa_decode_free_layout(pa_model* m) {
     if (m && m->dec) { delete m->dec; m->dec = nullptr; }
 }
 
-extern "C" int64_t pa_decode_ws_bytes(pa_model* m, int32_t B, int32_t S, int32_t Tmax) {
+extern "C" int64_t pa_decode_group_ws_bytes(pa_model* m, int32_t B, int32_t G, int32_t S, int32_t Tmax) {
     if (!m) return PA_EINVAL;
-    const DecodePlan pl = plan_decode(m->cfg, B, S, Tmax, decode_switches());
+    const DecodePlan pl = plan_decode(m->cfg, B, G, S, Tmax, decode_switches());
     return pl.status ? pl.status : pl.ws_bytes;
 }
+extern "C" int64_t pa_decode_ws_bytes(pa_model* m, int32_t B, int32_t S, int32_t Tmax) { return pa_decode_group_ws_bytes(m, B, 1, S, Tmax); }
 
 static_assert(sizeof(pa_decode_plan_info) == 72, "pa_decode_plan_info is 72 bytes (plankassembly_amd/_lib.py mirrors it)");
 // The dry run of pa_decode_begin / pa_decode_ws_bytes / pa_decode_beam_ws_bytes (include/plank_hip.h): no handle, no device, no launch.
-extern "C" int pa_decode_plan(const pa_model_cfg* cfg, int32_t B, int32_t S, int32_t Tmax, pa_decode_plan_info* out) {
-    if (!cfg || !out) return PA_EINVAL;
+static_assert(sizeof(pa_decode_group_info) == 24, "pa_decode_group_info is 24 bytes (plankassembly_amd/_lib.py mirrors it)");
+extern "C" int pa_decode_group_plan(const pa_model_cfg* cfg, int32_t B, int32_t G, int32_t S, int32_t Tmax, pa_decode_plan_info* out,
+                                    pa_decode_group_info* g) {
+    if (!cfg || !out || !g) return PA_EINVAL;
     *out = pa_decode_plan_info();
-    const DecodePlan pl = plan_decode(*cfg, B, S, Tmax, decode_switches());
-    if (!pl.status) *out = pl;
+    *g = pa_decode_group_info();
+    const DecodePlan pl = plan_decode(*cfg, B, G, S, Tmax, decode_switches());
+    if (!pl.status) { *out = pl; *g = pl.group; }
     return pl.status;
+}
+extern "C" int pa_decode_plan(const pa_model_cfg* cfg, int32_t B, int32_t S, int32_t Tmax, pa_decode_plan_info* out) {
+    pa_decode_group_info g;
+    return pa_decode_group_plan(cfg, B, 1, S, Tmax, out, &g);
 }
 
 // Requires a preceding encoder-only pa_model_train_fwd (batch.output_value == NULL) on the same stream:
 // uses its memory, batch size, sequence length and input_mask.
-extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t Tmax, void* stream) {
-    if (!m || !m->bound || !ws || m->B <= 0 || Tmax <= 0 || Tmax > MAX_T) return PA_EINVAL;
+// Decode group: the encoder ran on m->B DRAWINGS; the decode is laid out for m->B * G rows (row r belongs to drawing r / G) over one
+// copy of the memory, mask and offsets - or one set of cross-attention K / V caches - per drawing.  G 1 is the plain decode.
+extern "C" int pa_decode_group_begin(pa_model* m, int32_t G, void* ws, int64_t ws_bytes, int32_t Tmax, void* stream) {
+    if (!m || !m->bound || !ws || m->B <= 0 || Tmax <= 0 || Tmax > MAX_T || G < 1 || G > PA_SAMPLE_MAX) return PA_EINVAL;
     if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return PA_EALIGN;
     const pa_model_cfg& c = m->cfg;
-    const DecodePlan pl = plan_decode(c, m->B, m->S, Tmax, decode_switches());
+    const DecodePlan pl = plan_decode(c, m->B, G, m->S, Tmax, decode_switches());
     if (pl.status) return pl.status;
-    if (pl.ws_bytes - 256 > ws_bytes) return PA_EINVAL;
+    if (pl.ws_bytes > ws_bytes) return PA_EINVAL;          // (the documented size; the layout itself ends 256 bytes before it)
     if (!m->dec) m->dec = new (std::nothrow) DecodeLayout();
     if (!m->dec) return PA_EINVAL;
     DecodeLayout* L = m->dec;
     L->plan = pl;
-    dec_layout(c, pl, L, (char*)ws, m->B, m->S, Tmax);
-    const int d = c.d_model, B = m->B, S = m->S;
+    dec_layout(c, pl, L, (char*)ws, m->B, m->B * G, m->S, Tmax);
+    const int d = c.d_model, Bd = m->B, B = Bd * G, S = m->S;            // B: rows
     const size_t e = c.dtype == PA_BF16 ? 2 : 4;
     const void* memory = c.has_enc_norm ? m->memory : m->X[c.n_enc];
     hipStream_t s = (hipStream_t)stream;
@@ -1569,10 +1598,10 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
     }
     L->cu = nullptr;
     if (m->batch.cu_in) {
-        HIP_RC(hipMemcpyAsync(L->cu_store, m->batch.cu_in, (size_t)(B + 1) * 4, hipMemcpyDeviceToDevice, s));
+        HIP_RC(hipMemcpyAsync(L->cu_store, m->batch.cu_in, (size_t)(Bd + 1) * 4, hipMemcpyDeviceToDevice, s));
         L->cu = L->cu_store;
     }
-    HIP_RC(hipMemcpyAsync(L->kpm, m->batch.input_mask, (size_t)B * S, hipMemcpyDeviceToDevice, s));
+    HIP_RC(hipMemcpyAsync(L->kpm, m->batch.input_mask, (size_t)Bd * S, hipMemcpyDeviceToDevice, s));
     HIP_RC(hipMemsetAsync(L->first_end, 0xFF, (size_t)B * 4, s));
     HIP_RC(hipMemsetAsync(L->t_dev, 0, 8, s));                  // step counter (and the word beside it, once the removed fused tail's ticket)
     if (L->mq_sp)                                               // the range blocks' tickets (every launch leaves them zero again)
@@ -1582,6 +1611,10 @@ extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t 
     HIP_RC(hipMemsetAsync(L->tokens, 0, (size_t)B * Tmax * 8, s));
     HIP_RC(hipMemsetAsync(L->attach, 0xFF, (size_t)B * Tmax * 8, s));
     return 0;
+}
+
+extern "C" int pa_decode_begin(pa_model* m, void* ws, int64_t ws_bytes, int32_t Tmax, void* stream) {
+    return pa_decode_group_begin(m, 1, ws, ws_bytes, Tmax, stream);
 }
 
 extern "C" int pa_decode_step(pa_model* m, void* stream) {
@@ -1630,6 +1663,35 @@ extern "C" int pa_dec_cross_mq32_ws(float* ctx, const float* qt, const float* me
                              ws_bytes);
 }
 
+// The launches of a decode group on their own (include/plank_hip.h; tests / tools/group_time.py): B drawings' memory rows (mem, kpm, cu
+// as above), qt / ctx [B * G][H][512] - row r attends over drawing r / G; rows_per_block 1 or 2 rows of a drawing per block
+// (PA_EINVAL for 2 with an odd G or 2 H > 16); nparts 0 = range blocks by the rule for the launch's units, n > 0 = n per unit (1 where
+// ws - 256-byte aligned, its ticket words zero - cannot hold them: ceil(4 units / 256) * 256 + units * nparts * 40 KB).
+template <typename T>
+static int dec_cross_group(T* ctx, const T* qt, const T* mem, const uint8_t* kpm, const int32_t* cu, int B, int G, int S, int H, int d,
+                           int rpb, int nparts, void* ws, int64_t ws_bytes, void* stream) {
+    if (!ctx || !qt || !mem || B <= 0 || G < 1 || G > PA_SAMPLE_MAX || B > INT32_MAX / G || nparts < 0 || H < 1) return PA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(qt) | reinterpret_cast<uintptr_t>(mem) | reinterpret_cast<uintptr_t>(ctx)) & 15) return PA_EALIGN;
+    MqUnits un;
+    if (int rc = mq_units(B * G, H, G, rpb, &un)) return rc;
+    const int parts = nparts > 0 ? std::min(nparts, 64) : standalone_parts(un.units, S);
+    const DecodeSwitches& sw = decode_switches();
+    if constexpr (sizeof(T) == 2)
+        return launch_cross_mq(ctx, qt, mem, kpm, cu, B * G, S, H, d, (hipStream_t)stream, parts, sw.mq_nt, sw.mq_swap, ws, ws_bytes, nullptr, G, rpb);
+    else
+        return launch_cross_mq32(ctx, qt, mem, kpm, cu, B * G, S, H, d, (hipStream_t)stream, parts, sw.mq32_w8, nullptr, ws, ws_bytes, G, rpb);
+}
+extern "C" int pa_dec_cross_mq_group(void* ctx, const void* qt, const void* mem, const uint8_t* kpm, const int32_t* cu, int32_t B, int32_t G,
+                                     int32_t S, int32_t H, int32_t d, int32_t rows_per_block, int32_t nparts, void* ws, int64_t ws_bytes,
+                                     void* stream) {
+    return dec_cross_group<bf16>((bf16*)ctx, (const bf16*)qt, (const bf16*)mem, kpm, cu, B, G, S, H, d, rows_per_block, nparts, ws, ws_bytes, stream);
+}
+extern "C" int pa_dec_cross_mq32_group(float* ctx, const float* qt, const float* mem, const uint8_t* kpm, const int32_t* cu, int32_t B,
+                                       int32_t G, int32_t S, int32_t H, int32_t d, int32_t rows_per_block, int32_t nparts, void* ws,
+                                       int64_t ws_bytes, void* stream) {
+    return dec_cross_group<float>(ctx, qt, mem, kpm, cu, B, G, S, H, d, rows_per_block, nparts, ws, ws_bytes, stream);
+}
+
 extern "C" int pa_dec_self_mq32(float* ctx, const float* qt, const float* xcache, const int32_t* t_dev, int32_t B, int32_t Tmax,
                                 int32_t H, int32_t d, void* stream) {
     if (!ctx || !qt || !xcache || !t_dev) return PA_EINVAL;
@@ -1646,7 +1708,7 @@ extern "C" int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void
 // Beam search over a begun decode (include/plank_hip.h).
 extern "C" int64_t pa_decode_beam_ws_bytes(pa_model* m, int32_t rows, int32_t S, int32_t Tmax, int32_t K) {
     if (!m || K < 1 || K > PA_BEAM_MAX || rows <= 0 || rows % K != 0) return PA_EINVAL;
-    const DecodePlan pl = plan_decode(m->cfg, rows, S, Tmax, decode_switches());
+    const DecodePlan pl = plan_decode(m->cfg, rows, 1, S, Tmax, decode_switches());   // (scr_row depends on the rows, not on their grouping)
     if (pl.status || pl.scr_row < 0) return pl.status ? pl.status : pl.scr_row;
     return (int64_t)beam_layout(nullptr, nullptr, rows, K, pl.scr_row) + 256;
 }

@@ -22,7 +22,11 @@
 
 namespace {
 typedef short mq_s16x4 __attribute__((ext_vector_type(4)));
-constexpr int MQ_D = 512, MQ_KT = 16, MQ_ROW = MQ_D * 2, MQ_TILE = MQ_KT * MQ_ROW, MQ_NS = 8, MQ_MAXH = 8;
+constexpr int MQ_D = 512, MQ_KT = 16, MQ_ROW = MQ_D * 2, MQ_TILE = MQ_KT * MQ_ROW, MQ_NS = 8, MQ_MAXH = 8, MQ_SLOTS = 16;
+// (MQ_MAXH: the model's heads; MQ_SLOTS: the head slots of a block = the columns of its 16 x 16 score tile.  A block serves one UNIT:
+// one query row's H heads, or - decode groups, rows_per_block 2 - the 2 H heads of two neighbouring rows of the same drawing, which
+// lie in qt / ctx as [rows / 2][2 H][512] already.  `gdiv` units share a drawing: unit u reads the memory, mask and offsets of drawing
+// u / gdiv and the query / context rows of unit u; with gdiv 1 every address is the one-row-per-drawing one.)
 constexpr int MQ_MAXS = 16384;                // key-padding mask bytes kept in LDS behind the ring
 
 // LDS image of a tile: row r (key) at r * 1024; its 16-byte chunk c sits at position (c & 48) | ((c ^ r) & 15) so that the 16 rows a
@@ -51,14 +55,16 @@ template <bool SWAP> __device__ __forceinline__ float mq_rows_max(float v) {
 constexpr int MQ_SP_BYTES = 40 * 1024;
 template <int AUX, bool SWAP, bool MASK>
 __global__ __launch_bounds__(256, 1) void dec_cross_mq_kernel(bf16* ctx, const bf16* qt, const bf16* mem, const uint8_t* kpm,
-                                                              const int32_t* cu, int S, int H, int nparts, char* sp, const int32_t* t_dev) {
+                                                              const int32_t* cu, int S, int H, int nparts, char* sp, const int32_t* t_dev,
+                                                              int gdiv, int tick_bytes) {
     extern __shared__ __attribute__((aligned(256))) char mq_smem[];
-    const int b = blockIdx.x / nparts, part = blockIdx.x - b * nparts, tid = threadIdx.x, lane = tid & 63;
+    const int u = blockIdx.x / nparts, part = blockIdx.x - u * nparts, tid = threadIdx.x, lane = tid & 63;     // u: the unit, H = its head slots
+    const int b = u / gdiv;                                               // the drawing whose keys it reads
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, g = lane >> 4;
     const int row0 = cu ? cu[b] : b * S;
     const int Lk = t_dev ? *t_dev + 1 : (cu ? cu[b + 1] - row0 : S);     // (t_dev: rows 0 .. t of a [B][S] row cache - the self-attention form)
-    bf16* out = ctx + (size_t)b * H * MQ_D;
+    bf16* out = ctx + (size_t)u * H * MQ_D;
     if (Lk <= 0) {                                                      // (block-uniform) no key: zeros, as dec_attn_kernel
         if (part == 0) for (int idx = tid; idx < H * MQ_D; idx += 256) out[idx] = (bf16)0.f;
         return;
@@ -75,7 +81,7 @@ __global__ __launch_bounds__(256, 1) void dec_cross_mq_kernel(bf16* ctx, const b
     // query fragments (B operand of the score product): head slot n, dims 32 ks + 8 g .. + 7; slots >= H are zero
     u32x4 qf[16];
     {
-        const bf16* qrow = qt + ((size_t)b * H + min(n, H - 1)) * MQ_D + 8 * g;
+        const bf16* qrow = qt + ((size_t)u * H + min(n, H - 1)) * MQ_D + 8 * g;
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) {
             u32x4 v = *reinterpret_cast<const u32x4*>(qrow + 32 * ks);
@@ -205,13 +211,13 @@ __global__ __launch_bounds__(256, 1) void dec_cross_mq_kernel(bf16* ctx, const b
     l_run += __shfl_xor(l_run, 32);
     if (nparts > 1) {
         // publish (O^T, m, l); the element's last range block to arrive rescales all of them to the common reference point and stores
-        char* const pbase = sp + 256 * (((size_t)gridDim.x / nparts * 4 + 255) / 256) + (size_t)b * nparts * MQ_SP_BYTES;
+        char* const pbase = sp + tick_bytes + (size_t)u * nparts * MQ_SP_BYTES;
         const SplitOut so(pbase + (size_t)part * MQ_SP_BYTES, MQ_SP_BYTES);
 #pragma unroll
         for (int nb = 0; nb < 8; ++nb) so.put(nb, 256, acc[nb]);
         so.put(8, 256, f32x4{m_run, l_run, 0.f, 0.f});
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // (the ring's last LDS reads are done before its first bytes become the flag)
-        if (!split_arrive(reinterpret_cast<int*>(sp) + b, nparts, reinterpret_cast<int*>(mq_smem))) return;
+        if (!split_arrive(reinterpret_cast<int*>(sp) + u, nparts, reinterpret_cast<int*>(mq_smem))) return;
         // merged IN RANGE ORDER (own partial re-read like the others): the same sums whichever block arrives last
         float m_all = -INFINITY;
         for (int pp = 0; pp < nparts; ++pp) m_all = fmaxf(m_all, split_get(pbase + (size_t)pp * MQ_SP_BYTES, 8, 256, MQ_SP_BYTES)[0]);
@@ -253,14 +259,14 @@ __global__ __launch_bounds__(256, 1) void dec_cross_mq_kernel(bf16* ctx, const b
 constexpr int MQF_ROW = MQ_D * 4, MQF_TILE = MQ_KT * MQF_ROW, MQF_NS = 4, MQF_SCR = 2 * 4 * 1024;
 template <bool MASK>
 __global__ __launch_bounds__(256, 1) void dec_cross_mq32_kernel(float* ctx, const float* qt, const float* mem, const uint8_t* kpm,
-                                                                const int32_t* cu, int S, int H, const int32_t* t_dev) {
+                                                                const int32_t* cu, int S, int H, const int32_t* t_dev, int gdiv) {
     extern __shared__ __attribute__((aligned(256))) char mq_smem[];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int u = blockIdx.x, b = u / gdiv, tid = threadIdx.x, lane = tid & 63;      // (unit and drawing: dec_cross_mq_kernel)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, g = lane >> 4;
     const int row0 = cu ? cu[b] : b * S;
     const int Lk = t_dev ? *t_dev + 1 : (cu ? cu[b + 1] - row0 : S);     // (t_dev: rows 0 .. t of a [B][S] cache - the self-attention form)
-    float* out = ctx + (size_t)b * H * MQ_D;
+    float* out = ctx + (size_t)u * H * MQ_D;
     if (Lk <= 0) {
         for (int idx = tid; idx < H * MQ_D; idx += 256) out[idx] = 0.f;
         return;
@@ -276,7 +282,7 @@ __global__ __launch_bounds__(256, 1) void dec_cross_mq32_kernel(float* ctx, cons
     // query values (B operand of the partial score product): head slot n, k-step 4 j + e <-> dim 128 wave + 32 g + 4 j + e
     f32x4 qf[8];
     {
-        const float* qrow = qt + ((size_t)b * H + min(n, H - 1)) * MQ_D + 128 * wave + 32 * g;
+        const float* qrow = qt + ((size_t)u * H + min(n, H - 1)) * MQ_D + 128 * wave + 32 * g;
 #pragma unroll
         for (int j = 0; j < 8; ++j) qf[j] = n < H ? *reinterpret_cast<const f32x4*>(qrow + 4 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]), "+v"(qf[4]), "+v"(qf[5]), "+v"(qf[6]), "+v"(qf[7]) :: "memory");
@@ -420,14 +426,16 @@ __global__ __launch_bounds__(256, 1) void dec_cross_mq32_kernel(float* ctx, cons
 constexpr int MQ8_SCR = 2 * 8 * 1024;
 template <bool MASK>
 __global__ __launch_bounds__(512, 1) void dec_cross_mq32w8_kernel(float* ctx, const float* qt, const float* mem, const uint8_t* kpm,
-                                                                  const int32_t* cu, int S, int H, const int32_t* t_dev, int nparts, char* sp) {
+                                                                  const int32_t* cu, int S, int H, const int32_t* t_dev, int nparts, char* sp,
+                                                                  int gdiv, int tick_bytes) {
     extern __shared__ __attribute__((aligned(256))) char mq_smem[];
-    const int b = blockIdx.x / nparts, part = blockIdx.x - b * nparts, tid = threadIdx.x, lane = tid & 63;     // (range blocks: dec_cross_mq_kernel)
+    const int u = blockIdx.x / nparts, part = blockIdx.x - u * nparts, tid = threadIdx.x, lane = tid & 63;     // (units, range blocks: dec_cross_mq_kernel)
+    const int b = u / gdiv;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, g = lane >> 4;
     const int row0 = cu ? cu[b] : b * S;
     const int Lk = t_dev ? *t_dev + 1 : (cu ? cu[b + 1] - row0 : S);
-    float* out = ctx + (size_t)b * H * MQ_D;
+    float* out = ctx + (size_t)u * H * MQ_D;
     if (Lk <= 0) {
         if (part == 0) for (int idx = tid; idx < H * MQ_D; idx += 512) out[idx] = 0.f;
         return;
@@ -443,7 +451,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_mq32w8_kernel(float* ctx, co
     // query values: head slot n, k-step 4 j + e <-> dim 64 wave + 16 g + 4 j + e
     f32x4 qf[4];
     {
-        const float* qrow = qt + ((size_t)b * H + min(n, H - 1)) * MQ_D + 64 * wave + 16 * g;
+        const float* qrow = qt + ((size_t)u * H + min(n, H - 1)) * MQ_D + 64 * wave + 16 * g;
 #pragma unroll
         for (int j = 0; j < 4; ++j) qf[j] = n < H ? *reinterpret_cast<const f32x4*>(qrow + 4 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]) :: "memory");
@@ -582,13 +590,13 @@ __global__ __launch_bounds__(512, 1) void dec_cross_mq32w8_kernel(float* ctx, co
     if (nparts > 1) {
         // (as dec_cross_mq_kernel) publish (O^T, m, l); the element's last range block to arrive merges them IN RANGE ORDER - a fixed
         // summation order whichever block arrives last: the token-exact path stays run-to-run identical
-        char* const pbase = sp + 256 * (((size_t)gridDim.x / nparts * 4 + 255) / 256) + (size_t)b * nparts * MQ_SP_BYTES;
+        char* const pbase = sp + tick_bytes + (size_t)u * nparts * MQ_SP_BYTES;
         const SplitOut so(pbase + (size_t)part * MQ_SP_BYTES, MQ_SP_BYTES);
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) so.put(nb, 512, acc[nb]);
         so.put(4, 512, f32x4{m_run, l_run, 0.f, 0.f});
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (!split_arrive(reinterpret_cast<int*>(sp) + b, nparts, reinterpret_cast<int*>(mq_smem))) return;
+        if (!split_arrive(reinterpret_cast<int*>(sp) + u, nparts, reinterpret_cast<int*>(mq_smem))) return;
         float m_all = -INFINITY;
         for (int pp = 0; pp < nparts; ++pp) m_all = fmaxf(m_all, split_get(pbase + (size_t)pp * MQ_SP_BYTES, 4, 512, MQ_SP_BYTES)[0]);
         const float ms = m_all == -INFINITY ? 0.f : m_all;
@@ -740,7 +748,7 @@ __global__ __launch_bounds__(256) void mq_absorb_o_kernel(T* Wt, float* bt, cons
     }
 }
 
-// range blocks per batch element for a launch of B elements with up to S keys: enough blocks to fill the chip, at least `mint` key
+// range blocks per unit for a launch of B units (rows, or - decode groups - pairs of rows) with up to S keys: enough blocks to fill the chip, at least `mint` key
 // tiles each (DecodeSwitches::mq_mint); `force` > 0 (DecodeSwitches::mq_parts) replaces the rule, at most 64 either way
 int mq_parts(int B, int S, int force, int mint) {
     if (force > 0) return force > 64 ? 64 : force;
@@ -749,17 +757,38 @@ int mq_parts(int B, int S, int force, int mint) {
     if (p > ntiles / (mint > 0 ? mint : 1)) p = ntiles / (mint > 0 ? mint : 1);
     return p < 1 ? 1 : (p > 64 ? 64 : p);
 }
-int64_t mq_split_bytes(int B, int nparts) { return nparts > 1 ? (((int64_t)B * 4 + 255) / 256) * 256 + (int64_t)B * nparts * MQ_SP_BYTES : 0; }
+// scratch of a launch of `n` units with `nparts` range blocks each: one ticket word per unit - the ticket area sized for `tick_n`
+// units (a step whose launches differ in their unit count keeps ONE ticket area, of its largest launch, so that no launch's partials
+// lie where another launch expects zero tickets) - then the partials
+int64_t mq_tick_bytes(int n) { return (((int64_t)n * 4 + 255) / 256) * 256; }
+int64_t mq_split_bytes(int n, int nparts, int tick_n = 0) {
+    return nparts > 1 ? mq_tick_bytes(tick_n > n ? tick_n : n) + (int64_t)n * nparts * MQ_SP_BYTES : 0;
+}
 
-// The two launches take their choices from the caller: `nparts` range blocks per element (1 when the scratch `sp` cannot hold them),
-// `nt` / `swap` / `w8` the kernel variants (DecodeSwitches).
+// How the `rows` query rows of a launch map to blocks (decode groups): `G` neighbouring rows share a drawing (its memory rows, mask,
+// offsets), `rpb` = 1 or 2 of them share a block.  2 needs an even G and 2 H head slots within the score tile.
+struct MqUnits { int units, slots, gdiv; };
+int mq_units(int rows, int H, int G, int rpb, MqUnits* o) {
+    if (G < 1 || rows % G || (rpb != 1 && rpb != 2)) return PA_EINVAL;
+    if (rpb == 2 && (G % 2 || 2 * H > MQ_SLOTS)) return PA_EINVAL;
+    o->units = rows / rpb; o->slots = H * rpb; o->gdiv = G / rpb;
+    return 0;
+}
+
+// The two launches take their choices from the caller: `nparts` range blocks per unit (1 when the scratch `sp` cannot hold them),
+// `nt` / `swap` / `w8` the kernel variants (DecodeSwitches), `G` / `rpb` the decode group (mq_units; the self-attention form - t_dev -
+// is per row: 1 / 1), `tick_n` the units the caller's ticket area was sized for (0: this launch's own).
 int launch_cross_mq(bf16* ctx, const bf16* qt, const bf16* mem, const uint8_t* kpm, const int32_t* cu, int B, int S, int H, int d,
-                    hipStream_t s, int nparts, int nt, int swap, void* sp = nullptr, int64_t sp_bytes = 0, const int32_t* t_dev = nullptr) {
+                    hipStream_t s, int nparts, int nt, int swap, void* sp = nullptr, int64_t sp_bytes = 0, const int32_t* t_dev = nullptr,
+                    int G = 1, int rpb = 1, int tick_n = 0) {
     if (d != MQ_D || H < 1 || H > MQ_MAXH || B <= 0 || S <= 0 || S > MQ_MAXS) return PA_ESHAPE;
+    MqUnits un;
+    if (int rc = mq_units(B, H, G, rpb, &un)) return rc;
+    if (t_dev && (G != 1 || rpb != 1)) return PA_EINVAL;
     const int lds = MQ_NS * MQ_TILE + ((!cu && kpm) ? (S + 31) / 16 * 16 : 0);
     static bool attr_done = false;
     constexpr int MAXLDS = MQ_NS * MQ_TILE + MQ_MAXS + 32;
-    typedef void (*KernT)(bf16*, const bf16*, const bf16*, const uint8_t*, const int32_t*, int, int, int, char*, const int32_t*);
+    typedef void (*KernT)(bf16*, const bf16*, const bf16*, const uint8_t*, const int32_t*, int, int, int, char*, const int32_t*, int, int);
     static const KernT ks[8] = {dec_cross_mq_kernel<0, false, false>, dec_cross_mq_kernel<0, false, true>, dec_cross_mq_kernel<0, true, false>,
                                 dec_cross_mq_kernel<0, true, true>,   dec_cross_mq_kernel<2, false, false>, dec_cross_mq_kernel<2, false, true>,
                                 dec_cross_mq_kernel<2, true, false>,  dec_cross_mq_kernel<2, true, true>};
@@ -771,16 +800,20 @@ int launch_cross_mq(bf16* ctx, const bf16* qt, const bf16* mem, const uint8_t* k
         attr_done = true;
     }
     const bool mask = !cu && kpm;
-    if (nparts < 1 || !sp || mq_split_bytes(B, nparts) > sp_bytes || (reinterpret_cast<uintptr_t>(sp) & 255)) nparts = 1;
-    PA_LAUNCH(ks[(nt ? 4 : 0) + (swap ? 2 : 0) + (mask ? 1 : 0)], dim3(B * nparts), dim3(256), lds, s, ctx, qt, mem, kpm, cu, S, H, nparts,
-              static_cast<char*>(sp), t_dev);
+    if (nparts < 1 || !sp || mq_split_bytes(un.units, nparts, tick_n) > sp_bytes || (reinterpret_cast<uintptr_t>(sp) & 255)) nparts = 1;
+    PA_LAUNCH(ks[(nt ? 4 : 0) + (swap ? 2 : 0) + (mask ? 1 : 0)], dim3(un.units * nparts), dim3(256), lds, s, ctx, qt, mem, kpm, cu, S, un.slots,
+              nparts, static_cast<char*>(sp), t_dev, un.gdiv, (int)mq_tick_bytes(tick_n > un.units ? tick_n : un.units));
     return 0;
 }
 
 int launch_cross_mq32(float* ctx, const float* qt, const float* mem, const uint8_t* kpm, const int32_t* cu, int B, int S, int H, int d,
-                      hipStream_t s, int nparts, int w8, const int32_t* t_dev = nullptr, void* sp = nullptr, int64_t sp_bytes = 0) {
+                      hipStream_t s, int nparts, int w8, const int32_t* t_dev = nullptr, void* sp = nullptr, int64_t sp_bytes = 0,
+                      int G = 1, int rpb = 1, int tick_n = 0) {
     constexpr int MAXS32 = 16000;                 // (ring + partial-score slots + mask bytes within 160 KB)
     if (d != MQ_D || H < 1 || H > MQ_MAXH || B <= 0 || S <= 0 || S > MAXS32) return PA_ESHAPE;
+    MqUnits un;
+    if (int rc = mq_units(B, H, G, rpb, &un)) return rc;
+    if (t_dev && (G != 1 || rpb != 1)) return PA_EINVAL;
     const bool mask = !cu && kpm;
     static bool attr_done = false;
     if (!attr_done) {
@@ -794,15 +827,17 @@ int launch_cross_mq32(float* ctx, const float* qt, const float* mem, const uint8
         attr_done = true;
     }
     const int mbytes = mask ? (S + 31) / 16 * 16 : 0;
+    const int U = un.units, HS = un.slots;
     if (w8) {
         const int lds = MQF_NS * MQF_TILE + MQ8_SCR + mbytes;
-        if (nparts < 1 || !sp || mq_split_bytes(B, nparts) > sp_bytes || (reinterpret_cast<uintptr_t>(sp) & 255)) nparts = 1;
-        if (mask) PA_LAUNCH(dec_cross_mq32w8_kernel<true>, dim3(B * nparts), dim3(512), lds, s, ctx, qt, mem, kpm, cu, S, H, t_dev, nparts, static_cast<char*>(sp));
-        else PA_LAUNCH(dec_cross_mq32w8_kernel<false>, dim3(B * nparts), dim3(512), lds, s, ctx, qt, mem, kpm, cu, S, H, t_dev, nparts, static_cast<char*>(sp));
+        if (nparts < 1 || !sp || mq_split_bytes(U, nparts, tick_n) > sp_bytes || (reinterpret_cast<uintptr_t>(sp) & 255)) nparts = 1;
+        const int tick = (int)mq_tick_bytes(tick_n > U ? tick_n : U);
+        if (mask) PA_LAUNCH(dec_cross_mq32w8_kernel<true>, dim3(U * nparts), dim3(512), lds, s, ctx, qt, mem, kpm, cu, S, HS, t_dev, nparts, static_cast<char*>(sp), un.gdiv, tick);
+        else PA_LAUNCH(dec_cross_mq32w8_kernel<false>, dim3(U * nparts), dim3(512), lds, s, ctx, qt, mem, kpm, cu, S, HS, t_dev, nparts, static_cast<char*>(sp), un.gdiv, tick);
     } else {
         const int lds = MQF_NS * MQF_TILE + MQF_SCR + mbytes;
-        if (mask) PA_LAUNCH(dec_cross_mq32_kernel<true>, dim3(B), dim3(256), lds, s, ctx, qt, mem, kpm, cu, S, H, t_dev);
-        else PA_LAUNCH(dec_cross_mq32_kernel<false>, dim3(B), dim3(256), lds, s, ctx, qt, mem, kpm, cu, S, H, t_dev);
+        if (mask) PA_LAUNCH(dec_cross_mq32_kernel<true>, dim3(U), dim3(256), lds, s, ctx, qt, mem, kpm, cu, S, HS, t_dev, un.gdiv);
+        else PA_LAUNCH(dec_cross_mq32_kernel<false>, dim3(U), dim3(256), lds, s, ctx, qt, mem, kpm, cu, S, HS, t_dev, un.gdiv);
     }
     return 0;
 }

@@ -62,7 +62,7 @@ class _Lane:
         self.enc_ws = _Arena(slack=512)
         self.ws = _Arena()
         self.keep = None
-        self.key = None                                # what a captured step depends on: (B, S, Tmax, flat, shadow, ws pointer, ws allocation)
+        self.key = None                                # what a captured step depends on: (B, S, Tmax, flat, shadow, ws pointer, ws allocation, group)
         self.stream = None
 
     def h(self):
@@ -73,8 +73,9 @@ class _Lane:
             L.lib().pa_model_destroy(self.handle)
             self.handle = None
 
-    def begin(self, batch, Tmax):
-        """Encoder + cross-K/V projection + state reset for this lane's samples.  Returns B."""
+    def begin(self, batch, Tmax, group=1):
+        """Encoder on the batch as given + cross-K/V projection + state reset for this lane's rows: ``group`` decode rows per drawing
+        of the batch over one memory per drawing (pa_decode_group_begin).  Returns the rows, B * group."""
         m, lib = self.model, L.lib()
         b, keep = m._make_batch(batch, with_output=False)
         b.T = 1
@@ -83,12 +84,13 @@ class _Lane:
         stats = torch.empty(L.lib().pa_model_stats_floats(), dtype=torch.float32, device=dev)   # include/plank_hip.h: f32[8]
         L.check(lib.pa_model_train_fwd(self.h(), C.byref(b), C.c_void_p(base), C.c_int64(room), C.c_uint32(0), 0,
                                        L.ptr(stats), L.stream()), "pa_model_train_fwd(encoder)")
-        base, room = self.ws.ensure(L.ws_bytes("pa_decode_ws_bytes", self.h(), b.B, b.S, Tmax), dev)
-        L.check(lib.pa_decode_begin(self.h(), C.c_void_p(base), C.c_int64(room), Tmax, L.stream()), "pa_decode_begin")
+        group = int(group)
+        base, room = self.ws.ensure(L.ws_bytes("pa_decode_group_ws_bytes", self.h(), b.B, group, b.S, Tmax), dev)
+        L.check(lib.pa_decode_group_begin(self.h(), group, C.c_void_p(base), C.c_int64(room), Tmax, L.stream()), "pa_decode_group_begin")
         self.keep = (b, keep, stats)
         shadow = m._shadow.data_ptr() if m._shadow is not None else 0
-        self.key = (b.B, b.S, Tmax, m._flat.data_ptr(), shadow, self.ws.data_ptr(), self.ws.grown)
-        return b.B
+        self.key = (b.B, b.S, Tmax, m._flat.data_ptr(), shadow, self.ws.data_ptr(), self.ws.grown, group)
+        return b.B * group
 
     def step(self):
         L.check(L.lib().pa_decode_step(self.h(), L.stream()), "pa_decode_step")
@@ -201,6 +203,7 @@ def check_planks(tokens, end, n_val, min_planks=1):
 
 class GreedyDecoder:
     _repeat = None                                     # rows per drawing (BeamDecoder: K, SampleDecoder: N; None: the batch as given)
+    share_encoder = False                              # the _repeat rows of a drawing as a decode group over ONE encoder pass and memory
 
     def __init__(self, model, use_graph=None, check_every=16, strict_graph=False, lanes=None):
         """``strict_graph``: a failed hipGraph capture raises instead of falling back to eager launches (benchmarks must
@@ -252,16 +255,22 @@ class GreedyDecoder:
         return None
 
     def begin(self, batch, max_len=None):
-        """Encoder (on the batch with every drawing repeated ``_repeat`` times) + cross-K/V projection + state reset + the mode's
+        """Encoder (on the batch with every drawing repeated ``_repeat`` times, or - ``share_encoder`` - on the batch as given, its
+        ``_repeat`` rows per drawing a decode group over the drawing's one memory) + cross-K/V projection + state reset + the mode's
         begin.  Returns (rows, Tmax)."""
         m = self.model
-        if self._repeat is not None:
+        group = 1
+        if self._repeat is not None and self.share_encoder:
+            group = self._repeat
+        elif self._repeat is not None:
             batch = _repeat_batch(batch, self._repeat)
             if m.unpad:
                 batch = m.prepare_batch(batch, groups=False)
         Tmax = int(max_len or m.max_output_length)
-        B = batch["input_value"].shape[0]
+        B = batch["input_value"].shape[0] * group
         n = 2 if (self.max_lanes >= 2 and B >= 32) else 1
+        if n == 2 and group > 1:
+            raise ValueError("a decode group (share_encoder) needs the one-lane decode (lanes=1)")
         self._bounds = [(0, B)] if n == 1 else [(0, B // 2), (B // 2, B)]
         self._active = n
         if n == 2 and self._side is None:
@@ -271,7 +280,7 @@ class GreedyDecoder:
             ln = self._lane(i)
             sub = batch if n == 1 else m.prepare_batch(_split_batch(batch, lo, hi), groups=False) if m.unpad else _split_batch(batch, lo, hi)
             if i == 0:
-                ln.begin(sub, Tmax)
+                ln.begin(sub, Tmax, group)
             else:
                 self._side.wait_stream(main)
                 with torch.cuda.stream(self._side):
@@ -433,6 +442,12 @@ class GreedyDecoder:
         return tokens, attach
 
 
+def _share_flag(v):
+    if not isinstance(v, bool):
+        raise ValueError(f"SHARE_ENCODER must be a bool, got {v!r}")
+    return v
+
+
 def _repeat_batch(batch, K):
     """Every drawing repeated K times, drawing-major (row b*K + k is beam k of drawing b)."""
     out = {}
@@ -455,10 +470,12 @@ class BeamDecoder(GreedyDecoder):
     ends with the beam selection (per-row top-K of the greedy step's own distribution, merge per drawing, history reorder)
     instead of the greedy arg-max.  Always one lane.  ``length_penalty`` (alpha) only changes the final ranking of a drawing's
     beams, by score / len^alpha (len = first END + 1, or Tmax); 0 ranks by the raw cumulative log-probability.  K = 1 gives the
-    greedy tokens up to each row's first END (PAD / attach -1 after it)."""
+    greedy tokens up to each row's first END (PAD / attach -1 after it).  ``share_encoder``: the encoder runs on the batch as given and
+    the K beams of a drawing decode over its one memory - the same search."""
 
-    def __init__(self, model, beam_size, length_penalty=0.0, use_graph=None, check_every=16, strict_graph=False):
+    def __init__(self, model, beam_size, length_penalty=0.0, use_graph=None, check_every=16, strict_graph=False, share_encoder=False):
         super().__init__(model, use_graph=use_graph, check_every=check_every, strict_graph=strict_graph, lanes=1)
+        self.share_encoder = _share_flag(share_encoder)
         self.beam_size = int(beam_size)
         self.length_penalty = float(length_penalty)
         self._repeat = self.beam_size
@@ -557,11 +574,13 @@ class SampleDecoder(GreedyDecoder):
     The draw of sample n of drawing b at step t depends on (seed, b, n, t) only, so drawings are keyed by their position in the
     batch.  Always one lane.  Every sample carries its score, the sum of log p of its tokens under the model (untempered,
     unfiltered); ``length_penalty`` (alpha) ranks a drawing's samples by score / len^alpha.  top_k = 1 gives the greedy tokens up
-    to each row's first END (PAD / attach -1 after it)."""
+    to each row's first END (PAD / attach -1 after it).  ``share_encoder``: the encoder runs on the batch as given and the N samples
+    of a drawing decode over its one memory - the same draws (seed, b, n, t)."""
 
     def __init__(self, model, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0, use_graph=None,
-                 check_every=16, strict_graph=False):
+                 check_every=16, strict_graph=False, share_encoder=False):
         super().__init__(model, use_graph=use_graph, check_every=check_every, strict_graph=strict_graph, lanes=1)
+        self.share_encoder = _share_flag(share_encoder)
         self.params = sample_params(num_samples, temperature, top_k, top_p, seed)
         self.num_samples = int(num_samples)
         self.length_penalty = float(length_penalty)

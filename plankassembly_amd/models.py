@@ -136,8 +136,12 @@ class PlankModel(nn.Module):
                  normalize_before=True, num_encoder_layers=6, num_decoder_layers=6, num_view=3, num_type=2,
                  num_input_dof=4, num_output_dof=6, max_input_length=400, max_output_length=128, vocab_size=514,
                  token=None, compute_dtype=None, beam_size=1, length_penalty=0.0, num_samples=0, temperature=1.0, top_k=0,
-                 top_p=1.0, sample_seed=0, constraint=None, sample_select=None, label_smoothing=0.0):
+                 top_p=1.0, sample_seed=0, constraint=None, sample_select=None, label_smoothing=0.0, share_encoder=False):
         super().__init__()
+        # beam search, sampling and sequence-level training decode the rows of a drawing as a decode group over ONE encoder pass and
+        # memory instead of repeating the drawing; the calls' share_encoder=None means this setting
+        from .decode import _share_flag
+        self.share_encoder = _share_flag(share_encoder)
         # train_step's objective: eps of the label smoothing over a row's allowed classes; 0 = the reference's loss
         if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)) or not 0.0 <= label_smoothing < 1.0:
             raise ValueError(f"LABEL_SMOOTHING must be a number in [0, 1), got {label_smoothing!r}")
@@ -931,7 +935,7 @@ class PlankModel(nn.Module):
             raise ValueError(f"SAMPLE_SELECT must be 'consensus' or none, got {select!r}")
         return select
 
-    def eval_step(self, batch, prefix=None, constraint=None, parse=True):
+    def eval_step(self, batch, prefix=None, constraint=None, parse=True, share_encoder=None):
         """reference models.py:267-323: greedy autoregressive sampling (KV-cached HIP decode); beam search instead when the
         model was built with beam_size > 1 (cfg.MODEL.BEAM_SIZE), seeded sampling of num_samples per drawing, best returned,
         when it was built with num_samples >= 1 (cfg.MODEL.NUM_SAMPLES).
@@ -949,10 +953,11 @@ class PlankModel(nn.Module):
         constraint = self._grammar(constraint)
         if self.beam_size > 1:
             return self.beam_search(batch, self.beam_size, self.length_penalty, prefix=prefix, constraint=constraint or False,
-                                    parse=parse)
+                                    parse=parse, share_encoder=share_encoder)
         if self.num_samples >= 1:
             return self.sample(batch, self.num_samples, length_penalty=self.length_penalty, prefix=prefix,
-                               constraint=constraint or False, parse=parse, select=self.sample_select, **self.sample_cfg)
+                               constraint=constraint or False, parse=parse, select=self.sample_select, share_encoder=share_encoder,
+                               **self.sample_cfg)
         dec = self._decoder_for()
         output, attach = dec.run(batch, prefix=prefix, constraint=constraint)
         return self._decode_dict(batch, {"tokens": output, "attach": attach, "prefix_scores": dec.last_prefix_scores,
@@ -1000,10 +1005,11 @@ class PlankModel(nn.Module):
         scores = torch.where(summed, logprobs.double(), torch.zeros((), dtype=torch.float64)).sum(1).float()
         return {"scores": scores, "logprobs": logprobs, "lengths": table[0]}
 
-    def complete(self, batch, num_planks, constraint=None):
+    def complete(self, batch, num_planks, constraint=None, share_encoder=None):
         """eval_step continuing the first ``num_planks`` planks of the ground truth: the first num_planks * num_output_dof
         positions of ``batch["output_value"]``, clipped before each row's END, with the pointers of ``batch["output_label"]`` when
-        the batch has it, as the forced prefix.  ``constraint``: as in eval_step (the forced positions are not filtered)."""
+        the batch has it, as the forced prefix.  ``constraint``: as in eval_step (the forced positions are not filtered);
+        ``share_encoder``: as in beam_search / sample (nothing to share in a greedy decode)."""
         tok = batch["output_value"]
         P = min(int(num_planks) * self.num_output_dof, tok.shape[1])
         tok = tok[:, :P].detach().cpu()
@@ -1013,7 +1019,7 @@ class PlankModel(nn.Module):
         if "output_label" in batch:
             label = batch["output_label"][:, :P].detach().cpu()
             prefix["attach"] = torch.where(label >= self.vocab_size, label - self.vocab_size, torch.full_like(label, -1))
-        return self.eval_step(batch, prefix=prefix, constraint=constraint)
+        return self.eval_step(batch, prefix=prefix, constraint=constraint, share_encoder=share_encoder)
 
     def _decoder_for(self, key=None, build=None):
         """The way into a decoder: a bound handle, fresh bf16 shadows, and the cached decoder - the greedy one (``_decoder``; None
@@ -1029,6 +1035,16 @@ class PlankModel(nn.Module):
         if dec is None:
             dec = self._mode_decoders[key] = build()
         return dec
+
+    def _share(self, share_encoder):
+        """A call's ``share_encoder``: None = the model's setting (MODEL.SHARE_ENCODER), else a bool."""
+        from .decode import _share_flag
+        return self.share_encoder if share_encoder is None else _share_flag(share_encoder)
+
+    @staticmethod
+    def _share_key(share):
+        """What sharing adds to a decoder's cache key (_decoder_for): nothing when off - the keys of the unshared decoders stay."""
+        return ("share_encoder",) if share else ()
 
     def _decode_dict(self, batch, r, prefix, parse=True):
         """The eval_step dict of a decoder's result ``r``: the best row's parse (``parse``), then what the mode adds - ``scores``,
@@ -1047,16 +1063,19 @@ class PlankModel(nn.Module):
             groundtruths.append(self.parse_sequence(batch["output_value"][i].to(output.device)))
         return {"samples": output, "attach": attach, "predicts": predicts, "groundtruths": groundtruths}
 
-    def beam_search(self, batch, beam_size, length_penalty=0.0, prefix=None, constraint=None, parse=True):
+    def beam_search(self, batch, beam_size, length_penalty=0.0, prefix=None, constraint=None, parse=True, share_encoder=None):
         """Beam-search decode (decode.BeamDecoder): the eval_step dict of the best beam of every drawing plus ``scores``
         [B, K], the cumulative log-probabilities of all beams in final-ranking order.  ``prefix``: as in eval_step, per drawing;
-        ``constraint`` / ``parse``: as in eval_step."""
+        ``constraint`` / ``parse``: as in eval_step.  ``share_encoder`` (None: the model's setting): one encoder pass and one memory
+        per drawing for its K beams."""
         from .decode import BeamDecoder
-        dec = self._decoder_for(("beam", int(beam_size), float(length_penalty)), lambda: BeamDecoder(self, beam_size, length_penalty))
+        share = self._share(share_encoder)
+        dec = self._decoder_for(("beam", int(beam_size), float(length_penalty)) + self._share_key(share),
+                                lambda: BeamDecoder(self, beam_size, length_penalty, share_encoder=share))
         return self._decode_dict(batch, dec.run(batch, prefix=prefix, constraint=self._grammar(constraint)), prefix, parse)
 
     def sample(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0, prefix=None,
-               constraint=None, parse=True, select=None, consensus_threshold=None):
+               constraint=None, parse=True, select=None, consensus_threshold=None, share_encoder=None):
         """Seeded sampling decode (decode.SampleDecoder): the eval_step dict of the best sample of every drawing (by score /
         len^length_penalty) plus ``scores`` [B, N] (log-likelihood of every sample) and ``sample_tokens`` / ``sample_attach``
         [B, N, n], samples in final-ranking order.  The same seed and batch give the same samples on every call.  ``prefix``: as in
@@ -1066,11 +1085,16 @@ class PlankModel(nn.Module):
         are those of the sample that agrees best with the other N - 1 as a set of planks - the largest sum of pairwise plank F1 at
         IoU > ``consensus_threshold`` (default 0.5), the most likely one among equals - instead of the most likely one.  The dict
         then also has ``consensus_f1`` float64 [B, N] (each sample's mean F1 against the others) and ``consensus_index`` int64 [B];
-        ``scores`` / ``sample_tokens`` / ``sample_attach`` and their order are those of ``select=None``."""
+        ``scores`` / ``sample_tokens`` / ``sample_attach`` and their order are those of ``select=None``.
+
+        ``share_encoder`` (None: the model's setting): one encoder pass and one memory per drawing for its N samples (DESIGN.md
+        section 25); the draws are those of (seed, b, n, t) either way."""
         from .decode import SampleDecoder, consensus_select
         select = self._check_select(select)
-        key = ("sample", int(num_samples), float(temperature), int(top_k), float(top_p), float(length_penalty))
-        dec = self._decoder_for(key, lambda: SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, length_penalty))
+        share = self._share(share_encoder)
+        key = ("sample", int(num_samples), float(temperature), int(top_k), float(top_p), float(length_penalty)) + self._share_key(share)
+        dec = self._decoder_for(key, lambda: SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, length_penalty,
+                                                           share_encoder=share))
         r = dec.run(batch, seed=seed, prefix=prefix, constraint=self._grammar(constraint))
         if select == "consensus":
             if self.num_output_dof != 6:
@@ -1096,7 +1120,7 @@ class PlankModel(nn.Module):
         return pairs
 
     def sequence_batch(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, objective="reinforce", baseline="mean",
-                       alpha=1.0, nll_weight=0.0, constraint=None, threshold=0.5):
+                       alpha=1.0, nll_weight=0.0, constraint=None, threshold=0.5, share_encoder=None):
         """The training batch of one sequence-level step on plank F1, built on the device under no_grad:
         ``num_samples`` seeded samples per drawing (decode.SampleDecoder.run_device), one ops.plank_match of the sample rows against
         ``batch["output_value"]`` (zero-extent sample planks dropped, edges at IoU > ``threshold``, ties no edges), then one
@@ -1104,7 +1128,8 @@ class PlankModel(nn.Module):
         weight of its F1 - ``objective`` ``reinforce`` with ``baseline`` ``none`` / ``mean`` (of the drawing's other samples) /
         ``greedy`` (the F1 of ``eval_step``'s decode, run before the sampling), or ``risk`` (expected 1 - F1 under the softmax of
         ``alpha`` * the samples' log-likelihoods) - and, with ``nll_weight`` != 0, the ground-truth row of each drawing with that
-        weight.  ``constraint``: as in eval_step, for the sampling and the greedy baseline.
+        weight.  ``constraint``: as in eval_step, for the sampling and the greedy baseline.  ``share_encoder`` (None: the model's
+        setting): the sampling runs one encoder pass per drawing.
 
         Returns a batch for ``train_step``: the input keys with every drawing repeated G = num_samples + (nll_weight != 0) times,
         ``output_value`` / ``output_label`` / ``output_mask`` [B*G, T] and ``loss_weight`` [B*G], plus ``reward`` f32 [B, N],
@@ -1132,8 +1157,9 @@ class PlankModel(nn.Module):
                 # decoder's buffers hold only until its next begin
                 greedy = self.eval_step(batch, constraint=constraint, parse=False)["samples"]
                 base_counts = ops.plank_match(greedy, truth, end_token=end, filter_a=True, filter_b=False, threshold=threshold)
-            key = ("sample", N, float(temperature), int(top_k), float(top_p), 0.0)
-            dec = self._decoder_for(key, lambda: SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, 0.0))
+            share = self._share(share_encoder)
+            key = ("sample", N, float(temperature), int(top_k), float(top_p), 0.0) + self._share_key(share)
+            dec = self._decoder_for(key, lambda: SampleDecoder(self, num_samples, temperature, top_k, top_p, seed, 0.0, share_encoder=share))
             tokens, attach, first_end, scores = dec.run_device(batch, seed=seed, constraint=self._grammar(constraint))
             counts = ops.plank_match(tokens, truth, self._seq_pairs(B, N, dev), end_token=end, filter_a=True, filter_b=False,
                                      threshold=threshold, check_pairs=False)
@@ -1200,7 +1226,9 @@ def build_model(cfg):
     (bool, default off): eval_step decodes - in whichever mode - under the plank grammar of DESIGN.md section 15, with
     ``MIN_PLANKS`` (default 1) and ``MAX_PLANKS`` (default: the last plank boundary of the decode).  ``SAMPLE_SELECT``
     (``consensus``; default none): which of the NUM_SAMPLES samples eval_step returns (PlankModel.sample); it needs NUM_SAMPLES
-    >= 1.  ``LABEL_SMOOTHING`` (a number in [0, 1), default 0): eps of train_step's label smoothing.  A bad value, SAMPLE_SELECT without samples, or
+>= 1.  ``LABEL_SMOOTHING`` (a number in [0, 1), default 0): eps of train_step's label smoothing.  ``SHARE_ENCODER`` (bool, default
+    off): beam search, sampling and sequence-level training run one encoder pass and keep one memory per drawing (DESIGN.md section
+    25).  A bad value, SAMPLE_SELECT without samples, or
     NUM_SAMPLES >= 1 together with BEAM_SIZE > 1, raises ValueError."""
     model_cfg = cfg.MODEL
 
@@ -1222,4 +1250,4 @@ def build_model(cfg):
         cfg.TOKEN, compute_dtype=dtype, beam_size=opt("BEAM_SIZE", 1), length_penalty=float(opt("LENGTH_PENALTY", 0.0)),
         num_samples=opt("NUM_SAMPLES", 0), temperature=opt("TEMPERATURE", 1.0), top_k=opt("TOP_K", 0), top_p=opt("TOP_P", 1.0),
         sample_seed=opt("SAMPLE_SEED", 0), constraint=grammar, sample_select=opt("SAMPLE_SELECT"),
-        label_smoothing=opt("LABEL_SMOOTHING", 0.0))
+        label_smoothing=opt("LABEL_SMOOTHING", 0.0), share_encoder=opt("SHARE_ENCODER", False))

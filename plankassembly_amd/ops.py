@@ -542,6 +542,23 @@ def dec_cross_mq(qt, mem, *, kpm=None, cu=None, S=None, ws=None):
     return ctx
 
 
+def dec_cross_mq_group(qt, mem, group, *, kpm=None, cu=None, S=None, rows_per_block=1, nparts=0, ws=None):
+    """dec_cross_mq for a decode group (pa_dec_cross_mq_group / pa_dec_cross_mq32_group): qt [B * group, H, 512],
+    mem / kpm / cu of B drawings - row r attends over drawing r // group.  ``rows_per_block`` 1 or 2 rows of a drawing per block;
+    ``nparts`` 0 = range blocks by the rule, n = n per unit; ``ws``: zeroed uint8 scratch that holds them (None: one block per unit)."""
+    R, H, d = qt.shape
+    if R % int(group):
+        raise ValueError(f"{R} rows are no multiple of the group {group}")
+    if cu is None:
+        S = mem.shape[1]
+    ctx = torch.empty_like(qt)
+    name = "pa_dec_cross_mq32_group" if qt.dtype == torch.float32 else "pa_dec_cross_mq_group"
+    L.check(getattr(L.lib(), name)(L.ptr(ctx), L.ptr(qt), L.ptr(mem), L.ptr(kpm), L.ptr(cu), R // int(group), int(group), int(S), H, d,
+                                   int(rows_per_block), int(nparts), L.ptr(ws), C.c_int64(ws.numel() if ws is not None else 0),
+                                   L.stream()), name)
+    return ctx
+
+
 def dec_cross_mq_ws(B, S, device):
     """Zeroed scratch for dec_cross_mq(..., ws=): None when the library would launch one block per element anyway."""
     n = int(L.lib().pa_dec_cross_mq_ws_bytes(int(B), int(S)))

@@ -457,7 +457,7 @@ def recipe_options(hparams):
 
 
 SEQ_TRAIN_KEYS = ("NUM_SAMPLES", "TEMPERATURE", "TOP_K", "TOP_P", "OBJECTIVE", "BASELINE", "ALPHA", "NLL_WEIGHT", "CONSTRAIN_PLANKS",
-                  "START_STEP", "SEED")
+                  "START_STEP", "SEED", "SHARE_ENCODER")
 
 
 def seq_train_options(hparams):
@@ -470,7 +470,8 @@ def seq_train_options(hparams):
     and ``ALPHA`` (1; > 0, the sharpness of the risk's softmax); ``NLL_WEIGHT`` (0): the weight of each drawing's ground-truth row,
     0 = no such row; ``CONSTRAIN_PLANKS`` (null: the model's own MODEL.CONSTRAIN_PLANKS; true: the default grammar; false: none);
     ``START_STEP`` (0): the first global step trained this way, the steps before it are plain NLL steps; ``SEED`` (0): see
-    ``seq_train_seed``."""
+    ``seq_train_seed``; ``SHARE_ENCODER`` (null: the model's own MODEL.SHARE_ENCODER; a bool: the step's ``share_encoder``, DESIGN.md
+    section 25 - the key is in "step" only when the block sets it)."""
     from .decode import sample_params
     from .ops import SEQ_BASELINES, SEQ_OBJECTIVES
     blk = hparams.get("SEQ_TRAIN")
@@ -507,9 +508,11 @@ def seq_train_options(hparams):
     if constrain is not None:
         constrain = _bool("CONSTRAIN_PLANKS", constrain)
     start = _count("START_STEP", get("START_STEP", 0))
-    return {"step": {"num_samples": n, "temperature": float(temp), "top_k": top_k, "top_p": float(top_p), "objective": objective,
-                     "baseline": baseline, "alpha": alpha, "nll_weight": nll_weight, "constraint": constrain},
-            "start_step": start, "seed": seed}
+    step = {"num_samples": n, "temperature": float(temp), "top_k": top_k, "top_p": float(top_p), "objective": objective,
+            "baseline": baseline, "alpha": alpha, "nll_weight": nll_weight, "constraint": constrain}
+    if blk.get("SHARE_ENCODER") is not None:
+        step["share_encoder"] = _bool("SHARE_ENCODER", blk["SHARE_ENCODER"])
+    return {"step": step, "start_step": start, "seed": seed}
 
 
 def seq_train_seed(seed, global_step, rank):
