@@ -36,6 +36,14 @@ struct DecAct {
     float *lse_sa, *lse_ca, *m1, *r1, *m2, *r2, *m3, *r3;
 };
 
+// The mixture NLL behind its five public entries (rowops.hip): `e` NULL = the plain objective; `plain_stats`: pa_mixture_nll_fwd's form.
+int nll_fwd_launch(float* stats, float* row_lse, const float* vocab, int32_t ldv, const float* ptr, const float* sw,
+                   const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad, const pa_loss_ext* e, bool plain_stats,
+                   void* stream);
+int nll_bwd_launch(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, const float* stats, const float* row_lse,
+                   const float* vocab, int32_t ldv, const float* ptr, const float* sw, const int64_t* label, int32_t B, int32_t T,
+                   int32_t V, int32_t pad, float gscale, const float* upstream, const pa_loss_ext* e, void* stream);
+
 struct DecodeLayout;
 struct pa_model {
     pa_model_cfg cfg;
@@ -59,7 +67,7 @@ struct pa_model {
     // words are zeroed whenever the region moved or changed size (pa_model_train_fwd)
     void* attn_ws = nullptr; int64_t attn_ws_bytes = 0; void* attn_ws_zeroed = nullptr; int64_t attn_ws_zeroed_bytes = 0;
     const float* upstream = nullptr;      // d(loss) of the caller's autograd (pa_model_set_upstream), or nullptr = stats[3]
-    bool loss_on = false; pa_loss_ext loss{};   // the extended objective (pa_model_set_loss); off = the calls of the reference-parity step
+    bool loss_on = false; pa_loss_ext loss{};   // the extended objective (pa_model_set_loss); off = the plain objective of the reference-parity step
     // backward temporaries
     void *gA, *gB, *gC, *gD, *gE, *gF, *gQ3, *gKV, *dmem, *dvlog, *dplog; float *dsw, *delta, *partial, *splitws;
     void* gPre = nullptr;                        // ACTIVATION gelu: the FFN pre-activation, recomputed by the backward pass (rows x d_ff)

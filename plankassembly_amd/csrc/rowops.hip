@@ -5,6 +5,7 @@
 #include <type_traits>
 #include "pa_device.h"
 #include "../../include/plank_hip.h"
+#include "model.h"      // (the mixture-NLL launchers runtime.hip calls)
 
 namespace {
 
@@ -733,7 +734,7 @@ __device__ __forceinline__ RowStat wave_merge(RowStat a) {
     return a;
 }
 
-constexpr int NLL_ROWS = 4;      // rows per block (one per wave); the three statistics leave a block as ONE atomic each
+constexpr int NLL_ROWS = 4;      // rows per block (one per wave); the statistics leave a block as ONE atomic each
 constexpr int NLL_VSLOTS = 16;   // a lane holds up to 16 vocabulary logits (V <= 1024) / 4 pointer logits (T <= 256) of its row:
 constexpr int NLL_PSLOTS = 4;    // all loads are issued up front, unconditionally (clamped index), then reduced in order
 // FIXED (the stats8 form): the blocks' NLL sums meet in a 64-bit fixed-point word (stats[6..7], 2^-30 units) - integer addition is
@@ -741,125 +742,21 @@ constexpr int NLL_PSLOTS = 4;    // all loads are issued up front, unconditional
 // the arrival order: the same batch twice differed by 3 ulp).  The two counts are whole numbers below 2^24 and exact in any order.  A
 // sum that is not finite, or too large for the word, still goes to stats[0] as a float and reaches the loss.
 constexpr float NLL_FIXED_ONE = 1073741824.f;                        // 2^30
-template <bool FIXED>
+// The extended objective (include/plank_hip.h pa_loss_ext): label smoothing over the ALLOWED classes of a row
+// (the V vocabulary entries and the i pointers j < i - the filled pointers get no mass), a weight per drawing or per token, and the
+// plain -log p(label) per token next to the objective.
+struct NllExt { float eps; const float* weight; int per_token; float* token_nll; float* ext_stats; };
+// The one forward kernel: <false, false> pa_mixture_nll_fwd, <true, false> pa_mixture_nll_fwd_fin, <true, true> pa_mixture_nll_fwd_ext.
+// No load sits under a range test: row, label, weight and logit indices are clamped, every load is issued, and what is out of range is
+// discarded in the arithmetic.  Only EXT keeps the smoothing's two lane sums, loads a weight, writes token_nll and carries the fourth
+// statistic (the plain NLL sum: word ext_stats[0..1], fall-back ext_stats[2]); with eps == 0 and no weight its stats and row_lse are the others'.
+template <bool FIXED, bool EXT>
 __global__ __launch_bounds__(256) void mixture_nll_fwd_kernel(float* stats, float* row_lse, const float* vocab, int ldv,
                                                               const float* ptr, const float* sw, const int64_t* label,
-                                                              int B, int Tn, int V, int pad) {
-    __shared__ float red[4][3];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float a_nll = 0.f, a_cnt = 0.f, a_hit = 0.f;
-    for (int rr = wave; rr < NLL_ROWS; rr += 4) {
-        const int64_t row = (int64_t)blockIdx.x * NLL_ROWS + rr;
-        if (row >= (int64_t)B * Tn) break;
-        const int i = (int)(row % Tn);
-        const float* vr = vocab + row * ldv;
-        const float* pr = ptr + row * Tn;
-        RowStat sv{-INFINITY, 0.f, 0x7fffffff}, sp{-INFINITY, 0.f, 0x7fffffff};
-        if (V <= 64 * NLL_VSLOTS && Tn <= 64 * NLL_PSLOTS) {
-            float xv[NLL_VSLOTS], xp[NLL_PSLOTS];
-#pragma unroll
-            for (int q = 0; q < NLL_VSLOTS; ++q) xv[q] = vr[min(lane + 64 * q, V - 1)];
-#pragma unroll
-            for (int q = 0; q < NLL_PSLOTS; ++q) xp[q] = pr[min(lane + 64 * q, Tn - 1)];
-#pragma unroll
-            for (int q = 0; q < NLL_VSLOTS; ++q) { const int k = lane + 64 * q; if (k < V) online(sv, xv[q], k); }
-#pragma unroll
-            for (int q = 0; q < NLL_PSLOTS; ++q) { const int j = lane + 64 * q; if (j < Tn) online(sp, (j >= i) ? 1e-6f : xp[q], j); }
-        } else {
-            for (int k = lane; k < V; k += 64) online(sv, vr[k], k);
-            for (int j = lane; j < Tn; j += 64) online(sp, (j >= i) ? 1e-6f : pr[j], j);
-        }
-        sv = wave_merge(sv);
-        sp = wave_merge(sp);
-        const float lse_v = sv.m + logf(sv.s), lse_p = sp.m + logf(sp.s);
-        const float prob = 1.0f / (1.0f + expf(-sw[row]));
-        const float lv = logf(fmaxf(1.0f - prob, 1e-6f)), lp = logf(fmaxf(prob, 1e-6f));
-        if (lane == 0) {
-            row_lse[row * 2] = lse_v; row_lse[row * 2 + 1] = lse_p;
-            const int64_t lab = label[row];
-            if (lab != pad) {
-                float logp;
-                if (lab < V) logp = vr[lab] - lse_v + lv;
-                else { const int j = (int)(lab - V); logp = ((j >= i) ? 1e-6f : pr[j]) - lse_p + lp; }
-                const float best_v = sv.m - lse_v + lv, best_p = sp.m - lse_p + lp;
-                const int64_t pred = (best_p > best_v) ? (int64_t)V + sp.arg : (int64_t)sv.arg;
-                a_nll -= logp; a_cnt += 1.0f;
-                if (pred == lab) a_hit += 1.0f;
-            }
-        }
-    }
-    if (lane == 0) { red[wave][0] = a_nll; red[wave][1] = a_cnt; red[wave][2] = a_hit; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const float v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-        if (FIXED && threadIdx.x == 0 && fabsf(v) < 4294967296.f) {                       // (false for a NaN)
-            if (v != 0.f) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 6), (unsigned long long)__float2ll_rn(v * NLL_FIXED_ONE));
-        } else if (v != 0.f) atomicAdd(stats + threadIdx.x, v);
-    }
-}
-// stats8 form (pa_mixture_nll_fwd_fin): loss = nll / count, accuracy = hits / (count + 1e-10) (reference models.py:226-231) and the
-// upstream gradient's default 1.0 in ONE one-wave launch behind the forward kernel - what five tiny torch launches and a memset did
-// on the step's serial chain before.  Two in-kernel forms were measured first and lost: the last block (ticket)
-// finishing the sums behind __threadfence() took the forward kernel from 11.7 to 38.6 us, and with returning device-scope atomics
-// instead of the fence to 33.8 us (512 blocks x 4 returning atomics on four words) - more than the launches they replaced.
-__global__ void mixture_nll_finish_kernel(float* stats) {
-    if (threadIdx.x == 0) {
-        const long long q = *reinterpret_cast<const long long*>(stats + 6);               // the fixed-point NLL sum (8-byte aligned)
-        const float s0 = stats[0] + (float)((double)q * (1.0 / (double)NLL_FIXED_ONE)), s1 = stats[1], s2 = stats[2];
-        stats[0] = s0;
-        stats[4] = s0 / s1; stats[5] = s2 / (s1 + 1e-10f); stats[3] = 1.0f;
-    }
-}
-
-template <typename TO>
-__global__ __launch_bounds__(256) void mixture_nll_bwd_kernel(TO* dvocab, TO* dptr, float* dsw, const float* stats,
-                                                              const float* row_lse, const float* vocab, int ldv,
-                                                              const float* ptr, const float* sw, const int64_t* label,
-                                                              int B, int Tn, int V, int pad, float gscale, const float* upstream) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= (int64_t)B * Tn) return;
-    const int i = (int)(row % Tn);
-    const int64_t lab = label[row];
-    TO* dv = dvocab + row * ldv;
-    TO* dp = dptr + row * Tn;
-    if (lab == pad) {
-        for (int k = lane; k < ldv; k += 64) st1<TO>(dv + k, 0.f);
-        for (int j = lane; j < Tn; j += 64) st1<TO>(dp + j, 0.f);
-        if (lane == 0) dsw[row] = 0.f;
-        return;
-    }
-    const float g = gscale * (upstream ? *upstream : stats[3]) / stats[1];      // upstream d(loss), device resident (stats[3] unless given)
-    const float prob = 1.0f / (1.0f + expf(-sw[row]));
-    if (lab < V) {
-        const float lse_v = row_lse[row * 2];
-        const float* vr = vocab + row * ldv;
-        for (int k = lane; k < ldv; k += 64)
-            st1<TO>(dv + k, (k < V) ? g * (expf(vr[k] - lse_v) - (k == lab ? 1.f : 0.f)) : 0.f);
-        for (int j = lane; j < Tn; j += 64) st1<TO>(dp + j, 0.f);
-        if (lane == 0) dsw[row] = (1.0f - prob >= 1e-6f) ? g * prob : 0.f;
-    } else {
-        const float lse_p = row_lse[row * 2 + 1];
-        const float* pr = ptr + row * Tn;
-        const int js = (int)(lab - V);
-        for (int k = lane; k < ldv; k += 64) st1<TO>(dv + k, 0.f);
-        for (int j = lane; j < Tn; j += 64)
-            st1<TO>(dp + j, (j < i) ? g * (expf(pr[j] - lse_p) - (j == js ? 1.f : 0.f)) : 0.f);
-        if (lane == 0) dsw[row] = (prob >= 1e-6f) ? -g * (1.0f - prob) : 0.f;
-    }
-}
-
-// ---- extended objective (include/plank_hip.h pa_loss_ext): label smoothing over the ALLOWED classes of a row
-// (the V vocabulary entries and the i pointers j < i - the filled pointers get no mass), a weight per drawing or per token, and the
-// plain -log p(label) per token next to the objective.  Same shape as the pair above: one wave per row, NLL_ROWS rows per block, the
-// slot arrays when V <= 1024 && T <= 256.  No load sits under a range test here: row, label, weight and logit indices are clamped, every
-// load is issued, and what is out of range is discarded in the arithmetic.  With eps == 0 and no weight every operation that reaches an
-// output is the one the kernels above do, so the outputs are theirs bit for bit (tests/test_loss_ext_gpu.py).
-__global__ __launch_bounds__(256) void mixture_nll_ext_fwd_kernel(float* stats, float* row_lse, const float* vocab, int ldv,
-                                                                  const float* ptr, const float* sw, const int64_t* label,
-                                                                  int B, int Tn, int V, int pad, float eps, const float* weight,
-                                                                  int per_token, float* token_nll, float* ext_stats) {
-    __shared__ float red[4][4];
+                                                              int B, int Tn, int V, int pad, NllExt x) {
+    static_assert(FIXED || !EXT, "the extended objective exists in the stats8 form only");
+    constexpr int NS = EXT ? 4 : 3;                              // statistics per block
+    __shared__ float red[4][NS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t n = (int64_t)B * Tn;
     float a_obj = 0.f, a_cnt = 0.f, a_hit = 0.f, a_nll = 0.f;
@@ -871,13 +768,13 @@ __global__ __launch_bounds__(256) void mixture_nll_ext_fwd_kernel(float* stats, 
         const float* vr = vocab + row * ldv;
         const float* pr = ptr + row * Tn;
         const int64_t lab = label[row];
-        const float w = weight ? weight[per_token ? row : row / Tn] : 1.f;
+        const float w = (EXT && x.weight) ? x.weight[x.per_token ? row : row / Tn] : 1.f;
         const int kl = (int)(lab < 0 ? 0 : (lab < V ? lab : V - 1));
         const int64_t jl64 = lab - V;
         const int jl = (int)(jl64 < 0 ? 0 : (jl64 < Tn ? jl64 : Tn - 1));
         const float x_lab = vr[kl], z_lab = pr[jl], s_row = sw[row];
         RowStat sv{-INFINITY, 0.f, 0x7fffffff}, sp{-INFINITY, 0.f, 0x7fffffff};
-        float sum_x = 0.f, sum_z = 0.f;                          // sum_k x_k and sum_{j<i} z_j of this lane's entries (smoothing)
+        float sum_x = 0.f, sum_z = 0.f;                          // sum_k x_k and sum_{j<i} z_j of this lane's entries (smoothing; dead unless EXT)
         if (V <= 64 * NLL_VSLOTS && Tn <= 64 * NLL_PSLOTS) {
             float xv[NLL_VSLOTS], xp[NLL_PSLOTS];
 #pragma unroll
@@ -892,7 +789,7 @@ __global__ __launch_bounds__(256) void mixture_nll_ext_fwd_kernel(float* stats, 
                 if (j < Tn) { online(sp, (j >= i) ? 1e-6f : xp[q], j); sum_z += (j >= i) ? 0.f : xp[q]; }
             }
         } else {
-            for (int k = lane; k < V; k += 64) { const float x = vr[k]; online(sv, x, k); sum_x += x; }
+            for (int k = lane; k < V; k += 64) { const float xk = vr[k]; online(sv, xk, k); sum_x += xk; }
             for (int j = lane; j < Tn; j += 64) { const float z = pr[j]; online(sp, (j >= i) ? 1e-6f : z, j); sum_z += (j >= i) ? 0.f : z; }
         }
         sv = wave_merge(sv);
@@ -901,7 +798,7 @@ __global__ __launch_bounds__(256) void mixture_nll_ext_fwd_kernel(float* stats, 
         const float prob = 1.0f / (1.0f + expf(-s_row));
         const float lv = logf(fmaxf(1.0f - prob, 1e-6f)), lp = logf(fmaxf(prob, 1e-6f));
         float smooth = 0.f;
-        if (eps > 0.f) {                                         // (eps == 0 never forms it: 0 * inf would poison a row that is fine without)
+        if (EXT && x.eps > 0.f) {                                // (eps == 0 never forms it: 0 * inf would poison a row that is fine without)
             sum_x = wave_sum(sum_x);
             sum_z = wave_sum(sum_z);
             const float Vf = (float)V, If = (float)i;
@@ -914,44 +811,52 @@ __global__ __launch_bounds__(256) void mixture_nll_ext_fwd_kernel(float* stats, 
         else { const int j = (int)(lab - V); logp = ((j >= i) ? 1e-6f : z_lab) - lse_p + lp; }
         if (lane == 0 && in_rows) {
             row_lse[row * 2] = lse_v; row_lse[row * 2 + 1] = lse_p;
-            if (token_nll) token_nll[row] = valid ? -logp : 0.f;
+            if (EXT && x.token_nll) x.token_nll[row] = valid ? -logp : 0.f;
             if (valid) {
                 const float best_v = sv.m - lse_v + lv, best_p = sp.m - lse_p + lp;
                 const int64_t pred = (best_p > best_v) ? (int64_t)V + sp.arg : (int64_t)sv.arg;
-                const float ell = (eps > 0.f) ? (1.0f - eps) * -logp + eps * smooth : -logp;
-                if (!weight) a_obj += ell;
+                const float ell = (EXT && x.eps > 0.f) ? (1.0f - x.eps) * -logp + x.eps * smooth : -logp;
+                if (!EXT || !x.weight) a_obj += ell;
                 else if (w != 0.f) a_obj += w * ell;             // (a zero weight masks the row out whatever its logits hold)
-                a_nll -= logp; a_cnt += 1.0f;
+                a_nll -= logp; a_cnt += 1.0f;                    // (a_nll: the fourth statistic, dead unless EXT)
                 if (pred == lab) a_hit += 1.0f;
             }
         }
     }
-    if (lane == 0) { red[wave][0] = a_obj; red[wave][1] = a_cnt; red[wave][2] = a_hit; red[wave][3] = a_nll; }
+    if (lane == 0) { red[wave][0] = a_obj; red[wave][1] = a_cnt; red[wave][2] = a_hit; if (EXT) red[wave][3] = a_nll; }
     __syncthreads();
-    if (threadIdx.x < 4) {
+    if (threadIdx.x < NS) {
         const float v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-        const bool fixed = (threadIdx.x == 0 || threadIdx.x == 3) && fabsf(v) < 4294967296.f;          // (false for a NaN)
-        // objective: stats[6..7], fall-back stats[0]; plain sum: ext_stats[0..1], fall-back ext_stats[2] (the finish turns it into the mean)
-        float* word = threadIdx.x == 0 ? stats + 6 : ext_stats;
-        float* slot = threadIdx.x == 3 ? ext_stats + 2 : stats + threadIdx.x;
+        const bool fixed = FIXED && (threadIdx.x == 0 || threadIdx.x == 3) && fabsf(v) < 4294967296.f;      // (false for a NaN)
+        // objective: stats[6..7], fall-back stats[0]; plain sum (EXT): ext_stats[0..1], fall-back ext_stats[2] (the finish makes it the mean)
+        float* word = (EXT && threadIdx.x == 3) ? x.ext_stats : stats + 6;
+        float* slot = (EXT && threadIdx.x == 3) ? x.ext_stats + 2 : stats + threadIdx.x;
         if (fixed) {
             if (v != 0.f) atomicAdd(reinterpret_cast<unsigned long long*>(word), (unsigned long long)__float2ll_rn(v * NLL_FIXED_ONE));
         } else if (v != 0.f) atomicAdd(slot, v);
     }
 }
-// mixture_nll_finish_kernel, and the plain mean ext_stats[2] = (plain NLL sum) / count behind it in the same one-wave launch.
-__global__ void mixture_nll_ext_finish_kernel(float* stats, float* ext_stats) {
+// stats8 form: loss = nll / count, accuracy = hits / (count + 1e-10) (reference models.py:226-231) and the upstream gradient's
+// default 1.0 in ONE one-wave launch behind the forward kernel - what five tiny torch launches and a memset did on the step's serial
+// chain before; with `ext_stats` (the extended objective) the plain mean ext_stats[2] = (plain NLL sum) / count
+// too.  Two in-kernel forms were measured first and lost: the last block (ticket) finishing the sums behind __threadfence() took the
+// forward kernel from 11.7 to 38.6 us, and with returning device-scope atomics instead of the fence to 33.8 us (512 blocks x 4
+// returning atomics on four words) - more than the launches they replaced.
+__global__ void mixture_nll_finish_kernel(float* stats, float* ext_stats) {
     if (threadIdx.x == 0) {
-        const long long q = *reinterpret_cast<const long long*>(stats + 6);
+        const long long q = *reinterpret_cast<const long long*>(stats + 6);               // the fixed-point NLL sum (8-byte aligned)
         const float s0 = stats[0] + (float)((double)q * (1.0 / (double)NLL_FIXED_ONE)), s1 = stats[1], s2 = stats[2];
         stats[0] = s0;
         stats[4] = s0 / s1; stats[5] = s2 / (s1 + 1e-10f); stats[3] = 1.0f;
-        const long long qn = *reinterpret_cast<const long long*>(ext_stats);
-        const float n0 = ext_stats[2] + (float)((double)qn * (1.0 / (double)NLL_FIXED_ONE));
-        ext_stats[2] = n0 / s1;
+        if (ext_stats) {
+            const long long qn = *reinterpret_cast<const long long*>(ext_stats);
+            const float n0 = ext_stats[2] + (float)((double)qn * (1.0 / (double)NLL_FIXED_ONE));
+            ext_stats[2] = n0 / s1;
+        }
     }
 }
 
+// The one backward kernel (pa_mixture_nll_bwd, pa_mixture_nll_bwd_up: eps 0 and no weight; pa_mixture_nll_bwd_ext).
 template <typename TO>
 __global__ __launch_bounds__(256) void mixture_nll_ext_bwd_kernel(TO* dvocab, TO* dptr, float* dsw, const float* stats,
                                                                   const float* row_lse, const float* vocab, int ldv,
@@ -973,7 +878,7 @@ __global__ __launch_bounds__(256) void mixture_nll_ext_bwd_kernel(TO* dvocab, TO
         if (lane == 0) dsw[row] = 0.f;
         return;
     }
-    float g = gscale * (upstream ? *upstream : stats[3]) / stats[1];
+    float g = gscale * (upstream ? *upstream : stats[3]) / stats[1];      // upstream d(loss), device resident (stats[3] unless given)
     if (weight) g *= w;
     const float prob = 1.0f / (1.0f + expf(-s_row));
     const float* vr = vocab + row * ldv;
@@ -997,7 +902,7 @@ __global__ __launch_bounds__(256) void mixture_nll_ext_bwd_kernel(TO* dvocab, TO
             const float dlv = (1.0f - prob >= 1e-6f) ? -prob : 0.f, dlp = (prob >= 1e-6f) ? 1.0f - prob : 0.f;
             dsw[row] = g * (-om * (in_v ? dlv : dlp) - ec * (Vf * dlv + If * dlp));
         }
-    } else if (lab < V) {                                        // eps == 0: mixture_nll_bwd_kernel's two branches, only the label's part is read
+    } else if (lab < V) {                                        // eps == 0: only the label's part is read
         for (int k = lane; k < ldv; k += 64)
             st1<TO>(dv + k, (k < V) ? g * (expf(vr[min(k, V - 1)] - lse_v) - (k == lab ? 1.f : 0.f)) : 0.f);
         for (int j = lane; j < Tn; j += 64) st1<TO>(dp + j, 0.f);
@@ -1012,39 +917,6 @@ __global__ __launch_bounds__(256) void mixture_nll_ext_bwd_kernel(TO* dvocab, TO
 }
 
 // ================================================================================ Adam / cast
-__global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, bf16* pb, int64_t n,
-                                                   float step_size, float b1, float b2, float eps, float inv_sqrt_bc2,
-                                                   float gscale) {
-    const int64_t n4 = n >> 2;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
-        f32x4 pp = *reinterpret_cast<f32x4*>(p + e * 4);
-        f32x4 gg = *reinterpret_cast<const f32x4*>(g + e * 4);
-        f32x4 mm = *reinterpret_cast<f32x4*>(m + e * 4);
-        f32x4 vv = *reinterpret_cast<f32x4*>(v + e * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float gj = gg[j] * gscale;
-            mm[j] = b1 * mm[j] + (1.f - b1) * gj;
-            vv[j] = b2 * vv[j] + (1.f - b2) * gj * gj;
-            pp[j] -= step_size * mm[j] / (sqrtf(vv[j]) * inv_sqrt_bc2 + eps);
-        }
-        *reinterpret_cast<f32x4*>(p + e * 4) = pp;
-        *reinterpret_cast<f32x4*>(m + e * 4) = mm;
-        *reinterpret_cast<f32x4*>(v + e * 4) = vv;
-        if (pb) st4<bf16>(pb + e * 4, pp);
-    }
-    // tail (n % 4)
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t e = (n4 << 2) + threadIdx.x;
-        const float gj = g[e] * gscale;
-        const float mj = b1 * m[e] + (1.f - b1) * gj;
-        const float vj = b2 * v[e] + (1.f - b2) * gj * gj;
-        m[e] = mj; v[e] = vj;
-        p[e] -= step_size * mj / (sqrtf(vj) * inv_sqrt_bc2 + eps);
-        if (pb) pb[e] = (bf16)p[e];
-    }
-}
-
 // ---- gradient guard (include/plank_hip.h pa_grad_guard): the sum of squares of the flat gradient as one partial per block.
 // No atomics: block b always adds the same elements in the same order (4 lane chains per thread, xor butterfly, 4 wave sums),
 // so two calls on the same buffer give the same bits.  NaN / inf entries propagate into the partial.
@@ -1113,50 +985,10 @@ __global__ void grad_guard_init_kernel(pa_grad_guard_ctl* ctl, int step0) {
     for (int i = 0; i < 7; ++i) ctl->pad_[i] = 0;
 }
 
-// adam_kernel with the step's scalars read from the guard's control block: a step the guard refused returns before any store.
-__global__ __launch_bounds__(256) void adam_guarded_kernel(float* p, const float* g, float* m, float* v, bf16* pb, int64_t n,
-                                                           float b1, float b2, float eps, float gscale, float clip,
-                                                           const pa_grad_guard_ctl* ctl) {
-    if (ctl->apply == 0) return;
-    const float step_size = ctl->step_size, inv_sqrt_bc2 = ctl->inv_sqrt_bc2, coef = ctl->coef;
-    const float omb1 = 1.f - b1, omb2 = 1.f - b2;
-    const int64_t n4 = n >> 2;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
-        f32x4 pp = *reinterpret_cast<f32x4*>(p + e * 4);
-        f32x4 gg = *reinterpret_cast<const f32x4*>(g + e * 4);
-        f32x4 mm = *reinterpret_cast<f32x4*>(m + e * 4);
-        f32x4 vv = *reinterpret_cast<f32x4*>(v + e * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gj = gg[j] * gscale * coef;
-            gj = gj > clip ? clip : (gj < -clip ? -clip : gj);          // (clip = +inf when off; a NaN stays a NaN)
-            // The fused multiply-adds are spelled out in the forms the compiler gives adam_kernel's expressions (which product
-            // of a sum goes into the fma is its choice, and it chose differently here when left to it): with coef == 1 and no
-            // clamp the moments then equal pa_adam_step's bit for bit - tests/test_grad_guard_gpu.py holds the two together.
-            mm[j] = __builtin_fmaf(omb1, gj, b1 * mm[j]);
-            vv[j] = __builtin_fmaf(b2, vv[j], (omb2 * gj) * gj);
-            pp[j] -= step_size * mm[j] / __builtin_fmaf(sqrtf(vv[j]), inv_sqrt_bc2, eps);
-        }
-        *reinterpret_cast<f32x4*>(p + e * 4) = pp;
-        *reinterpret_cast<f32x4*>(m + e * 4) = mm;
-        *reinterpret_cast<f32x4*>(v + e * 4) = vv;
-        if (pb) st4<bf16>(pb + e * 4, pp);
-    }
-    // tail (n % 4)
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t e = (n4 << 2) + threadIdx.x;
-        float gj = g[e] * gscale * coef;
-        gj = gj > clip ? clip : (gj < -clip ? -clip : gj);
-        const float mj = __builtin_fmaf(b1, m[e], omb1 * gj);            // (adam_kernel's tail fuses the OTHER product of m)
-        const float vj = __builtin_fmaf(b2, v[e], (omb2 * gj) * gj);
-        m[e] = mj; v[e] = vj;
-        p[e] -= step_size * mj / __builtin_fmaf(sqrtf(vj), inv_sqrt_bc2, eps);
-        if (pb) pb[e] = (bf16)p[e];
-    }
-}
-
-// ---- extended Adam (include/plank_hip.h pa_adam_step_ext): adam_guarded_kernel's element rule with decoupled weight decay
-// before the update and an exponential moving average of the new weights after it, all in the one streaming pass.
+// ---- Adam (include/plank_hip.h pa_adam_step, pa_adam_step_guarded, pa_adam_step_ext): the one Adam kernel.  The element rule,
+// optionally with the step's scalars and the apply flag read from the guard's control block (a step the guard refused returns
+// before any store), decoupled weight decay before the update and an exponential moving average of the new weights after it, all
+// in the one streaming pass.
 // A product the compiler may not contract into the subtraction that follows it: the decayed weight is rounded to f32 before the
 // Adam update, as torch.optim.AdamW's p.mul_(1 - lr * wd) rounds it.
 __device__ __forceinline__ float mul_rounded(float a, float b) {
@@ -1170,6 +1002,10 @@ struct adam_ext_scalars {
 };
 
 // DECAY 0: none, 1: every element, 2: the elements whose bit is set in `bits`.  `ctl` (guarded or not) is uniform over the launch.
+// pa_adam_step and pa_adam_step_guarded are <0, false>: coef = 1 and clip = +inf change no bit (a NaN stays a NaN).
+// The fused multiply-adds of the moments and of the denominator are spelled out, because which product of a sum goes into the fma
+// is otherwise the compiler's choice and changes the last bit.  The forms - the main loop fuses (1 - b1) g into b1 m, the tail
+// b1 m into (1 - b1) g - are the ones every build so far has had: tests/test_rowops_family_bits_gpu.py holds the results to them.
 template <int DECAY, bool EMA>
 __global__ __launch_bounds__(256) void adam_ext_kernel(float* p, const float* g, float* m, float* v, bf16* pb, float* ema,
                                                        const uint8_t* bits, int64_t n, adam_ext_scalars s,
@@ -1203,8 +1039,8 @@ __global__ __launch_bounds__(256) void adam_ext_kernel(float* p, const float* g,
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float gj = gg[j] * gscale * coef;
-            gj = gj > clip ? clip : (gj < -clip ? -clip : gj);
-            mm[j] = __builtin_fmaf(omb1, gj, b1 * mm[j]);                  // (adam_guarded_kernel's forms, main loop and tail)
+            gj = gj > clip ? clip : (gj < -clip ? -clip : gj);          // (clip = +inf when off)
+            mm[j] = __builtin_fmaf(omb1, gj, b1 * mm[j]);
             vv[j] = __builtin_fmaf(b2, vv[j], (omb2 * gj) * gj);
             if (DECAY == 1) pp[j] = mul_rounded(pp[j], f);
             if (DECAY == 2) pp[j] = ((nib >> j) & 1u) ? mul_rounded(pp[j], f) : pp[j];
@@ -1650,87 +1486,81 @@ extern "C" int pa_switch_bwd(void* dh, int32_t accumulate, float* dw, float* db,
     return 0;
 }
 
-extern "C" int pa_mixture_nll_fwd(float* stats, float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
-                                  const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
-                                  void* stream) {
-    if (!stats || !row_lse || !vocab || !ptr || !sw || !label || B <= 0 || T <= 0 || V <= 0 || ldv < V) return PA_EINVAL;
-    const int grid = (int)(((int64_t)B * T + NLL_ROWS - 1) / NLL_ROWS);
-    PA_LAUNCH(mixture_nll_fwd_kernel<false>, dim3(grid), dim3(256), 0, ST(stream), stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad);
-    return 0;
-}
-extern "C" int pa_mixture_nll_fwd_fin(float* stats8, float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
-                                      const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
-                                      void* stream) {
-    if (!stats8 || !row_lse || !vocab || !ptr || !sw || !label || B <= 0 || T <= 0 || V <= 0 || ldv < V) return PA_EINVAL;
-    if (reinterpret_cast<uintptr_t>(stats8) & 7) return PA_EINVAL;                         // stats8[6..7] is one 64-bit word
-    const int grid = (int)(((int64_t)B * T + NLL_ROWS - 1) / NLL_ROWS);
-    if (hipMemsetAsync(stats8, 0, 8 * sizeof(float), ST(stream)) != hipSuccess) return PA_EINVAL;      // sums, ticket (and the rest)
-    PA_LAUNCH(mixture_nll_fwd_kernel<true>, dim3(grid), dim3(256), 0, ST(stream), stats8, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad);
-    PA_LAUNCH(mixture_nll_finish_kernel, dim3(1), dim3(64), 0, ST(stream), stats8);
-    return 0;
-}
-
-extern "C" int pa_mixture_nll_bwd_up(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, const float* stats,
-                                  const float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
-                                  const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
-                                  float gscale, const float* upstream, void* stream) {
-    if (!dvocab || !dptr || !dsw || !stats || !row_lse || !vocab || !ptr || !sw || !label) return PA_EINVAL;
-    if (B <= 0 || T <= 0 || V <= 0 || ldv < V) return PA_EINVAL;
-    const int grid = (int)(((int64_t)B * T + 3) / 4);
-    if (out_dtype == PA_BF16) PA_LAUNCH(mixture_nll_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, ST(stream), (bf16*)dvocab, (bf16*)dptr, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream);
-    else PA_LAUNCH(mixture_nll_bwd_kernel<float>, dim3(grid), dim3(256), 0, ST(stream), (float*)dvocab, (float*)dptr, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream);
-    return 0;
-}
-extern "C" int pa_mixture_nll_bwd(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, const float* stats,
-                                  const float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
-                                  const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
-                                  float gscale, void* stream) {
-    return pa_mixture_nll_bwd_up(dvocab, dptr, out_dtype, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, nullptr, stream);
-}
-
-// ---- extended objective (pa_loss_ext): one check of the block for both entries, before anything is enqueued
-extern "C" int64_t pa_loss_ext_bytes(void) { return (int64_t)sizeof(pa_loss_ext); }
+// ---- mixture NLL: five entries, one launcher per direction (model.h declares them for runtime.hip).  `e` NULL: the plain objective.
 static bool loss_ext_ok(const pa_loss_ext* e) {
     if (!e || !(e->smoothing >= 0.f && e->smoothing < 1.f)) return false;                  // (false for a NaN)
     if (e->weight_per_token != 0 && e->weight_per_token != 1) return false;
     return e->ext_stats && !(reinterpret_cast<uintptr_t>(e->ext_stats) & 7);               // ext_stats[0..1] is one 64-bit word
 }
+// stats8 form unless `plain_stats` (pa_mixture_nll_fwd: three float sums into the caller's zeroed stats, no finish).
+int nll_fwd_launch(float* stats, float* row_lse, const float* vocab, int32_t ldv, const float* ptr, const float* sw,
+                   const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad, const pa_loss_ext* e, bool plain_stats,
+                   void* stream) {
+    if (!stats || !row_lse || !vocab || !ptr || !sw || !label || B <= 0 || T <= 0 || V <= 0 || ldv < V) return PA_EINVAL;
+    if (e && (plain_stats || !loss_ext_ok(e))) return PA_EINVAL;
+    if (!plain_stats && (reinterpret_cast<uintptr_t>(stats) & 7)) return PA_EINVAL;        // stats8[6..7] is one 64-bit word
+    const dim3 grid((unsigned)(((int64_t)B * T + NLL_ROWS - 1) / NLL_ROWS));
+    const NllExt x = e ? NllExt{e->smoothing, e->weight, e->weight_per_token, e->token_nll, e->ext_stats} : NllExt{};
+#define PA_NLL_FWD(FIXED, EXT)                                                                                                  \
+    PA_LAUNCH((mixture_nll_fwd_kernel<FIXED, EXT>), grid, dim3(256), 0, ST(stream), stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, x)
+    if (plain_stats) { PA_NLL_FWD(false, false); return 0; }
+    if (hipMemsetAsync(stats, 0, 8 * sizeof(float), ST(stream)) != hipSuccess) return PA_EINVAL;        // sums, fixed-point word (and the rest)
+    if (e && hipMemsetAsync(e->ext_stats, 0, 4 * sizeof(float), ST(stream)) != hipSuccess) return PA_EINVAL;
+    if (e) PA_NLL_FWD(true, true); else PA_NLL_FWD(true, false);
+#undef PA_NLL_FWD
+    PA_LAUNCH(mixture_nll_finish_kernel, dim3(1), dim3(64), 0, ST(stream), stats, e ? e->ext_stats : (float*)nullptr);
+    return 0;
+}
+int nll_bwd_launch(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, const float* stats, const float* row_lse,
+                   const float* vocab, int32_t ldv, const float* ptr, const float* sw, const int64_t* label, int32_t B, int32_t T,
+                   int32_t V, int32_t pad, float gscale, const float* upstream, const pa_loss_ext* e, void* stream) {
+    if (!dvocab || !dptr || !dsw || !stats || !row_lse || !vocab || !ptr || !sw || !label) return PA_EINVAL;
+    if (B <= 0 || T <= 0 || V <= 0 || ldv < V || (e && !loss_ext_ok(e))) return PA_EINVAL;
+    const dim3 grid((unsigned)(((int64_t)B * T + 3) / 4));
+    const float eps = e ? e->smoothing : 0.f;
+    const float* weight = e ? e->weight : nullptr;
+    const int per_token = e ? e->weight_per_token : 0;
+    if (out_dtype == PA_BF16) PA_LAUNCH(mixture_nll_ext_bwd_kernel<bf16>, grid, dim3(256), 0, ST(stream), (bf16*)dvocab, (bf16*)dptr, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream, eps, weight, per_token);
+    else PA_LAUNCH(mixture_nll_ext_bwd_kernel<float>, grid, dim3(256), 0, ST(stream), (float*)dvocab, (float*)dptr, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream, eps, weight, per_token);
+    return 0;
+}
+
+extern "C" int pa_mixture_nll_fwd(float* stats, float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
+                                  const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
+                                  void* stream) {
+    return nll_fwd_launch(stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, nullptr, true, stream);
+}
+extern "C" int pa_mixture_nll_fwd_fin(float* stats8, float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
+                                      const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
+                                      void* stream) {
+    return nll_fwd_launch(stats8, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, nullptr, false, stream);
+}
+extern "C" int pa_mixture_nll_bwd_up(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, const float* stats,
+                                  const float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
+                                  const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
+                                  float gscale, const float* upstream, void* stream) {
+    return nll_bwd_launch(dvocab, dptr, out_dtype, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream, nullptr, stream);
+}
+extern "C" int pa_mixture_nll_bwd(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, const float* stats,
+                                  const float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
+                                  const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
+                                  float gscale, void* stream) {
+    return nll_bwd_launch(dvocab, dptr, out_dtype, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, nullptr, nullptr, stream);
+}
+// (the _ext entries reject a NULL block: to the launchers it means the plain objective)
+extern "C" int64_t pa_loss_ext_bytes(void) { return (int64_t)sizeof(pa_loss_ext); }
 extern "C" int pa_mixture_nll_fwd_ext(float* stats8, float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
                                       const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
                                       const pa_loss_ext* e, void* stream) {
-    if (!stats8 || !row_lse || !vocab || !ptr || !sw || !label || B <= 0 || T <= 0 || V <= 0 || ldv < V) return PA_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(stats8) & 7) || !loss_ext_ok(e)) return PA_EINVAL;
-    const int grid = (int)(((int64_t)B * T + NLL_ROWS - 1) / NLL_ROWS);
-    if (hipMemsetAsync(stats8, 0, 8 * sizeof(float), ST(stream)) != hipSuccess) return PA_EINVAL;
-    if (hipMemsetAsync(e->ext_stats, 0, 4 * sizeof(float), ST(stream)) != hipSuccess) return PA_EINVAL;
-    PA_LAUNCH(mixture_nll_ext_fwd_kernel, dim3(grid), dim3(256), 0, ST(stream), stats8, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad,
-              e->smoothing, e->weight, e->weight_per_token, e->token_nll, e->ext_stats);
-    PA_LAUNCH(mixture_nll_ext_finish_kernel, dim3(1), dim3(64), 0, ST(stream), stats8, e->ext_stats);
-    return 0;
+    if (!e) return PA_EINVAL;
+    return nll_fwd_launch(stats8, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, e, false, stream);
 }
 extern "C" int pa_mixture_nll_bwd_ext(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, const float* stats,
                                       const float* row_lse, const float* vocab, int32_t ldv, const float* ptr,
                                       const float* sw, const int64_t* label, int32_t B, int32_t T, int32_t V, int32_t pad,
                                       float gscale, const float* upstream, const pa_loss_ext* e, void* stream) {
-    if (!dvocab || !dptr || !dsw || !stats || !row_lse || !vocab || !ptr || !sw || !label) return PA_EINVAL;
-    if (B <= 0 || T <= 0 || V <= 0 || ldv < V || !loss_ext_ok(e)) return PA_EINVAL;
-    const int grid = (int)(((int64_t)B * T + 3) / 4);
-    if (out_dtype == PA_BF16) PA_LAUNCH(mixture_nll_ext_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, ST(stream), (bf16*)dvocab, (bf16*)dptr, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream, e->smoothing, e->weight, e->weight_per_token);
-    else PA_LAUNCH(mixture_nll_ext_bwd_kernel<float>, dim3(grid), dim3(256), 0, ST(stream), (float*)dvocab, (float*)dptr, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream, e->smoothing, e->weight, e->weight_per_token);
-    return 0;
-}
-
-extern "C" int pa_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float b1,
-                            float b2, float eps, int32_t step, float gscale, void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || step < 1) return PA_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-         reinterpret_cast<uintptr_t>(v)) & 15) return PA_EALIGN;
-    const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    PA_LAUNCH(adam_kernel, dim3(grid_for(n >> 2, 256, 2048)), dim3(256), 0, ST(stream), p, g, m, v, (bf16*)p_bf16, n,
-                       step_size, b1, b2, eps, inv_sqrt_bc2, gscale);
-    return 0;
+    if (!e) return PA_EINVAL;
+    return nll_bwd_launch(dvocab, dptr, out_dtype, dsw, stats, row_lse, vocab, ldv, ptr, sw, label, B, T, V, pad, gscale, upstream, e, stream);
 }
 
 // ---- gradient guard: workspace = PA_GRAD_GUARD_PARTIALS f32 partials, then the control block
@@ -1767,57 +1597,76 @@ extern "C" int pa_grad_guard(const float* g, int64_t n, float gscale, float max_
     return 0;
 }
 
-extern "C" int pa_adam_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float b1, float b2,
-                                    float eps, float gscale, float clip_value, const pa_grad_guard_ctl* ctl, void* stream) {
-    if (!p || !g || !m || !v || !ctl || n <= 0 || !(clip_value >= 0.f)) return PA_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-         reinterpret_cast<uintptr_t>(v)) & 15) return PA_EALIGN;
-    if (reinterpret_cast<uintptr_t>(ctl) & 3) return PA_EALIGN;
-    PA_LAUNCH(adam_guarded_kernel, dim3(grid_for(n >> 2, 256, 2048)), dim3(256), 0, ST(stream), p, g, m, v, (bf16*)p_bf16, n,
-              b1, b2, eps, gscale, clip_value > 0.f ? clip_value : __builtin_inff(), ctl);
-    return 0;
-}
-
+// ---- Adam: three entries, one launch.  Each entry checks its own arguments and hands a pa_adam_ext_args on.
 static_assert(sizeof(pa_adam_ext_args) == 112, "pa_adam_ext_args is 112 bytes (plankassembly_amd/_lib.py mirrors it)");
 extern "C" int64_t pa_adam_ext_args_bytes(void) { return (int64_t)sizeof(pa_adam_ext_args); }
 
-extern "C" int pa_adam_step_ext(const pa_adam_ext_args* a, void* stream) {
-    if (!a || !a->p || !a->g || !a->m || !a->v || a->n <= 0 || !(a->clip_value >= 0.f)) return PA_EINVAL;
-    if (!(a->weight_decay >= 0.f && a->weight_decay < __builtin_inff())) return PA_EINVAL;
-    if (!(a->ema_decay >= 0.f && a->ema_decay < 1.f)) return PA_EINVAL;
-    if (!a->ctl && a->step < 1) return PA_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(a->p) | reinterpret_cast<uintptr_t>(a->g) | reinterpret_cast<uintptr_t>(a->m) |
-         reinterpret_cast<uintptr_t>(a->v) | reinterpret_cast<uintptr_t>(a->ema)) & 15) return PA_EALIGN;
-    if (reinterpret_cast<uintptr_t>(a->ctl) & 3) return PA_EALIGN;
+static int adam_check(const pa_adam_ext_args& a) {
+    if (!a.p || !a.g || !a.m || !a.v || a.n <= 0) return PA_EINVAL;
+    if (!a.ctl && a.step < 1) return PA_EINVAL;
+    if (!(a.clip_value >= 0.f)) return PA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(a.p) | reinterpret_cast<uintptr_t>(a.g) | reinterpret_cast<uintptr_t>(a.m) |
+         reinterpret_cast<uintptr_t>(a.v) | reinterpret_cast<uintptr_t>(a.ema)) & 15) return PA_EALIGN;
+    if (reinterpret_cast<uintptr_t>(a.ctl) & 3) return PA_EALIGN;
+    return 0;
+}
+
+static int adam_launch(const pa_adam_ext_args& a, void* stream) {
     adam_ext_scalars s = {};
-    s.b1 = a->b1; s.b2 = a->b2; s.eps = a->eps; s.gscale = a->gscale;
-    s.clip = a->clip_value > 0.f ? a->clip_value : __builtin_inff();
-    s.decay_f = (float)(1.0 - (double)a->lr * (double)a->weight_decay);
-    s.ema_decay = a->ema_decay; s.ema_warmup = a->ema_warmup != 0;
-    if (!a->ctl) {                                     // unguarded: the step's scalars on the host, in double, rounded once
-        const double t = (double)a->step;
-        const double bc1 = 1.0 - pow((double)a->b1, t), bc2 = 1.0 - pow((double)a->b2, t);
-        s.step_size = (float)((double)a->lr / bc1);
+    s.b1 = a.b1; s.b2 = a.b2; s.eps = a.eps; s.gscale = a.gscale;
+    s.clip = a.clip_value > 0.f ? a.clip_value : __builtin_inff();
+    s.decay_f = (float)(1.0 - (double)a.lr * (double)a.weight_decay);
+    s.ema_decay = a.ema_decay; s.ema_warmup = a.ema_warmup != 0;
+    if (!a.ctl) {                                      // unguarded: the step's scalars on the host, in double, rounded once
+        const double t = (double)a.step;
+        const double bc1 = 1.0 - pow((double)a.b1, t), bc2 = 1.0 - pow((double)a.b2, t);
+        s.step_size = (float)((double)a.lr / bc1);
         s.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-        double d = (double)a->ema_decay;
+        double d = (double)a.ema_decay;
         if (s.ema_warmup) {
             const double w = (1.0 + t) / (10.0 + t);
             d = w < d ? w : d;
         }
         s.one_minus_d = (float)(1.0 - d);
     }
-    const int decay = a->weight_decay > 0.f ? (a->decay_bits ? 2 : 1) : 0;
-    const dim3 grid(grid_for(a->n >> 2, 256, 2048));
+    const int decay = a.weight_decay > 0.f ? (a.decay_bits ? 2 : 1) : 0;
+    const dim3 grid(grid_for(a.n >> 2, 256, 2048));
 #define PA_ADAM_EXT(D, E)                                                                                                      \
-    PA_LAUNCH((adam_ext_kernel<D, E>), grid, dim3(256), 0, ST(stream), a->p, a->g, a->m, a->v, (bf16*)a->p_bf16, a->ema,        \
-              a->decay_bits, a->n, s, a->ctl)
-    if (a->ema) {
+    PA_LAUNCH((adam_ext_kernel<D, E>), grid, dim3(256), 0, ST(stream), a.p, a.g, a.m, a.v, (bf16*)a.p_bf16, a.ema,              \
+              a.decay_bits, a.n, s, a.ctl)
+    if (a.ema) {
         if (decay == 2) PA_ADAM_EXT(2, true); else if (decay == 1) PA_ADAM_EXT(1, true); else PA_ADAM_EXT(0, true);
     } else {
         if (decay == 2) PA_ADAM_EXT(2, false); else if (decay == 1) PA_ADAM_EXT(1, false); else PA_ADAM_EXT(0, false);
     }
 #undef PA_ADAM_EXT
     return 0;
+}
+
+extern "C" int pa_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float b1,
+                            float b2, float eps, int32_t step, float gscale, void* stream) {
+    pa_adam_ext_args a = {};
+    a.p = p; a.g = g; a.m = m; a.v = v; a.p_bf16 = p_bf16; a.n = n;
+    a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps; a.gscale = gscale; a.step = step;
+    if (int rc = adam_check(a)) return rc;
+    return adam_launch(a, stream);
+}
+
+extern "C" int pa_adam_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float b1, float b2,
+                                    float eps, float gscale, float clip_value, const pa_grad_guard_ctl* ctl, void* stream) {
+    if (!ctl) return PA_EINVAL;
+    pa_adam_ext_args a = {};
+    a.p = p; a.g = g; a.m = m; a.v = v; a.p_bf16 = p_bf16; a.n = n;
+    a.b1 = b1; a.b2 = b2; a.eps = eps; a.gscale = gscale; a.clip_value = clip_value; a.ctl = ctl;
+    if (int rc = adam_check(a)) return rc;
+    return adam_launch(a, stream);
+}
+
+extern "C" int pa_adam_step_ext(const pa_adam_ext_args* a, void* stream) {
+    if (!a || !(a->weight_decay >= 0.f && a->weight_decay < __builtin_inff())) return PA_EINVAL;
+    if (!(a->ema_decay >= 0.f && a->ema_decay < 1.f)) return PA_EINVAL;
+    if (int rc = adam_check(*a)) return rc;
+    return adam_launch(*a, stream);
 }
 
 extern "C" int pa_cast(void* dst, int32_t dst_dtype, const void* src, int32_t src_dtype, int64_t n, void* stream) {

@@ -374,10 +374,8 @@ int pa_train_forward_impl(pa_model* m, void* st) {
     RC(pa_switch_fwd(m->sw, m->hid, c.dtype, PF(tl + T_SW_W), PF(tl + T_SW_B), (int64_t)BT, d, st));
     // (one memset inside; loss, accuracy and the upstream 1.0 are written by the kernel's last block: stats is 8 floats)
     m->upstream = nullptr;
-    if (m->loss_on)
-        RC(pa_mixture_nll_fwd_ext(m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw, m->batch.output_label, B, T, c.vocab, c.pad, &m->loss, st));
-    else
-        RC(pa_mixture_nll_fwd_fin(m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw, m->batch.output_label, B, T, c.vocab, c.pad, st));
+    RC(nll_fwd_launch(m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw, m->batch.output_label, B, T, c.vocab, c.pad,
+                      m->loss_on ? &m->loss : nullptr, false, st));
     return 0;
 }
 namespace {
@@ -390,12 +388,8 @@ int bwd_heads(pa_model* m, float gscale, void* st) {
     Ctx k{m, st};
     const int d = c.d_model, B = m->B, T = m->T, BT = B * T, tl = m->tail();
     auto G = [&](int i) { return (float*)m->gr[i]; };
-    if (m->loss_on)
-        RC(pa_mixture_nll_bwd_ext(m->dvlog, m->dplog, c.dtype, m->dsw, m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw,
-                                  m->batch.output_label, B, T, c.vocab, c.pad, gscale, m->upstream, &m->loss, st));
-    else
-        RC(pa_mixture_nll_bwd_up(m->dvlog, m->dplog, c.dtype, m->dsw, m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw,
-                                 m->batch.output_label, B, T, c.vocab, c.pad, gscale, m->upstream, st));
+    RC(nll_bwd_launch(m->dvlog, m->dplog, c.dtype, m->dsw, m->stats, m->row_lse, m->vlog, m->ldv, m->plog, m->sw,
+                      m->batch.output_label, B, T, c.vocab, c.pad, gscale, m->upstream, m->loss_on ? &m->loss : nullptr, st));
     // vocab head
     if (m->plT[tl + T_VOCAB_W])       // padded W^T shadow [d][ldv] (pad columns zero): contraction over the padded width, both k-contiguous
         RC(k.linear_dx(m->dvlog, m->ldv, m->pl[tl + T_VOCAB_W], d, m->gA, d, BT, m->ldv, d, nullptr, 0, nullptr, 0, 1.f,

@@ -6,12 +6,13 @@ Also refreshes the model's bf16 GEMM-operand shadow in the same pass.
 
 Optional gradient guard (``max_grad_norm`` / ``clip_value`` / ``skip_nonfinite``): the global norm of
 the flat gradient buffer, the clip coefficient and the decision to apply or skip the step are computed on the device and
-read by a second Adam kernel, so a guarded step is three launches instead of one and never waits for the GPU.
+read by the Adam kernel, so a guarded step is three launches instead of one and never waits for the GPU.
 
 Optional recipe extensions (``weight_decay`` / ``no_decay`` / ``ema_decay`` / ``ema_warmup``): decoupled
 weight decay (torch.optim.AdamW) and an exponential moving average of the weights, both inside the same streaming pass
-(pa_adam_step_ext), with or without the guard; and :func:`lr_factor`, the learning-rate schedule the trainer applies on the host.
-With none of them set the optimizer makes exactly the calls it made before they existed.
+with or without the guard; and :func:`lr_factor`, the learning-rate schedule the trainer applies on the host.
+
+Every step goes through pa_adam_step_ext (one Adam kernel: include/plank_hip.h); with nothing set it is pa_adam_step's rule bit for bit.
 """
 from __future__ import annotations
 
@@ -125,7 +126,7 @@ class FusedAdam(torch.optim.Optimizer):
         self.base_lr = lr
         self.weight_decay, self.no_decay = float(weight_decay), no_decay
         self.ema_decay, self.ema_warmup = None if ema_decay is None else float(ema_decay), bool(ema_warmup)
-        self.extended = self.weight_decay > 0 or self.ema_decay is not None      # True: step() goes through pa_adam_step_ext
+        self.extended = self.weight_decay > 0 or self.ema_decay is not None      # decay or EMA on
         self._ema = None              # f32 [numel] on the device, a copy of the weights when the first step begins
         self._ema_base = 0            # ema_updates - Adam step count (an EMA that began later than the optimizer: negative)
         self._bits = None             # the uploaded decay bitmask (no_decay "1d"), rebuilt when the flat buffer moves
@@ -150,12 +151,7 @@ class FusedAdam(torch.optim.Optimizer):
             self._v = torch.zeros_like(flat)
         grp = self.param_groups[0]
         shadow = m._shadow if m.compute_dtype == "bf16" else None
-        if self.extended:
-            self._ext_step(flat, g, grp, shadow)
-        elif self.guarded:
-            self._guarded_step(flat, g, grp, shadow)
-        else:
-            self._plain_step(flat, g, grp, shadow)
+        self._adam_step(flat, g, grp, shadow)
         # (the in-place update through the C ABI does not bump torch's version counters; a skipped guarded step rewrote
         # nothing, so a fresh shadow stays fresh either way)
         if shadow is not None:
@@ -164,16 +160,8 @@ class FusedAdam(torch.optim.Optimizer):
             m.invalidate_shadow()
         return loss
 
-    def _plain_step(self, flat, g, grp, shadow):
-        self._step += 1
-        self.model.wait_transposed()             # (the side-stream W^T refresh of the step before reads what this kernel rewrites)
-        L.check(L.lib().pa_adam_step(L.ptr(flat), L.ptr(g), L.ptr(self._m), L.ptr(self._v), L.ptr(shadow),
-                                     C.c_int64(flat.numel()), C.c_float(grp["lr"]), C.c_float(grp["betas"][0]),
-                                     C.c_float(grp["betas"][1]), C.c_float(grp["eps"]), self._step,
-                                     C.c_float(self.grad_scale), L.stream()), "pa_adam_step")
-
     def _enqueue_guard(self, flat, g, grp):
-        """pa_grad_guard into the device control block (made and initialised from self._step on first use); returns its address."""
+        """pa_grad_guard into the device control block (made and initialised from self._step on first use)."""
         lib = L.lib()
         if self._ws is None or self._ws.device != flat.device:
             self._ws = torch.empty(L.GRAD_GUARD_WS_BYTES, dtype=torch.uint8, device=flat.device)
@@ -187,39 +175,30 @@ class FusedAdam(torch.optim.Optimizer):
         L.check(lib.pa_grad_guard(L.ptr(g), C.c_int64(g.numel()), C.c_float(self.grad_scale),
                                   C.c_float(self.max_grad_norm or 0.0), int(self.skip_nonfinite), C.c_float(grp["lr"]),
                                   C.c_float(b1), C.c_float(b2), L.ptr(self._ws), nws, L.stream()), "pa_grad_guard")
-        return self._ws.data_ptr() + L.GRAD_GUARD_CTL_OFFSET
 
-    def _guarded_step(self, flat, g, grp, shadow):
-        """pa_grad_guard (norm, coefficient, apply-or-skip, bias corrections: all into the device control block), then the
-        Adam kernel that reads them.  Enqueue only: whether the step was applied is not known to the host here."""
-        ctl = self._enqueue_guard(flat, g, grp)
-        b1, b2 = grp["betas"]
-        self.model.wait_transposed()
-        L.check(L.lib().pa_adam_step_guarded(L.ptr(flat), L.ptr(g), L.ptr(self._m), L.ptr(self._v), L.ptr(shadow),
-                                             C.c_int64(flat.numel()), C.c_float(b1), C.c_float(b2), C.c_float(grp["eps"]),
-                                             C.c_float(self.grad_scale), C.c_float(self.clip_value or 0.0), C.c_void_p(ctl),
-                                             L.stream()), "pa_adam_step_guarded")
-
-    def _ext_step(self, flat, g, grp, shadow):
-        """pa_adam_step_ext: decay and / or EMA inside the Adam pass; with the guard on, pa_grad_guard first and its control
-        block handed to the kernel (which then takes the step count, and with it the EMA's d_t, from the device)."""
+    def _adam_step(self, flat, g, grp, shadow):
+        """The one step path: pa_adam_step_ext, with decay and / or EMA inside the Adam pass when they are set.  With the guard on,
+        pa_grad_guard first (norm, coefficient, apply-or-skip, bias corrections: all into the device control block) and the block
+        handed to the kernel, which then takes the step count, and with it the EMA's d_t, from the device.  Enqueue only: whether
+        a guarded step was applied is not known to the host here."""
         if self.ema_decay is not None:
             if self._ema is None:
                 self._ema = flat.detach().clone()
                 self._ema_base = -self._applied_steps()
             elif self._ema.device != flat.device:
                 self._ema = self._ema.to(flat.device)
-        if self.weight_decay > 0 and self.no_decay == "1d" and (self._bits is None or self._bits.device != flat.device):
+        masked = self.weight_decay > 0 and self.no_decay == "1d"
+        if masked and (self._bits is None or self._bits.device != flat.device):
             self._bits = torch.from_numpy(decay_bitmask(self.model, "1d")).to(flat.device)
         if self.guarded:
             self._enqueue_guard(flat, g, grp)
         else:
             self._step += 1
-        self.model.wait_transposed()
+        self.model.wait_transposed()             # (the side-stream W^T refresh of the step before reads what this kernel rewrites)
         ops.adam_step_ext(flat, g, self._m, self._v, step=self._step, ws=self._ws if self.guarded else None, lr=grp["lr"],
                           b1=grp["betas"][0], b2=grp["betas"][1], eps=grp["eps"], gscale=self.grad_scale,
                           clip_value=self.clip_value or 0.0, weight_decay=self.weight_decay,
-                          decay_bits=self._bits if self.weight_decay > 0 and self.no_decay == "1d" else None, ema=self._ema,
+                          decay_bits=self._bits if masked else None, ema=self._ema,
                           ema_decay=self.ema_decay or 0.0, ema_warmup=self.ema_warmup, p_bf16=shadow)
 
     @property

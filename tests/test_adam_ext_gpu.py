@@ -81,12 +81,13 @@ def test_everything_off_under_the_guard_is_the_guarded_step(n):
 @pytest.mark.parametrize("n", [N_TAIL, N_ONE, N_TWO])
 def test_everything_off_without_the_guard_against_the_plain_step(n):
     """ctl NULL: m and v equal pa_adam_step's bit for bit; p is within one f32 ulp of it, and the shadow is the bf16 of the
-    kernel's own p, so it equals pa_adam_step's wherever p does.  (pa_adam_step and pa_adam_step_guarded already differ in this
-    way: the compiler forms the denominator's fma and the final quotient differently when left to it; the extended kernel spells
-    them as the guarded one does.)
+    kernel's own p, so it equals pa_adam_step's wherever p does.
 
-    Observed on MI355X (three steps): n = 3: 0 elements of p differ; n = 100 003: 0; n = 4 194 309: 0 - the spelled forms are
-    the ones the compiler chose for adam_kernel at this compiler version; the one-ulp allowance is what the forms guarantee."""
+    pa_adam_step and pa_adam_step_ext launch the same kernel instantiation (adam_ext_kernel<0, false>), so this now holds the
+    two entries' host set-up together and observes 0 differing elements.  It was written when pa_adam_step had a kernel of its
+    own in plain C++ expressions, whose fused multiply-adds the compiler chose (observed then on MI355X, three steps: 0 elements
+    of p differing at n = 3, 100 003 and 4 194 309); that pa_adam_step still gives that kernel's bits is held by
+    tests/test_rowops_family_bits_gpu.py."""
     a, b = State(rnd(n, 310, 0.25)), State(rnd(n, 310, 0.25))
     for step in (1, 2, 3):
         g = rnd(n, 310 + step, 1e-3).to(DEV)

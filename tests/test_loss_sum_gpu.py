@@ -1,4 +1,4 @@
-"""The training loss is summed in an order-free way (csrc/rowops.hip mixture_nll_fwd_kernel<true>, pa_mixture_nll_fwd_fin): the
+"""The training loss is summed in an order-free way (csrc/rowops.hip mixture_nll_fwd_kernel<true, false>, pa_mixture_nll_fwd_fin): the
 blocks' NLL sums meet in a 64-bit fixed-point word, so the loss has the same bits whatever order the blocks arrive in - which
 tests/test_device_data_gpu.py::test_train_step_equals_the_cpu_collated_batch relies on (a float atomic made it differ by 3 ulp)."""
 import numpy as np

@@ -36,7 +36,7 @@ KEYS = [  # json key -> regex on the demangled kernel name
     ("layernorm_fwd", r"layernorm_fwd_kernel<__bf16"),
     ("splitk_reduce", r"splitk_reduce_kernel"),
     ("splitk_reduce_many", r"splitk_reduce_many_kernel"),
-    ("adam", r"adam_kernel"),
+    ("adam", r"adam_ext_kernel"),
 ]
 
 

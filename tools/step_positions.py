@@ -7,7 +7,7 @@ rows = con.execute("""select s.kernel_name, d.start, d.end, d.grid_size_x, d.wor
                       join rocpd_info_kernel_symbol s on d.kernel_id = s.id order by d.start""").fetchall()
 names = [re.sub(r"\(anonymous namespace\)::", "", r[0]) for r in rows]
 # a step ends with the Adam kernel
-ends = [i for i, n in enumerate(names) if "adam_kernel" in n]
+ends = [i for i, n in enumerate(names) if "adam_ext_kernel" in n]
 steps = [(ends[k] + 1, ends[k + 1] + 1) for k in range(len(ends) - 1)]
 steps = steps[3:]                                     # warm-up
 agg = {}

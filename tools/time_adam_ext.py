@@ -1,11 +1,12 @@
-"""What the extended Adam pass (pa_adam_step_ext) costs at the headline parameter count: the kernel alone,
-back to back, hip-event time per call, every variant in alternating blocks in ONE process.
+"""What the Adam pass (the one kernel behind pa_adam_step / pa_adam_step_guarded / pa_adam_step_ext) costs at
+the headline parameter count: the kernel alone, back to back, hip-event time per call, every variant in alternating blocks in ONE process.
 
     python tools/time_adam_ext.py [--parent-lib PATH/libplank_hip.so] [--blocks 6] [--reps 100] [--out profiles/adam_ext_time.txt]
 
-Variants: pa_adam_step of this tree twice (an A/A pair: the session's spread), pa_adam_step of the library given with
---parent-lib (a build of the parent commit), and pa_adam_step_ext with (a) everything off, (b) decay with the 1-D mask, (c) EMA,
-(d) both, (e) both under the guard's control block.  Bytes per call are counted from the buffer widths the kernel must move."""
+Variants: pa_adam_step of this tree twice (an A/A pair: the session's spread) and pa_adam_step_guarded; both entries of the library
+given with --parent-lib (a build of the parent commit); and pa_adam_step_ext with (a) everything off - the same kernel instantiation as
+pa_adam_step, through the struct entry -, (b) decay with the 1-D mask, (c) EMA, (d) both, (e) both under the guard's control block.
+Bytes per call are counted from the buffer widths the kernel must move."""
 import argparse
 import ctypes as C
 import os
@@ -48,16 +49,27 @@ def plain(lib):
     return lambda: L.check(fn(*a), "pa_adam_step")
 
 
+def guarded(lib):
+    fn = lib.pa_adam_step_guarded
+    fn.restype = C.c_int32
+    a = (L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(pb), C.c_int64(n), C.c_float(0.9), C.c_float(0.999), C.c_float(1e-8),
+         C.c_float(1.0), C.c_float(0.0), C.c_void_p(ws.data_ptr() + L.GRAD_GUARD_CTL_OFFSET), L.stream())
+    return lambda: L.check(fn(*a), "pa_adam_step_guarded")
+
+
 def ext(**kw):
     return lambda: ops.adam_step_ext(p, g, m, v, step=1000, p_bf16=pb, **kw)
 
 
 base, with_ema, with_mask = 30 * n, 8 * n, bits.numel()            # 4 f32 reads + 3 f32 writes + the bf16 shadow; e read + write
 variants = {"pa_adam_step (A)": (plain(L.lib()), base), "pa_adam_step (A again)": (plain(L.lib()), base)}
+variants["pa_adam_step_guarded"] = (guarded(L.lib()), base)
 if args.parent_lib:
-    variants["pa_adam_step (parent build)"] = (plain(C.CDLL(os.path.abspath(args.parent_lib))), base)
+    parent = C.CDLL(os.path.abspath(args.parent_lib))
+    variants["pa_adam_step (parent build)"] = (plain(parent), base)
+    variants["pa_adam_step_guarded (parent build)"] = (guarded(parent), base)
 variants.update({
-    "ext (a) everything off": (ext(), base),
+    "ext (a) off: pa_adam_step's kernel": (ext(), base),
     "ext (b) decay + mask": (ext(weight_decay=0.01, decay_bits=bits), base + with_mask),
     "ext (c) EMA": (ext(ema=ema, ema_decay=0.999), base + with_ema),
     "ext (d) decay + mask + EMA": (ext(weight_decay=0.01, decay_bits=bits, ema=ema, ema_decay=0.999), base + with_mask + with_ema),
@@ -90,7 +102,7 @@ lines = [f"device: {torch.cuda.get_device_name(0)}; n = {n} parameters ({4 * n /
          f"blocks of {args.reps} back-to-back calls per variant, hip-event time per block / calls (launch gaps included)"]
 for k, t in times.items():
     nbytes = variants[k][1]
-    lines.append(f"{k:30s}: mean {mean[k]:7.1f} us  min {min(t):7.1f}  max {max(t):7.1f}  x{mean[k] / ref:.3f} of (A)  "
+    lines.append(f"{k:36s}: mean {mean[k]:7.1f} us  min {min(t):7.1f}  max {max(t):7.1f}  x{mean[k] / ref:.3f} of (A)  "
                  f"{nbytes / 1e6:7.1f} MB -> {nbytes / mean[k] / 1e6:.2f} TB/s")
 lines.append(f"A/A spread: |A - A again| {abs(mean['pa_adam_step (A)'] - mean['pa_adam_step (A again)']):.1f} us; block-to-block range "
              f"of (A): {max(times['pa_adam_step (A)']) - min(times['pa_adam_step (A)']):.1f} us")
