@@ -14,6 +14,7 @@ import torch
 import bf16_decode_sim as SIM
 import large_cases as LC
 import prefix_reference as PR
+import shape_cases as SC
 from oracle import plank_oracle as O
 
 N_VOCAB_FORCED = 512          # forced vocabulary tokens are drawn from [0, 512): never END (512) / PAD (513)
@@ -30,6 +31,7 @@ CASES = {
     "E": dict(case="sideface", B=520, n=128, rows=[0, 173, 346, 519]),
     "F": dict(case="small", B=4, n=36, rows=[0, 1, 2, 3]),
 }
+CASES.update(SC.logprob_cases())                                   # the shape lattice (tests/test_shape_lattice_gpu.py): all 3 rows, 30 steps
 _ALLOWED = (O.pointer_mask(O.OracleCfg(), 1024) != 0).numpy()      # the oracle's eval pointer mask [t][j] (pinned by the golden tests)
 
 
@@ -43,7 +45,7 @@ def case_dict(cid):
         from conftest import load_fixture
         sd, batch, _ = load_fixture("fixture_small.npz")
         return dict(sd=sd, cfg=O.OracleCfg(**SMALL), batch=batch, d=64, ff=128)
-    c = LC.CASES[name]
+    c = LC.CASES[name] if name in LC.CASES else SC.CASES[name]      # (names large_cases does not know: the shape lattice)
     return dict(c, decode_seed=10) if name == "sideface" else c      # (sideface has no decode batch of its own)
 
 

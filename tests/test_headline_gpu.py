@@ -250,14 +250,10 @@ def test_f32_sideface_full_batch_64():
     f32_gate("sideface-64", c, sd, batch, m, out, mem, hid, grads)
 
 
-@pytest.mark.parametrize("name", ["headline", "complete", "visible", "sideface", "live", "gelu", "t1024"])
-def test_bf16_train_step_per_tensor(name):
-    """The benchmarked bf16 path against the f32 oracle, tensor by tensor: cosine and relative L2 of every gradient
-    (weighted summary printed), loss, memory and hiddens."""
-    c = LC.CASES[name]
-    sd, batch, ref, rgrads = oracle_train(name)
-    m = hip_model(c, "bf16", sd)
-    out, mem, hid, grads = run_hip_train(m, batch)
+def bf16_per_tensor_gate(name, batch, ref, rgrads, out, mem, hid, grads):
+    """The per-tensor rule of the bf16 step against the float64 oracle (`ref`, `rgrads`): loss within 2e-2, memory within 2e-2 and
+    hiddens within 3e-2 in relative L2, and per gradient tensor cosine > 0.997 and rel-L2 < 0.08 where the tensor carries more than
+    1e-3 of the gradient norm, 0.9 and 0.5 elsewhere.  Returns what it measured, worst tensors first."""
     loss_ref = float(ref["loss"])
     assert abs(out["loss"].item() - loss_ref) < 2e-2 * abs(loss_ref), (out["loss"].item(), loss_ref)
     valid = ~batch["input_mask"]
@@ -287,6 +283,18 @@ def test_bf16_train_step_per_tensor(name):
         big = nr / tot > 1e-3
         assert cos > (0.997 if big else 0.9), (k, cos, rl2, nr / tot)
         assert rl2 < (0.08 if big else 0.5), (k, cos, rl2, nr / tot)
+    return dict(r_mem=r_mem, r_hid=r_hid, rows=[(k, cos, rl2, nr / tot) for k, cos, rl2, nr in rows])
+
+
+@pytest.mark.parametrize("name", ["headline", "complete", "visible", "sideface", "live", "gelu", "t1024"])
+def test_bf16_train_step_per_tensor(name):
+    """The benchmarked bf16 path against the f32 oracle, tensor by tensor: cosine and relative L2 of every gradient
+    (weighted summary printed), loss, memory and hiddens."""
+    c = LC.CASES[name]
+    sd, batch, ref, rgrads = oracle_train(name)
+    m = hip_model(c, "bf16", sd)
+    out, mem, hid, grads = run_hip_train(m, batch)
+    bf16_per_tensor_gate(name, batch, ref, rgrads, out, mem, hid, grads)
 
 
 @pytest.mark.parametrize("name,dtype", [("headline", "f32"), ("headline", "bf16"), ("sideface", "f32"), ("live", "f32"), ("gelu", "f32"),

@@ -147,6 +147,49 @@ def test_mixture_inputs_meet_their_conditions(c):
         assert not R["valid"].any() and np.isnan(rp.nll_fwd_ref(c, t)["loss"][0])
 
 
+NLL_TEST_ORDERS = 2000
+
+
+@pytest.mark.parametrize("c", BY_GROUP["nll"], ids=[c["name"] for c in BY_GROUP["nll"]])
+def test_nll_sum_passes_in_every_arrival_order_and_every_defect_still_fails(c):
+    """pa_mixture_nll_fwd adds its block partials with float atomics: the order of addition is the arrival order.  The kernel's sum restated on
+    the CPU (float32 rows, four per block, (r0 + r1) + (r2 + r3), the non-zero partials added in float32) passes verify_nll in the natural order
+    and in 2000 seeded orders - seeded apart from the 64 orders behind the yardstick (rowops_parity.nll_sum_yardstick) - and the checker
+    still rejects every listed defect.  verify_nll reads the sum's VALUE alone, so it runs once per distinct value the orders produce."""
+    t = inputs(c)
+    sim = rp.simulate_nll(c, t)
+    rows = rp.nll_fwd_cpu32(c, t)["row_nll"]
+    sums = rp.nll_order_sums(rows, rp.seed_of(c["name"], 1), NLL_TEST_ORDERS)
+    assert sums.dtype == np.float32 and sums.shape == (1 + NLL_TEST_ORDERS,)
+    values, counts = np.unique(sums, return_counts=True)
+    ref = rp.nll_fwd_ref(c, t)["nll"]
+    e = ref[1] + 0.5 * rp.TINY
+    print(f"{c['name']}: {len(rp.nll_block_partials(rows))} non-zero block partials; {len(values)} distinct float32 sums over {len(sums)} orders: "
+          + ", ".join(f"r {abs(float(v) - ref[0]) / e:.4g} ({100.0 * n / len(sums):.1f} %)" for v, n in zip(values, counts))
+          + f"; yardstick r {abs(rp.nll_sum_yardstick(c, rp.nll_fwd_cpu32(c, t), ref[0]) - ref[0]) / e:.4g}, torch's float32 sum r {abs(sim['fwd']['stats'][0] - ref[0]) / e:.4g}")
+    for v in values:
+        got = dict(sim, fwd=dict(sim["fwd"], stats=np.array([float(v), sim["fwd"]["stats"][1], sim["fwd"]["stats"][2]])))
+        rp.verify_nll(c, t, got)
+    # The defects: each uses the kernel's own restated sum of its float32 rows; what a case catches is what it caught under the one-order rule.
+    for defect in rp.GROUPS["nll"][3]:
+        bad = rp.simulate_nll(c, t, defect)
+        dsum = rp.nll_order_sums(rp.nll_fwd_cpu32(c, t, defect)["row_nll"], 0, 0)[0]
+        bad["fwd"] = dict(bad["fwd"], stats=np.array([float(dsum), bad["fwd"]["stats"][1], bad["fwd"]["stats"][2]]))
+        if defect in NLL_DEFECT_NOT_SEEN.get(c["name"], NLL_DEFECT_NOT_SEEN["x1" if c["scale"] == 1 else "x30"]):
+            rp.verify_nll(c, t, bad)                                # (the defect changes nothing this case can see: it must not fail for another reason)
+        else:
+            with pytest.raises(AssertionError):
+                rp.verify_nll(c, t, bad)
+
+
+# Defects a case cannot see (all others must fail it): without the maximum, exp overflows only at scale 30 with more than 3 entries; the all-pad
+# case has no valid row, so only the masked pointer entries of row_lse differ; at V 1030, T 7, scale 30 no switch probability of a valid row
+# lies beyond the clamp.
+NLL_DEFECT_NOT_SEEN = {"x1": {"lse_without_max"}, "x30": set(), "nll_B1_T5_V3_ld3_x30": {"lse_without_max"},
+                       "nll_B1_T7_V1030_ld1032_x30": {"switch_clamp_ignored"},
+                       "nll_B2_T36_V514_ld520_allpad": {"lse_without_max", "argmax_larger_index_on_tie", "switch_clamp_ignored", "gscale_left_out"}}
+
+
 def test_segment_lengths_are_placed_by_construction():
     for c in BY_GROUP["embed_seg"]:
         t = inputs(c)
