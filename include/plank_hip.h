@@ -975,6 +975,43 @@ int pa_tokenise_drawings(const int32_t* line_off, const double* box, const doubl
                          uint8_t* in_mask, int64_t* out_value, int64_t* out_label, uint8_t* out_mask,
                          int32_t* n_tokens, void* stream);
 
+/* ---- side-face extraction from the line drawing (csrc/sideface.h, compiled into csrc/tokenise.hip) ----
+ * pa_tokenise_drawings for the sideface kind when the info files store no faces: one launch, one block of 256 threads per batch
+ * element, extracts the side faces of each drawing from its two-point, axis-aligned segments and tokenises them.  Restates
+ * plankassembly_amd/datasets.py `extract_sideface_flags` (reference plankassembly/datasets/sideface_data.py:22-38 centre lines of
+ * the thin polygons, :41-80 sequential merge of collinear ones and flat-capped buffer, :109-135 per view 0 .. 2, :233-245
+ * augmentation with the fallback to the clean drawing) for the domain of section 26, float64, every operation rounded on its own.
+ * The arguments of pa_tokenise_drawings, of which box, type and in_type are not read (NULL) and with_type must be 0, seg is
+ * required, and line_off / view describe the LINES of each drawing (at most PA_TOKENISE_MAX_LINES are read); then
+ *   max_thickness, min_thickness, merge_tolerance: the thresholds already divided by SCALE (NaN: PA_EINVAL);
+ *   faces_out f64 [B][F][4], faceviews_out uint8 [B][F], n_faces_out int32 [B] (each may be NULL), F = (S - 1) / 4: the merged
+ *     boxes before quantisation in the order of the row's tokens (zero behind the drawing's count);
+ *   flags_out int32 [B] (required): PA_EXTRACT_* bits.
+ * Faces: per view, nodes are the distinct end points (by value), dangles are pruned, next(u -> v) turns clockwise at v from v -> u
+ * (face on the left), edges with one ring on both sides are removed and the rings traced once more; a ring of positive float64
+ * shoelace area (summed from its smallest half-edge; half-edge 2i / 2i + 1 = line i forward / backward) gives its bounds.
+ * Candidates in the order (xmin, ymin, xmax, ymax, smallest half-edge) per view, horizontal before vertical; the reference's
+ * merge, literally; boxes of width >= min_thickness.  With augmentation the lines first get the noise of pa_tokenise_drawings
+ * (same draws); a drawing whose noisy lines give no box is extracted again from the clean lines (PA_EXTRACT_FELL_BACK).
+ * A drawing outside the domain (a segment not axis-aligned, a coordinate not in [-1, 1], two segments of a view leaving an end
+ * point in one direction) gives no box and PA_EXTRACT_OUT_OF_DOMAIN, never a fault; more than F boxes: those that sort first in
+ * the row's order stay, PA_EXTRACT_TRUNCATED; a ring with |2A| < 1e-12 is dropped, PA_EXTRACT_DEGENERATE.
+ * (S - 1) / 4 above PA_TOKENISE_MAX_LINES: PA_ESHAPE. */
+#define PA_EXTRACT_OUT_OF_DOMAIN 1
+#define PA_EXTRACT_TRUNCATED 2
+#define PA_EXTRACT_FELL_BACK 4
+#define PA_EXTRACT_DEGENERATE 8
+int pa_tokenise_sideface_drawings(const int32_t* line_off, const double* box, const double* seg, const uint8_t* view,
+                                  const uint8_t* type, const int32_t* plank_off, const double* coords, const int32_t* attach,
+                                  int32_t N, const int32_t* index, int32_t B, int32_t S, int32_t T, int32_t n_bits,
+                                  int32_t tok_end, int32_t tok_pad, int32_t vocab, int32_t with_type, int32_t augmentation,
+                                  double aug_ratio, double noise_ratio, double noise_length, uint32_t seed, uint32_t epoch,
+                                  int64_t* in_value, int64_t* in_pos, int64_t* in_coord, int64_t* in_view, int64_t* in_type,
+                                  uint8_t* in_mask, int64_t* out_value, int64_t* out_label, uint8_t* out_mask,
+                                  int32_t* n_tokens, double max_thickness, double min_thickness, double merge_tolerance,
+                                  double* faces_out, uint8_t* faceviews_out, int32_t* n_faces_out, int32_t* flags_out,
+                                  void* stream);
+
 /* ---- plank matching (csrc/match.hip, core csrc/match_core.h; plankassembly_amd/metric.py DevicePlankScorer) ----
  * One launch, one wave per pair: two token rows compared as sets of planks.  Restates plankassembly_amd/metric.py
  * `pairwise_iou_3d` and `HungarianMatcher` (reference third_party/matcher.py:15-27 IoU, :29-61 cost -1 where IoU > threshold

@@ -75,26 +75,13 @@ __device__ __forceinline__ bool tk_noise(double& x0, double& y0, double& x1, dou
     return true;
 }
 
-__global__ __launch_bounds__(TK_THREADS) void tokenise_kernel(TkArgs a) {
-    __shared__ uint64_t key[TK_MAX_LINES];             // sort key per line (line order)
-    __shared__ uint64_t skey[TK_MAX_LINES];            // the keys in sorted order
-    __shared__ uint32_t selh[TK_MAX_LINES];            // selection hash per line
-    __shared__ uint16_t spos[TK_MAX_LINES];            // rank within the view, sorted order
-
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int d = a.index[b];
-    const bool have = d >= 0 && d < a.N;
-    const int lo = have ? a.line_off[d] : 0;
-    int n = have ? a.line_off[d + 1] - lo : 0;
-    n = n < 0 ? 0 : (n > TK_MAX_LINES ? TK_MAX_LINES : n);
-    const int max_lines = (a.S - 1) >> 2;              // what fits the row (the host rejects longer drawings)
-    if (n > max_lines) n = max_lines < 0 ? 0 : max_lines;
-    const double rq = (double)((1 << a.n_bits) - 1);
-
-    // ---- the two per-drawing draws
+// ---- the stages tokenise_kernel and sideface_kernel (sideface.h) share; every one is called by the whole block
+// The two per-drawing draws over the drawing's ``n`` lines, and the selection hash of every line.  true: the drawing is augmented.
+__device__ __forceinline__ bool tk_draws(const TkArgs& a, int d, int n, uint32_t* selh, uint32_t& base, int& num_select) {
+    const int tid = threadIdx.x;
     bool augmented = false;
-    int num_select = 0;
-    uint32_t base = 0;
+    num_select = 0;
+    base = 0;
     if (a.augment && a.seg && n > 0) {
         base = tk_base(a.seed, a.epoch, (uint32_t)d);
         if (tk_unit(tk_draw(base, TK_DRAWING, TK_SLOT_AUGMENT)) < a.aug_ratio) {
@@ -110,45 +97,40 @@ __global__ __launch_bounds__(TK_THREADS) void tokenise_kernel(TkArgs a) {
         for (int i = tid; i < n; i += TK_THREADS) selh[i] = tk_draw(base, (uint32_t)i, TK_SLOT_SELECT);
         __syncthreads();
     }
+    return augmented;
+}
 
-    // ---- boxes -> keys
-    for (int i = tid; i < n; i += TK_THREADS) {
-        double x0, y0, x1, y1;
-        bool kept = true;
-        if (augmented) {
-            const double* s = a.seg + (size_t)(lo + i) * 4;
-            double sx0 = s[0], sy0 = s[1], sx1 = s[2], sy1 = s[3];
-            const uint64_t mine = ((uint64_t)selh[i] << 32) | (uint32_t)i;
-            int below = 0;                                                   // the num_select smallest (hash, line) pairs
-            for (int j = 0; j < n; ++j) below += (((uint64_t)selh[j] << 32) | (uint32_t)j) < mine;
-            if (below < num_select) kept = tk_noise(sx0, sy0, sx1, sy1, base, (uint32_t)i, a.noise_length);
-            x0 = sx0 < sx1 ? sx0 : sx1; x1 = sx0 < sx1 ? sx1 : sx0;          // the bounds of the segment
-            y0 = sy0 < sy1 ? sy0 : sy1; y1 = sy0 < sy1 ? sy1 : sy0;
-        } else {
-            const double* bx = a.box + (size_t)(lo + i) * 4;
-            x0 = bx[0]; y0 = bx[1]; x1 = bx[2]; y1 = bx[3];
-        }
-        uint64_t k = TK_DELETED;
-        if (kept) {
-            const uint64_t qmask = (1ull << TK_Q_BITS) - 1;
-            const uint64_t q0 = (uint64_t)tk_quantise(x0, rq) & qmask, q1 = (uint64_t)tk_quantise(y0, rq) & qmask;
-            const uint64_t q2 = (uint64_t)tk_quantise(x1, rq) & qmask, q3 = (uint64_t)tk_quantise(y1, rq) & qmask;
-            // np.lexsort(with_view.T[[3, 1, 2, 0, 4]]): view, column 0, column 2, column 1, column 3; stable -> line number
-            k = ((uint64_t)a.view[lo + i] << TK_VIEW_SHIFT) | (q0 << (TK_LINE_BITS + 3 * TK_Q_BITS)) |
-                (q2 << (TK_LINE_BITS + 2 * TK_Q_BITS)) | (q1 << (TK_LINE_BITS + TK_Q_BITS)) | (q3 << TK_LINE_BITS) | (uint64_t)i;
-        }
-        key[i] = k;
-    }
-    __syncthreads();
+// Line i of an augmented drawing: the segment as the noise leaves it.  false: the line is deleted.
+__device__ __forceinline__ bool tk_noisy_segment(const TkArgs& a, int lo, int i, int n, const uint32_t* selh, int num_select,
+                                                 uint32_t base, double& sx0, double& sy0, double& sx1, double& sy1) {
+    const double* s = a.seg + (size_t)(lo + i) * 4;
+    sx0 = s[0]; sy0 = s[1]; sx1 = s[2]; sy1 = s[3];
+    const uint64_t mine = ((uint64_t)selh[i] << 32) | (uint32_t)i;
+    int below = 0;                                                   // the num_select smallest (hash, line) pairs
+    for (int j = 0; j < n; ++j) below += (((uint64_t)selh[j] << 32) | (uint32_t)j) < mine;
+    if (below < num_select) return tk_noise(sx0, sy0, sx1, sy1, base, (uint32_t)i, a.noise_length);
+    return true;
+}
 
-    // ---- rank by counting: every key is distinct (the line number is part of it)
+// np.lexsort(with_view.T[[3, 1, 2, 0, 4]]): view, column 0, column 2, column 1, column 3; stable -> primitive number i
+__device__ __forceinline__ uint64_t tk_key(uint32_t view, double x0, double y0, double x1, double y1, double rq, int i) {
+    const uint64_t qmask = (1ull << TK_Q_BITS) - 1;
+    const uint64_t q0 = (uint64_t)tk_quantise(x0, rq) & qmask, q1 = (uint64_t)tk_quantise(y0, rq) & qmask;
+    const uint64_t q2 = (uint64_t)tk_quantise(x1, rq) & qmask, q3 = (uint64_t)tk_quantise(y1, rq) & qmask;
+    return ((uint64_t)view << TK_VIEW_SHIFT) | (q0 << (TK_LINE_BITS + 3 * TK_Q_BITS)) |
+           (q2 << (TK_LINE_BITS + 2 * TK_Q_BITS)) | (q1 << (TK_LINE_BITS + TK_Q_BITS)) | (q3 << TK_LINE_BITS) | (uint64_t)i;
+}
+
+// Rank by counting: every key is distinct (the primitive number is part of it).  Returns the number of kept primitives.
+__device__ __forceinline__ int tk_rank(const uint64_t* key, uint64_t* skey, uint16_t* spos, int n) {
+    const int tid = threadIdx.x;
     int nk = 0;
     for (int i0 = 0; i0 < n; i0 += TK_THREADS) {
         const int i = i0 + tid;
         const uint64_t mine = i < n ? key[i] : TK_DELETED;
         const bool kept = mine != TK_DELETED;
         if (kept) {
-            const uint64_t view_floor = mine >> TK_VIEW_SHIFT << TK_VIEW_SHIFT;      // the smallest key of the line's view
+            const uint64_t view_floor = mine >> TK_VIEW_SHIFT << TK_VIEW_SHIFT;      // the smallest key of the primitive's view
             int below = 0, below_view = 0;
             for (int j = 0; j < n; ++j) {
                 const uint64_t k = key[j];
@@ -161,8 +143,12 @@ __global__ __launch_bounds__(TK_THREADS) void tokenise_kernel(TkArgs a) {
         nk += __syncthreads_count(kept);
     }
     __syncthreads();
+    return nk;
+}
 
-    // ---- encoder rows: 4 tokens per kept line, END, PAD; consecutive threads store consecutive elements
+// Encoder rows: 4 tokens per kept primitive, END, PAD; consecutive threads store consecutive elements
+__device__ __forceinline__ void tk_store_inputs(const TkArgs& a, int b, int lo, const uint64_t* skey, const uint16_t* spos, int nk) {
+    const int tid = threadIdx.x;
     const size_t row = (size_t)b * a.S;
     const int n_tok = 4 * nk;
     for (int j = tid; j < a.S; j += TK_THREADS) {
@@ -185,8 +171,11 @@ __global__ __launch_bounds__(TK_THREADS) void tokenise_kernel(TkArgs a) {
         a.in_mask[row + j] = j > n_tok;
     }
     if (tid == 0) a.n_tokens[b] = n_tok + 1;
+}
 
-    // ---- decoder rows: 6 tokens per plank, END, PAD; a pointer label where the plank attaches
+// Decoder rows: 6 tokens per plank, END, PAD; a pointer label where the plank attaches
+__device__ __forceinline__ void tk_store_outputs(const TkArgs& a, int b, int d, bool have, double rq) {
+    const int tid = threadIdx.x;
     const int plo = have ? a.plank_off[d] : 0;
     int np = have ? a.plank_off[d + 1] - plo : 0;
     const int max_planks = (a.T - 1) / 6;
@@ -205,6 +194,50 @@ __global__ __launch_bounds__(TK_THREADS) void tokenise_kernel(TkArgs a) {
         a.out_mask[orow + j] = j > 6 * np;
     }
 }
+
+__global__ __launch_bounds__(TK_THREADS) void tokenise_kernel(TkArgs a) {
+    __shared__ uint64_t key[TK_MAX_LINES];             // sort key per line (line order)
+    __shared__ uint64_t skey[TK_MAX_LINES];            // the keys in sorted order
+    __shared__ uint32_t selh[TK_MAX_LINES];            // selection hash per line
+    __shared__ uint16_t spos[TK_MAX_LINES];            // rank within the view, sorted order
+
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int d = a.index[b];
+    const bool have = d >= 0 && d < a.N;
+    const int lo = have ? a.line_off[d] : 0;
+    int n = have ? a.line_off[d + 1] - lo : 0;
+    n = n < 0 ? 0 : (n > TK_MAX_LINES ? TK_MAX_LINES : n);
+    const int max_lines = (a.S - 1) >> 2;              // what fits the row (the host rejects longer drawings)
+    if (n > max_lines) n = max_lines < 0 ? 0 : max_lines;
+    const double rq = (double)((1 << a.n_bits) - 1);
+
+    uint32_t base;
+    int num_select;
+    const bool augmented = tk_draws(a, d, n, selh, base, num_select);
+
+    // ---- boxes -> keys
+    for (int i = tid; i < n; i += TK_THREADS) {
+        double x0, y0, x1, y1;
+        bool kept = true;
+        if (augmented) {
+            double sx0, sy0, sx1, sy1;
+            kept = tk_noisy_segment(a, lo, i, n, selh, num_select, base, sx0, sy0, sx1, sy1);
+            x0 = sx0 < sx1 ? sx0 : sx1; x1 = sx0 < sx1 ? sx1 : sx0;          // the bounds of the segment
+            y0 = sy0 < sy1 ? sy0 : sy1; y1 = sy0 < sy1 ? sy1 : sy0;
+        } else {
+            const double* bx = a.box + (size_t)(lo + i) * 4;
+            x0 = bx[0]; y0 = bx[1]; x1 = bx[2]; y1 = bx[3];
+        }
+        key[i] = kept ? tk_key(a.view[lo + i], x0, y0, x1, y1, rq, i) : TK_DELETED;
+    }
+    __syncthreads();
+
+    const int nk = tk_rank(key, skey, spos, n);
+    tk_store_inputs(a, b, lo, skey, spos, nk);
+    tk_store_outputs(a, b, d, have, rq);
+}
+
+#include "sideface.h"                                  // sideface_kernel and its launch arguments, on the stages above
 
 }  // namespace
 
@@ -233,5 +266,40 @@ extern "C" int pa_tokenise_drawings(const int32_t* line_off, const double* box, 
     a.in_value = in_value; a.in_pos = in_pos; a.in_coord = in_coord; a.in_view = in_view; a.in_type = in_type;
     a.in_mask = in_mask; a.out_value = out_value; a.out_label = out_label; a.out_mask = out_mask; a.n_tokens = n_tokens;
     PA_LAUNCH(tokenise_kernel, dim3(B), dim3(TK_THREADS), 0, ST(stream), a);
+    return 0;
+}
+
+extern "C" int pa_tokenise_sideface_drawings(const int32_t* line_off, const double* box, const double* seg, const uint8_t* view,
+                                             const uint8_t* type, const int32_t* plank_off, const double* coords,
+                                             const int32_t* attach, int32_t N, const int32_t* index, int32_t B, int32_t S, int32_t T,
+                                             int32_t n_bits, int32_t tok_end, int32_t tok_pad, int32_t vocab, int32_t with_type,
+                                             int32_t augmentation, double aug_ratio, double noise_ratio, double noise_length,
+                                             uint32_t seed, uint32_t epoch, int64_t* in_value, int64_t* in_pos, int64_t* in_coord,
+                                             int64_t* in_view, int64_t* in_type, uint8_t* in_mask, int64_t* out_value,
+                                             int64_t* out_label, uint8_t* out_mask, int32_t* n_tokens, double max_thickness,
+                                             double min_thickness, double merge_tolerance, double* faces_out,
+                                             uint8_t* faceviews_out, int32_t* n_faces_out, int32_t* flags_out, void* stream) {
+    (void)box; (void)type; (void)in_type;                                    // side faces carry no stored boxes and no type row
+    if (with_type) return PA_EINVAL;
+    if (!line_off || !seg || !view || !coords || !attach || !plank_off || !index || !in_value || !in_pos || !in_coord || !in_view ||
+        !in_mask || !out_value || !out_label || !out_mask || !n_tokens || !flags_out)
+        return PA_EINVAL;
+    if (N <= 0 || B <= 0 || S <= 0 || T <= 0) return PA_EINVAL;
+    if (n_bits < 1 || n_bits > TK_Q_BITS) return PA_ESHAPE;
+    if ((S - 1) / 4 > TK_MAX_LINES) return PA_ESHAPE;                        // the row cannot hold more faces than the sort keys
+    if (!(aug_ratio >= 0.0) || !(noise_ratio >= 0.0) || !(noise_length >= 0.0)) return PA_EINVAL;
+    if (max_thickness != max_thickness || min_thickness != min_thickness || merge_tolerance != merge_tolerance) return PA_EINVAL;
+    SfArgs s;
+    TkArgs& a = s.t;
+    a.line_off = line_off; a.box = nullptr; a.seg = seg; a.view = view; a.type = nullptr;
+    a.plank_off = plank_off; a.coords = coords; a.attach = attach; a.index = index;
+    a.N = N; a.S = S; a.T = T; a.n_bits = n_bits; a.tok_end = tok_end; a.tok_pad = tok_pad; a.vocab = vocab;
+    a.with_type = 0; a.augment = augmentation;
+    a.aug_ratio = aug_ratio; a.noise_ratio = noise_ratio; a.noise_length = noise_length; a.seed = seed; a.epoch = epoch;
+    a.in_value = in_value; a.in_pos = in_pos; a.in_coord = in_coord; a.in_view = in_view; a.in_type = nullptr;
+    a.in_mask = in_mask; a.out_value = out_value; a.out_label = out_label; a.out_mask = out_mask; a.n_tokens = n_tokens;
+    s.max_thickness = max_thickness; s.min_thickness = min_thickness; s.merge_tolerance = merge_tolerance;
+    s.faces_out = faces_out; s.faceviews_out = faceviews_out; s.n_faces_out = n_faces_out; s.flags_out = flags_out;
+    PA_LAUNCH(sideface_kernel, dim3(B), dim3(TK_THREADS), 0, ST(stream), s);
     return 0;
 }

@@ -8,12 +8,15 @@ method names), numpy only - shapely / PythonOCC are not needed to READ the prepa
 * ``LineDataset.__getitem__``                             reference line_data.py:111-142 (info JSON schema: SURVEY appendix B)
 * ``SidefaceDataset.prepare_input_sequence``              reference sideface_data.py:137-189 incl. the empty case (pinned)
 
-Two things need computational geometry the image does not have and stay out of scope: the shapely line-noise
-augmentation (data_utils.py:24-75) is restated here for the straight 2-point segments the info files hold
-(``add_noise``; unpinned - there is no shapely to compare with), and side-face extraction from the line drawing
-(sideface_data.py:21-135: polygonize + STRtree merge) is not reimplemented: ``SidefaceDataset`` reads the side-face
-boxes from the info file when a preprocessing step has stored them (keys ``faces`` / ``faceviews``) and raises
-otherwise.
+* ``extract_sideface`` / ``SidefaceDataset.__getitem__``   reference sideface_data.py:22-135, 215-254
+
+The shapely line-noise augmentation (data_utils.py:24-75) is restated here for the straight 2-point segments the info
+files hold (``add_noise``; unpinned - there is no shapely to compare with).  Side-face extraction from the line drawing
+(sideface_data.py:21-135: polygonize + STRtree merge) is restated for the same domain - two-point, axis-aligned segments
+that meet at end points - as a face trace with comparisons only (``extract_sideface``; DESIGN.md section 26 fixes the
+semantics, csrc/sideface.h runs them on the device).  It is pinned to an independent flood-fill oracle
+(tests/sideface_reference.py), not to GEOS.  ``SidefaceDataset`` extracts when the info file stores no ``faces`` /
+``faceviews`` and whenever it augments; stored faces without augmentation are read as before.
 """
 from __future__ import annotations
 
@@ -104,6 +107,216 @@ def _bounds(lines):
     return np.array([[p[:, 0].min(), p[:, 1].min(), p[:, 0].max(), p[:, 1].max()] for p in lines], dtype=float).reshape(-1, 4)
 
 
+# ---------------------------------------------------------------------------------- side faces
+EXTRACT_OUT_OF_DOMAIN, EXTRACT_TRUNCATED, EXTRACT_FELL_BACK, EXTRACT_DEGENERATE = 1, 2, 4, 8
+_DEGENERATE_AREA2 = 1e-12
+_DOMAIN = ("side-face extraction takes straight two-point, axis-aligned segments with finite coordinates in [-1, 1], "
+           "no two of one view leaving a common end point in the same direction (DESIGN.md section 26); "
+           "for anything else store the extracted boxes in the info file as 'faces' / 'faceviews'")
+
+
+def _trace_faces(seg, numbers):
+    """The bounded faces of ONE view.  ``seg`` float [n, 4] (x0 y0 x1 y1; no zero-length row), ``numbers`` the line number of
+    each row (half-edge 2i / 2i + 1 is line i forward / backward).  Returns ([(xmin, ymin, xmax, ymax, smallest half-edge)],
+    flags).  Nodes are end points compared by value; a node has at most one half-edge per direction E, N, W, S."""
+    n = len(seg)
+    origin, direction, node_of, table = [], [], {}, {}
+    for i in range(n):
+        x0, y0, x1, y1 = (float(v) for v in seg[i])
+        if x0 != x1 and y0 != y1:
+            return [], EXTRACT_OUT_OF_DOMAIN
+        fwd = (0 if x1 > x0 else 2) if y0 == y1 else (1 if y1 > y0 else 3)
+        origin += [(x0, y0), (x1, y1)]
+        direction += [fwd, (fwd + 2) % 4]
+    node = [node_of.setdefault(p, len(node_of)) for p in origin]
+    for h in range(2 * n):
+        if (node[h], direction[h]) in table:
+            return [], EXTRACT_OUT_OF_DOMAIN
+        table[node[h], direction[h]] = h
+    alive = [True] * n
+
+    def drop(i):
+        alive[i] = False
+        del table[node[2 * i], direction[2 * i]], table[node[2 * i + 1], direction[2 * i + 1]]
+
+    def degree(v):
+        return sum((v, d) in table for d in range(4))
+
+    for _ in range(n):                                             # dangles: at most one round per edge
+        dangles = [i for i in range(n) if alive[i] and (degree(node[2 * i]) == 1 or degree(node[2 * i + 1]) == 1)]
+        if not dangles:
+            break
+        for i in dangles:
+            drop(i)
+
+    def rings():
+        """ring label (its smallest half-edge) per surviving half-edge; next(u -> v): clockwise at v from the direction v -> u"""
+        nxt, label = {}, {}
+        for h in range(2 * n):
+            if alive[h >> 1]:
+                v, back = node[h ^ 1], direction[h ^ 1]
+                nxt[h] = next(table[v, (back - k) % 4] for k in (1, 2, 3, 4) if (v, (back - k) % 4) in table)
+        for h in sorted(nxt):
+            g = h
+            while g not in label:
+                label[g] = h
+                g = nxt[g]
+        return nxt, label
+
+    nxt, label = rings()
+    cuts = [i for i in range(n) if alive[i] and label[2 * i] == label[2 * i + 1]]
+    if cuts:                                                       # an edge with the same ring on both sides bounds no face
+        for i in cuts:
+            drop(i)
+        nxt, label = rings()
+    faces, flags = [], 0
+    for rep in sorted(set(label.values())):
+        area2, g = 0.0, rep
+        xs, ys = [], []
+        while True:
+            (xu, yu), (xv, yv) = origin[g], origin[g ^ 1]
+            area2 = area2 + (xu * yv - xv * yu)                    # float64 shoelace from the ring's smallest half-edge
+            xs.append(xu); ys.append(yu)
+            g = nxt[g]
+            if g == rep:
+                break
+        if abs(area2) < _DEGENERATE_AREA2:
+            flags |= EXTRACT_DEGENERATE
+        elif area2 > 0.0:                                          # the face is on the left: positive = bounded
+            faces.append((min(xs), min(ys), max(xs), max(ys), 2 * int(numbers[rep >> 1]) + (rep & 1)))
+    return faces, flags
+
+
+def parse_sideface_candidates(faces, max_thickness):
+    """reference parse_sideface_from_polygons (sideface_data.py:22-38) on face bounds: centre lines (x0, y0, x1, y1, width,
+    type), horizontal (type 1) before vertical (type 0)."""
+    out = []
+    for xmin, ymin, xmax, ymax in (tuple(float(v) for v in f) for f in faces):
+        h, w = ymax - ymin, xmax - xmin
+        if h < max_thickness:
+            yc = (ymin + ymax) / 2
+            out.append((xmin, yc, xmax, yc, h, 1))
+        if w < max_thickness:
+            xc = (xmin + xmax) / 2
+            out.append((xc, ymin, xc, ymax, w, 0))
+    return out
+
+
+def _segments_intersect(a, b):
+    """Closed segments (x0, y0, x1, y1) share a point (shapely ``intersects``): orientation test with the collinear cases."""
+    def orient(px, py, qx, qy, rx, ry):
+        v = (qx - px) * (ry - py) - (qy - py) * (rx - px)
+        return int(v > 0) - int(v < 0)
+
+    def within(px, py, qx, qy, rx, ry):                            # r inside the box of p q
+        return min(px, qx) <= rx <= max(px, qx) and min(py, qy) <= ry <= max(py, qy)
+
+    ax0, ay0, ax1, ay1 = a[:4]
+    bx0, by0, bx1, by1 = b[:4]
+    o1, o2 = orient(ax0, ay0, ax1, ay1, bx0, by0), orient(ax0, ay0, ax1, ay1, bx1, by1)
+    o3, o4 = orient(bx0, by0, bx1, by1, ax0, ay0), orient(bx0, by0, bx1, by1, ax1, ay1)
+    if o1 != o2 and o3 != o4:
+        return True
+    return ((o1 == 0 and within(ax0, ay0, ax1, ay1, bx0, by0)) or (o2 == 0 and within(ax0, ay0, ax1, ay1, bx1, by1)) or
+            (o3 == 0 and within(bx0, by0, bx1, by1, ax0, ay0)) or (o4 == 0 and within(bx0, by0, bx1, by1, ax1, ay1)))
+
+
+def merges_literal(q, m, merge_tolerance):
+    """The reference's test (sideface_data.py:47-60) on two centre lines (x0, y0, x1, y1, width, type)."""
+    xs, ys = (q[0], q[2], m[0], m[2]), (q[1], q[3], m[1], m[3])
+    return (_segments_intersect(q, m)
+            and (max(xs) - min(xs) < merge_tolerance or max(ys) - min(ys) < merge_tolerance)
+            and abs(q[4] - m[4]) < merge_tolerance and q[5] == m[5])
+
+
+def merges_reduced(q, m, merge_tolerance):
+    """The same test as the kernel states it for axis-aligned centre lines: same type, the same centre coordinate exactly,
+    ranges that overlap or touch, widths closer than the tolerance (which then is positive)."""
+    if q[5] != m[5] or not abs(q[4] - m[4]) < merge_tolerance:
+        return False
+    if q[5] == 1:
+        return q[1] == m[1] and q[0] <= m[2] and m[0] <= q[2]
+    return q[0] == m[0] and q[1] <= m[3] and m[1] <= q[3]
+
+
+def merge_colinear_sidefaces(cands, merge_tolerance, merges=merges_literal):
+    """reference merge_colinaer_sidefaces (sideface_data.py:41-76), literally and in that order, on centre lines."""
+    merged = [cands[0]]
+    for q in cands[1:]:
+        hit = [j for j, m in enumerate(merged) if merges(q, m, merge_tolerance)]
+        if hit:
+            xs = [q[0], q[2]] + [merged[j][k] for j in hit for k in (0, 2)]
+            ys = [q[1], q[3]] + [merged[j][k] for j in hit for k in (1, 3)]
+            q = (min(xs), min(ys), max(xs), max(ys), q[4], q[5])
+            for j in reversed(hit):
+                merged.pop(j)
+        merged.append(q)
+    return merged
+
+
+def sideface_boxes(merged, min_thickness):
+    """The flat-capped buffer of each kept centre line (sideface_data.py:18-19, 78) as its bounds."""
+    out = []
+    for x0, y0, x1, y1, width, kind in merged:
+        if width >= min_thickness:
+            half = width / 2
+            out.append([x0, y0 - half, x1, y0 + half] if kind == 1 else [x0 - half, y0, x0 + half, y1])
+    return out
+
+
+def view_faces(segments, views, view):
+    """Face bounds [n, 4] of one view in the defined candidate order (xmin, ymin, xmax, ymax, smallest half-edge), and flags."""
+    seg = np.asarray(segments, dtype=np.float64).reshape(-1, 4) + 0.0          # -0.0 -> 0.0: nodes compare by value
+    views = np.asarray(views, dtype=np.int64).reshape(-1)
+    if len(views) != len(seg):
+        raise ValueError(f"{len(views)} views for {len(seg)} segments")
+    pick = [i for i in range(len(seg)) if views[i] == view and (seg[i, 0] != seg[i, 2] or seg[i, 1] != seg[i, 3])]
+    if pick and not (np.isfinite(seg[pick]).all() and seg[pick].min() >= -1.0 and seg[pick].max() <= 1.0):
+        return np.zeros((0, 4)), EXTRACT_OUT_OF_DOMAIN
+    faces, flags = _trace_faces(seg[pick], pick)
+    return np.asarray([f[:4] for f in sorted(faces)], dtype=np.float64).reshape(-1, 4), flags
+
+
+def extract_sideface_flags(segments, views, max_thickness, min_thickness, merge_tolerance):
+    """``extract_sideface`` that never raises: (faces [n, 4], faceviews [n], flags).  A drawing outside the domain yields no
+    face at all and EXTRACT_OUT_OF_DOMAIN, as the kernel reports it."""
+    boxes, faceviews, flags = [], [], 0
+    for view in range(3):                                          # the reference loops range(3); other views are ignored
+        faces, f = view_faces(segments, views, view)
+        flags |= f
+        cands = parse_sideface_candidates(faces, max_thickness)
+        if cands:
+            got = sideface_boxes(merge_colinear_sidefaces(cands, merge_tolerance), min_thickness)
+            boxes += got
+            faceviews += [view] * len(got)
+    if flags & EXTRACT_OUT_OF_DOMAIN:
+        boxes, faceviews = [], []
+    return np.asarray(boxes, dtype=np.float64).reshape(-1, 4), np.asarray(faceviews, dtype=np.int64), flags
+
+
+def extract_sideface(segments, views, max_thickness, min_thickness, merge_tolerance):
+    """reference SidefaceDataset.extract_sideface (sideface_data.py:109-135) for two-point axis-aligned segments
+    ``segments`` [n, 4] (x0 y0 x1 y1) with their ``views``: per view 0, 1, 2 the bounded faces of the drawing (dangles
+    pruned, faces traced with the face on the left, cut edges removed), thin faces as centre lines, collinear ones merged
+    in the defined order, buffered back to boxes.  Returns (faces float64 [n, 4], faceviews int64 [n]).  Raises ValueError
+    outside the domain.  DESIGN.md section 26."""
+    faces, faceviews, flags = extract_sideface_flags(segments, views, max_thickness, min_thickness, merge_tolerance)
+    if flags & EXTRACT_OUT_OF_DOMAIN:
+        raise ValueError(_DOMAIN)
+    return faces, faceviews
+
+
+def two_point_segments(svgs, where=""):
+    """``svgs`` of an info file -> float [n, 4]; a polyline is refused."""
+    seg = np.zeros((len(svgs), 4))
+    for i, svg in enumerate(svgs):
+        pts = _segment_points(svg)
+        if len(pts) != 2:
+            raise ValueError(f"{where}svg {i} has {len(pts)} vertices; {_DOMAIN}")
+        seg[i] = pts.reshape(4)
+    return seg
+
+
 class _TokenisedDataset(torch.utils.data.Dataset):
     def __init__(self, root, info_files, token, cfg, augmentation=False):
         self.root = root
@@ -190,8 +403,47 @@ class LineDataset(_TokenisedDataset):
         return {"name": info["name"], **inputs, **outputs}
 
 
+def sideface_thresholds(cfg):
+    """(max_thickness, min_thickness, merge_tolerance) of a ``DATA`` node: MAX_THICKNESS, MIN_THICKNESS, MERGE_TOLERANCE over
+    SCALE (reference sideface_data.py:102-104), as Python floats."""
+    get = (lambda k: cfg.get(k, None)) if hasattr(cfg, "get") else (lambda k: getattr(cfg, k, None))
+    vals = {k: get(k) for k in ("MAX_THICKNESS", "MIN_THICKNESS", "MERGE_TOLERANCE", "SCALE")}
+    missing = [k for k, v in vals.items() if v is None]
+    if missing:
+        raise ValueError(f"side-face extraction needs DATA.{', DATA.'.join(missing)} (configs/train_sideface.yaml)")
+    return tuple(vals[k] / vals["SCALE"] for k in ("MAX_THICKNESS", "MIN_THICKNESS", "MERGE_TOLERANCE"))
+
+
+EXTRACT_MODES = ("auto", "true", "false")
+
+
+def extract_mode(value):
+    """``DATA.EXTRACT_SIDEFACE``: ``auto`` (default; extract where a file stores no faces), ``true`` (always extract from
+    ``svgs`` - what augmentation needs), ``false`` (stored faces only).  YAML booleans are accepted for true / false."""
+    if value is None:
+        return "auto"
+    if isinstance(value, bool):
+        return "true" if value else "false"
+    if isinstance(value, str) and value.lower() in EXTRACT_MODES:
+        return value.lower()
+    raise ValueError(f"DATA.EXTRACT_SIDEFACE must be one of {EXTRACT_MODES}, got {value!r}")
+
+
 class SidefaceDataset(_TokenisedDataset):
-    """reference plankassembly/datasets/sideface_data.py:85-254 minus the geometry (module docstring)."""
+    """reference plankassembly/datasets/sideface_data.py:85-254.  ``extract`` (default: ``DATA.EXTRACT_SIDEFACE``, else
+    ``auto``): see ``extract_mode``.  The input is extracted from ``svgs`` when the mode says so, and - mode ``auto`` or
+    ``true`` - whenever the sample is augmented (the noise acts on the lines, sideface_data.py:233-245)."""
+
+    def __init__(self, root, info_files, token, cfg, augmentation=False, extract=None):
+        super().__init__(root, info_files, token, cfg, augmentation)
+        if extract is None:
+            extract = cfg.get("EXTRACT_SIDEFACE", None) if hasattr(cfg, "get") else getattr(cfg, "EXTRACT_SIDEFACE", None)
+        self.extract = extract_mode(extract)
+        self._cfg = cfg
+
+    def extract_sideface(self, segments, views):
+        """(faces, faceviews, flags) under the thresholds of the ``DATA`` node; never raises on the geometry."""
+        return extract_sideface_flags(segments, views, *sideface_thresholds(self._cfg))
 
     def prepare_input_sequence(self, faces, views):
         if len(faces) != 0:
@@ -205,13 +457,28 @@ class SidefaceDataset(_TokenisedDataset):
 
     def __getitem__(self, index):
         info = self._read_info(index)
-        if "faces" not in info or "faceviews" not in info:
+        stored = "faces" in info and "faceviews" in info
+        if self.extract == "false" and not stored:
             raise NotImplementedError(
-                "side-face extraction from the line drawing (reference sideface_data.py:21-135, shapely polygonize + "
-                "STRtree) is outside this package; store the extracted boxes in the info file as 'faces' "
-                "[[xmin, ymin, xmax, ymax]] and 'faceviews' [0|1|2]")
+                "this info file stores no side faces ('faces' [[xmin, ymin, xmax, ymax]] and 'faceviews' [0|1|2]) and "
+                "DATA.EXTRACT_SIDEFACE is false; 'auto' or 'true' extracts them from the line drawing ('svgs')")
         planks = np.array(info["coords"]).flatten()
         attach = np.array(info["attach"]).flatten()
-        inputs = self.prepare_input_sequence(np.array(info["faces"], dtype="float").reshape(-1, 4), info["faceviews"])
+        where = f"{self.info_files[index]}: "
+        faces, faceviews = [], []
+        if (self.augmentation and self.extract != "false" and len(info.get("svgs") or [])
+                and np.random.random() < self.aug_ratio):
+            views = list(np.array(info["views"], dtype="long"))
+            segs, noisy_views, _ = add_noise([_segment_points(s) for s in info["svgs"]], views, views, self.noise_ratio,
+                                             self.noise_length)
+            faces, faceviews, _ = self.extract_sideface(np.array(segs, dtype=float).reshape(-1, 4), noisy_views)
+        if len(faces) == 0:                                        # not augmented, or the noise left no face
+            if stored and self.extract != "true":
+                faces, faceviews = np.array(info["faces"], dtype="float").reshape(-1, 4), info["faceviews"]
+            else:
+                faces, faceviews, flags = self.extract_sideface(two_point_segments(info["svgs"], where), info["views"])
+                if flags & EXTRACT_OUT_OF_DOMAIN:
+                    raise ValueError(where + _DOMAIN)
+        inputs = self.prepare_input_sequence(faces, faceviews)
         outputs = self.prepare_output_sequence(planks, attach)
         return {"name": info["name"], **inputs, **outputs}

@@ -13,6 +13,10 @@ What differs from the CPU classes, all of it in the augmentation (``LineDataset`
     the position in the batch or the number of ranks, and no two runs of the CPU class can be compared draw for draw;
   - straight two-point segments only (all the info files hold, ``datasets.py`` docstring): ``pack_infos`` refuses a
     polyline and points to ``LineDataset``;
+  - side faces: with ``pack_infos(..., "sideface", extract=True)`` the LINES are packed and
+    ``pa_tokenise_sideface_drawings`` (csrc/sideface.h) extracts the side faces of every batch row on the device - faces
+    of each view, centre lines, merge, boxes - then tokenises them; such a set can be augmented (the noise acts on the
+    lines) and returns ``_extract_flags``; stored ``faces`` (the default) are tokenised as they are and never augmented;
   - a drawing whose every line the noise deleted tokenises as the empty case ``[END, PAD, ...]`` - ``LineDataset`` (and
     the reference) raise there, a kernel cannot; ``num_select`` is capped at the number of lines (``NOISE_RATIO`` > 1
     raises in numpy's ``choice``), and ``NOISE_RATIO`` 0 leaves a drawing as it is (numpy's ``randint(1, 1)`` raises).
@@ -27,26 +31,56 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .datasets import _segment_points
+from .datasets import (EXTRACT_OUT_OF_DOMAIN, _DOMAIN, _segment_points, extract_sideface_flags, sideface_thresholds,
+                       two_point_segments, view_faces)
 
 MAX_LINES = 1024                      # include/plank_hip.h PA_TOKENISE_MAX_LINES: the kernel's LDS key array
 _SIDEFACE_MISSING = (
-    "side-face extraction from the line drawing (reference sideface_data.py:21-135, shapely polygonize + "
-    "STRtree) is outside this package; store the extracted boxes in the info file as 'faces' "
-    "[[xmin, ymin, xmax, ymax]] and 'faceviews' [0|1|2]")
+    "this info file stores no side faces ('faces' [[xmin, ymin, xmax, ymax]] and 'faceviews' [0|1|2]); side-face extraction "
+    "from the line drawing (reference sideface_data.py:21-135) is pack_infos(..., 'sideface', extract=True) / "
+    "DATA.EXTRACT_SIDEFACE auto or true")
 
 
 def _in_unit_range(a):
     return a.size == 0 or (np.isfinite(a).all() and a.min() >= -1.0 and a.max() <= 1.0)
 
 
-def pack_infos(root, info_files, kind="line"):
+def sideface_count(seg, view, data_cfg, where=""):
+    """The number of side faces ``extract_sideface`` finds in one drawing's clean lines, checked against the row: what
+    the host knows of an extracting set without augmentation.  Raises ValueError naming ``where`` beyond (S - 1) / 4."""
+    faces, _, flags = extract_sideface_flags(seg, view, *sideface_thresholds(data_cfg))
+    if flags & EXTRACT_OUT_OF_DOMAIN:
+        raise ValueError(f"{where}{_DOMAIN}")
+    room = (int(data_cfg.MAX_INPUT_LENGTH) - 2) // 4
+    if len(faces) > room:
+        raise ValueError(f"{where}{len(faces)} side faces ({4 * len(faces)} input tokens) do not fit "
+                         f"MAX_INPUT_LENGTH={int(data_cfg.MAX_INPUT_LENGTH)} ({room} faces)")
+    return len(faces)
+
+
+def pack_infos(root, info_files, kind="line", extract=False, data_cfg=None):
     """Read every info JSON once -> dict of numpy arrays, CSR over the drawings: ``line_off`` int32 [N+1], ``box`` f64
     [L,4] (``lines`` / ``faces`` as stored), ``seg`` f64 [L,4] (x0 y0 x1 y1 of ``svgs``; lines only, None when the files
     carry no svgs), ``view`` u8 [L], ``type`` u8 [L] (lines only), ``plank_off`` int32 [N+1], ``coords`` f64 [P,6],
-    ``attach`` int32 [P,6], ``names`` and ``files`` (lists), ``kind``."""
+    ``attach`` int32 [P,6], ``names`` and ``files`` (lists), ``kind``.
+
+    ``kind="sideface"`` with ``extract=True``: ``seg`` / ``view`` / ``line_off`` hold the LINES of
+    ``svgs`` (``box`` their bounds) and the side faces are extracted on the device, batch by batch; every drawing is
+    checked against the extraction's domain here, by file name.  With ``data_cfg`` (the ``DATA`` node) the extraction
+    also runs once per drawing on the host: ``n_faces`` int64 [N], checked against the row; without it
+    ``DeviceDrawings`` does that.  ``extract="auto"``: True unless every file stores ``faces`` / ``faceviews``."""
     if kind not in ("line", "sideface"):
         raise ValueError(f"kind must be 'line' or 'sideface', got {kind!r}")
+    if extract == "auto":
+        def stored(fn):
+            with open(os.path.join(root, fn), "r") as f:
+                info = json.loads(f.read())
+            return "faces" in info and "faceviews" in info
+        extract = kind == "sideface" and not all(stored(fn) for fn in info_files)
+    if extract and kind != "sideface":
+        raise ValueError("extract=True is for kind='sideface'")
+    if extract:
+        return _pack_extracting(root, info_files, data_cfg)
     line_off, plank_off = [0], [0]
     box, seg, view, typ, coords, attach, names = [], [], [], [], [], [], []
     have_seg = kind == "line"
@@ -104,6 +138,47 @@ def pack_infos(root, info_files, kind="line"):
     return out
 
 
+def _pack_extracting(root, info_files, data_cfg):
+    line_off, plank_off = [0], [0]
+    seg, view, coords, attach, names, n_faces = [], [], [], [], [], []
+    for fn in info_files:
+        with open(os.path.join(root, fn), "r") as f:
+            info = json.loads(f.read())
+        s = two_point_segments(info.get("svgs") or [], f"{fn}: ")
+        v = np.array(info["views"], dtype="long").reshape(-1)
+        if len(v) != len(s) or (len(v) and (v.min() < 0 or v.max() > 254)):
+            raise ValueError(f"{fn}: {len(v)} views in [0, 254] expected for {len(s)} svgs")
+        if len(s) > MAX_LINES:
+            raise ValueError(f"{fn}: {len(s)} lines, the extraction kernel holds at most {MAX_LINES}")
+        if any(view_faces(s, v, k)[1] & EXTRACT_OUT_OF_DOMAIN for k in range(3)):
+            raise ValueError(f"{fn}: {_DOMAIN}")
+        c = np.array(info["coords"], dtype="float").reshape(-1)
+        a = np.array(info["attach"], dtype="long").reshape(-1)
+        if len(c) % 6 or len(a) != len(c):
+            raise ValueError(f"{fn}: coords ({len(c)} values) and attach ({len(a)}) must hold 6 values per plank")
+        if not _in_unit_range(c):
+            raise ValueError(f"{fn}: coordinates outside [-1, 1]")
+        if data_cfg is not None:
+            n_faces.append(sideface_count(s, v, data_cfg, f"{fn}: "))
+        seg.append(s); view.append(v.astype(np.uint8)); coords.append(c.reshape(-1, 6)); attach.append(a.reshape(-1, 6))
+        line_off.append(line_off[-1] + len(s)); plank_off.append(plank_off[-1] + len(c) // 6)
+        names.append(info["name"])
+
+    def cat(parts, width, dtype):
+        return np.concatenate(parts).astype(dtype) if parts else np.zeros((0, width) if width else (0,), dtype)
+
+    segs = cat(seg, 4, np.float64)
+    box = np.stack([np.minimum(segs[:, 0], segs[:, 2]), np.minimum(segs[:, 1], segs[:, 3]),
+                    np.maximum(segs[:, 0], segs[:, 2]), np.maximum(segs[:, 1], segs[:, 3])], axis=1)
+    out = {"kind": "sideface", "extract": True, "names": names, "files": list(info_files),
+           "line_off": np.asarray(line_off, np.int32), "box": box, "seg": segs, "view": cat(view, 0, np.uint8),
+           "plank_off": np.asarray(plank_off, np.int32), "coords": cat(coords, 6, np.float64),
+           "attach": cat(attach, 6, np.int32)}
+    if data_cfg is not None:
+        out["n_faces"] = np.asarray(n_faces, np.int64)
+    return out
+
+
 def _get(cfg, key, default):
     return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
 
@@ -129,8 +204,18 @@ class DeviceDrawings:
         self.n_lines = np.diff(packed["line_off"]).astype(np.int64)
         n_planks = np.diff(packed["plank_off"]).astype(np.int64)
         files = packed.get("files") or self.names
-        for i in np.nonzero(4 * self.n_lines + 1 > self.max_input_length - 1)[0]:
-            raise ValueError(f"{files[i]}: {4 * self.n_lines[i]} input tokens do not fit MAX_INPUT_LENGTH={self.max_input_length}")
+        self.extract = bool(packed.get("extract", False))              # side faces from the lines, on the device (section 26)
+        self.n_prims = self.n_lines                                    # primitives in a row without augmentation
+        if self.extract:
+            self.thresholds = tuple(float(t) for t in sideface_thresholds(data_cfg))
+            if packed.get("n_faces") is not None:
+                self.n_prims = np.asarray(packed["n_faces"], dtype=np.int64)
+            else:
+                off = packed["line_off"]
+                self.n_prims = np.asarray([sideface_count(packed["seg"][off[i]:off[i + 1]], packed["view"][off[i]:off[i + 1]],
+                                                          data_cfg, f"{files[i]}: ") for i in range(len(self.names))], np.int64)
+        for i in np.nonzero(4 * self.n_prims + 1 > self.max_input_length - 1)[0]:
+            raise ValueError(f"{files[i]}: {4 * self.n_prims[i]} input tokens do not fit MAX_INPUT_LENGTH={self.max_input_length}")
         for i in np.nonzero(self.n_lines > MAX_LINES)[0]:
             raise ValueError(f"{files[i]}: {self.n_lines[i]} lines, the tokenise kernel sorts at most {MAX_LINES}")
         for i in np.nonzero(6 * n_planks + 1 > self.max_output_length)[0]:
@@ -152,8 +237,9 @@ class DeviceDrawings:
         return len(self.names)
 
     def augments(self, augmentation):
-        """Whether ``batch(..., augmentation)`` draws noise at all (lines only, ``AUG_RATIO`` > 0)."""
-        return bool(augmentation) and self.kind == "line" and self.aug_ratio > 0.0
+        """Whether ``batch(..., augmentation)`` draws noise at all: lines, or side faces extracted from the lines, with
+        ``AUG_RATIO`` > 0 (stored side faces cannot be augmented - the noise acts on the lines)."""
+        return bool(augmentation) and (self.kind == "line" or self.extract) and self.aug_ratio > 0.0
 
     def batch(self, index, epoch=0, augmentation=False, host_index=None, seed=None):
         """``index``: int32 [B] on the device, drawing numbers.  One launch on the current stream -> the collated batch
@@ -184,6 +270,8 @@ class DeviceDrawings:
         out["output_label"] = torch.empty(B, T, dtype=torch.int64, device=dev)
         out["output_mask"] = torch.empty(B, T, dtype=torch.bool, device=dev)
         n_tokens = torch.empty(B, dtype=torch.int32, device=dev)
+        if self.extract:
+            return self._extract_batch(out, index, host_index, n_tokens, aug, epoch, seed)
         L.check(L.lib().pa_tokenise_drawings(
             L.ptr(self._line_off), L.ptr(self._box), L.ptr(self._seg), L.ptr(self._view), L.ptr(self._type),
             L.ptr(self._plank_off), L.ptr(self._coords), L.ptr(self._attach), len(self), L.ptr(index), B, S, T,
@@ -195,6 +283,31 @@ class DeviceDrawings:
         out["_n_tokens"] = n_tokens
         if not aug:
             out["_n_valid"] = int((4 * self.n_lines[host_index] + 1).sum())
+        return out
+
+    def _extract_batch(self, out, index, host_index, n_tokens, aug, epoch, seed):
+        """The extracting sideface set: one launch of ``pa_tokenise_sideface_drawings``.  Beside the batch: ``_extract_flags``
+        int32 [B] (include/plank_hip.h PA_EXTRACT_*), ``_faces`` f64 [B, F, 4] / ``_faceviews`` u8 [B, F] / ``_n_faces`` int32
+        [B]: the merged boxes before quantisation, in the order of the row's tokens."""
+        B, S, T, dev = index.numel(), self.max_input_length - 1, self.max_output_length, self.device
+        F = (S - 1) // 4
+        flags = torch.empty(B, dtype=torch.int32, device=dev)
+        faces = torch.empty(B, max(F, 1), 4, dtype=torch.float64, device=dev)
+        faceviews = torch.empty(B, max(F, 1), dtype=torch.uint8, device=dev)
+        n_faces = torch.empty(B, dtype=torch.int32, device=dev)
+        L.check(L.lib().pa_tokenise_sideface_drawings(
+            L.ptr(self._line_off), None, L.ptr(self._seg), L.ptr(self._view), None,
+            L.ptr(self._plank_off), L.ptr(self._coords), L.ptr(self._attach), len(self), L.ptr(index), B, S, T,
+            self.num_bits, int(self.token.END), int(self.token.PAD), self.vocab_size, 0, int(aug),
+            self.aug_ratio, self.noise_ratio, self.noise_length, int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+            L.ptr(out["input_value"]), L.ptr(out["input_pos"]), L.ptr(out["input_coord"]), L.ptr(out["input_view"]),
+            None, L.ptr(out["input_mask"]), L.ptr(out["output_value"]), L.ptr(out["output_label"]),
+            L.ptr(out["output_mask"]), L.ptr(n_tokens), *self.thresholds, L.ptr(faces), L.ptr(faceviews), L.ptr(n_faces),
+            L.ptr(flags), L.stream()), "pa_tokenise_sideface_drawings")
+        out["_n_tokens"], out["_extract_flags"] = n_tokens, flags
+        out["_faces"], out["_faceviews"], out["_n_faces"] = faces[:, :F], faceviews[:, :F], n_faces
+        if not aug:
+            out["_n_valid"] = int((4 * self.n_prims[host_index] + 1).sum())
         return out
 
 

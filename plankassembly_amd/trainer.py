@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from .config import CfgNode, load_cli_config
 from .data import SynthSpec, synth_sample
-from .datasets import LineDataset, SidefaceDataset, parse_splits_list  # noqa: F401  (parse_splits_list re-exported)
+from .datasets import LineDataset, SidefaceDataset, extract_mode, parse_splits_list  # noqa: F401  (parse_splits_list re-exported)
 from .metric import DevicePlankScorer, PlankScorer, planks_of_row, valid_planks
 from .models import build_model
 
@@ -87,6 +87,7 @@ class Trainer(torch.nn.Module):
         self.optimizer_kwargs = {}             # FusedAdam's guard arguments, from the `trainer:` block (optimizer_options)
         self.recipe = recipe_options(self.hparams_dict)  # weight decay / LR schedule / EMA keys of the hparams, validated
         self.seq_train = seq_train_options(self.hparams_dict)   # the SEQ_TRAIN block, validated; None: plain NLL steps only
+        self.extract_sideface = extract_option(self.hparams_dict)      # DATA.EXTRACT_SIDEFACE, validated (sideface kind only)
         self._train_reward = None
 
     # ------------------------------------------------------------------ logging (self.log of Lightning)
@@ -126,7 +127,9 @@ class Trainer(torch.nn.Module):
             dev = torch.device("cuda", torch.cuda.current_device())
         cache = self.__dict__.setdefault("_device_drawings", {})       # a split is read and uploaded once, not per validation
         if (split_key, dev) not in cache:
-            packed = pack_infos(str(self.cfg.get("ROOT", "")), parse_splits_list(self.cfg.get(split_key)), self.device_kind)
+            extract = {"auto": "auto", "true": True, "false": False}[self.extract_sideface] if self.device_kind == "sideface" else False
+            packed = pack_infos(str(self.cfg.get("ROOT", "")), parse_splits_list(self.cfg.get(split_key)), self.device_kind,
+                                extract=extract, data_cfg=self.cfg.DATA if extract else None)
             cache[split_key, dev] = DeviceDrawings(packed, self.cfg.TOKEN, self.cfg.DATA, dev)
         return DeviceLoader(cache[split_key, dev], self.cfg.BATCH_SIZE, shuffle, drop_last, augmentation, seed)
 
@@ -513,6 +516,14 @@ def seq_train_options(hparams):
     if blk.get("SHARE_ENCODER") is not None:
         step["share_encoder"] = _bool("SHARE_ENCODER", blk["SHARE_ENCODER"])
     return {"step": step, "start_step": start, "seed": seed}
+
+
+def extract_option(hparams):
+    """``DATA.EXTRACT_SIDEFACE`` of the hparams, validated -> ``auto`` (default: side faces are extracted from the line drawing
+    where the info files store none), ``true`` (always extracted from ``svgs`` - what train-time augmentation needs) or ``false``
+    (stored ``faces`` only).  Read by the sideface kind's CPU dataset and device dataset alike."""
+    data = hparams.get("DATA") or {}
+    return extract_mode(data.get("EXTRACT_SIDEFACE") if hasattr(data, "get") else None)
 
 
 def seq_train_seed(seed, global_step, rank):

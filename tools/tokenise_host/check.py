@@ -27,6 +27,7 @@ def stage():
     os.makedirs(os.path.join(tmp, "a", "b"))
     os.makedirs(os.path.join(tmp, "include"))
     shutil.copy(os.path.join(REPO, "plankassembly_amd", "csrc", "tokenise.hip"), os.path.join(tmp, "a", "b", "tokenise.cpp"))
+    shutil.copy(os.path.join(REPO, "plankassembly_amd", "csrc", "sideface.h"), os.path.join(tmp, "a", "b", "sideface.h"))
     shutil.copy(os.path.join(HERE, "pa_device.h"), os.path.join(tmp, "a", "b", "pa_device.h"))
     shutil.copy(os.path.join(REPO, "include", "plank_hip.h"), os.path.join(tmp, "include", "plank_hip.h"))
     return tmp
