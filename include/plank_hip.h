@@ -1012,6 +1012,49 @@ int pa_tokenise_sideface_drawings(const int32_t* line_off, const double* box, co
                                   double* faces_out, uint8_t* faceviews_out, int32_t* n_faces_out, int32_t* flags_out,
                                   void* stream);
 
+/* ---- the three-view line drawing from the planks (csrc/render.h, compiled into csrc/tokenise.hip) ----
+ * pa_tokenise_drawings for drawings that are not stored: one launch, one block of 256 threads per batch row, renders the row's
+ * planks as the reference's dataset/data_utils.py:49-205 does (build :49-60 - plank 0 skipped; project :63-101 - visible and
+ * hidden edges of the three views on the projectors of :15-25, the 2D point [X, -Y] of :104-110; split_lines_on_crossing_points
+ * :113-150, split_lines_on_endpoints and remove_overlapping_lines :153-205) for axis-aligned boxes seen along the axes, by the
+ * definition of DESIGN.md section 27 - float64 compares only - then applies the line noise of pa_tokenise_drawings (same draws,
+ * keyed by the canonical line number) and tokenises.  NOT pinned to OpenCASCADE / GEOS: the on-boundary and equal-depth
+ * conventions and the orientation of the views are section 27's reading of the reference and unverified against it.
+ *   plank_off int32 [N+1], coords f64 [P][6], attach int32 [P][6], index int32 [B], S, T, n_bits, tokens, vocab, with_type,
+ *   augmentation .. epoch and the ten outputs in_value .. n_tokens: as pa_tokenise_drawings.  out_value / out_label / out_mask
+ *   may be NULL together (no decoder rows; attach is then not read);
+ *   plank_cnt int32 [N] or NULL: the planks of drawing d are plank_cnt[d] rows from plank_off[d] (NULL: up to plank_off[d + 1]);
+ *   max_planks: the largest plank count of any drawing, as the host knows it; above PA_RENDER_MAX_PLANKS: PA_ESHAPE and nothing
+ *     is launched.  (A row that holds more all the same is cut at the cap and flagged PA_RENDER_TRUNCATED, never a fault.)
+ *   skip_first != 0: plank 0 of each drawing (the overall bounding box) is not drawn;
+ *   lines_out f64 [B][F][4] (xmin ymin xmax ymax), views_out / types_out uint8 [B][F], n_lines_out int32 [B] (each may be NULL),
+ *     F = (S - 1) / 4: the rendered lines before the noise, in the canonical order (view, xmin, ymin, xmax, ymax) as doubles, zero
+ *     behind the row's count; type 0 visible, 1 hidden;
+ *   flags_out int32 [B] (required): PA_RENDER_* bits.
+ * Views: 0 (x, -z) smaller y nearer; 1 (x, -y) larger z nearer; 2 (y, -z) larger x nearer; -0.0 becomes 0.0.  Lines: the noded
+ * arrangement of the near- and far-face rectangle edges of every box; a segment is hidden iff the cells on both of its sides are
+ * covered by boxes whose near face is strictly nearer than the nearest edge covering it.  A coordinate that is not finite or not
+ * in [-1, 1]: the row renders nothing, PA_RENDER_OUT_OF_DOMAIN; a box with lo >= hi on an axis is dropped, PA_RENDER_DEGENERATE;
+ * more than F lines: those that sort first in the order of the row's tokens stay (renumbered in canonical order),
+ * PA_RENDER_TRUNCATED.  A rendering with more lines than the sort keys hold (PA_TOKENISE_MAX_LINES) gets PA_RENDER_TRUNCATED |
+ * PA_RENDER_OVERFLOW: the first PA_TOKENISE_MAX_LINES lines in the kernel's emission order (view, horizontal before vertical,
+ * grid line, position) are taken before that cut, so the kept lines are NOT those of the defined order - the one flag that marks
+ * a row whose lines the definition does not give.
+ * (S - 1) / 4 above PA_TOKENISE_MAX_LINES: PA_ESHAPE. */
+#define PA_RENDER_MAX_PLANKS 32
+#define PA_RENDER_OUT_OF_DOMAIN 1
+#define PA_RENDER_TRUNCATED 2
+#define PA_RENDER_DEGENERATE 8
+#define PA_RENDER_OVERFLOW 16
+int pa_render_drawings(const int32_t* plank_off, const int32_t* plank_cnt, const double* coords, const int32_t* attach,
+                       int32_t N, const int32_t* index, int32_t B, int32_t max_planks, int32_t skip_first, int32_t S, int32_t T,
+                       int32_t n_bits, int32_t tok_end, int32_t tok_pad, int32_t vocab, int32_t with_type, int32_t augmentation,
+                       double aug_ratio, double noise_ratio, double noise_length, uint32_t seed, uint32_t epoch,
+                       int64_t* in_value, int64_t* in_pos, int64_t* in_coord, int64_t* in_view, int64_t* in_type,
+                       uint8_t* in_mask, int64_t* out_value, int64_t* out_label, uint8_t* out_mask, int32_t* n_tokens,
+                       double* lines_out, uint8_t* views_out, uint8_t* types_out, int32_t* n_lines_out, int32_t* flags_out,
+                       void* stream);
+
 /* ---- plank matching (csrc/match.hip, core csrc/match_core.h; plankassembly_amd/metric.py DevicePlankScorer) ----
  * One launch, one wave per pair: two token rows compared as sets of planks.  Restates plankassembly_amd/metric.py
  * `pairwise_iou_3d` and `HungarianMatcher` (reference third_party/matcher.py:15-27 IoU, :29-61 cost -1 where IoU > threshold

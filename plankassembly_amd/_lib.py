@@ -292,6 +292,8 @@ def lib():
                                          P, P, P, P, P, P, P, P, P, P, P]),
             "pa_tokenise_sideface_drawings": (I, [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, D, D, D, U, U,
                                                   P, P, P, P, P, P, P, P, P, P, D, D, D, P, P, P, P, P]),
+            "pa_render_drawings": (I, [P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, I, I, D, D, D, U, U,
+                                       P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
             "pa_plank_match": (I, [P, I64, I, P, I64, I, P, P, I, I, I, I, I, D, P, P]),
             "pa_seq_batch_args_bytes": (I64, []),
             "pa_sequence_batch": (I, [P, P]),

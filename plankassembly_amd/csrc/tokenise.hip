@@ -238,6 +238,7 @@ __global__ __launch_bounds__(TK_THREADS) void tokenise_kernel(TkArgs a) {
 }
 
 #include "sideface.h"                                  // sideface_kernel and its launch arguments, on the stages above
+#include "render.h"                                    // render_kernel: the drawing from the planks, on the same stages
 
 }  // namespace
 
@@ -301,5 +302,38 @@ extern "C" int pa_tokenise_sideface_drawings(const int32_t* line_off, const doub
     s.max_thickness = max_thickness; s.min_thickness = min_thickness; s.merge_tolerance = merge_tolerance;
     s.faces_out = faces_out; s.faceviews_out = faceviews_out; s.n_faces_out = n_faces_out; s.flags_out = flags_out;
     PA_LAUNCH(sideface_kernel, dim3(B), dim3(TK_THREADS), 0, ST(stream), s);
+    return 0;
+}
+
+extern "C" int pa_render_drawings(const int32_t* plank_off, const int32_t* plank_cnt, const double* coords, const int32_t* attach,
+                                  int32_t N, const int32_t* index, int32_t B, int32_t max_planks, int32_t skip_first, int32_t S,
+                                  int32_t T, int32_t n_bits, int32_t tok_end, int32_t tok_pad, int32_t vocab, int32_t with_type,
+                                  int32_t augmentation, double aug_ratio, double noise_ratio, double noise_length, uint32_t seed,
+                                  uint32_t epoch, int64_t* in_value, int64_t* in_pos, int64_t* in_coord, int64_t* in_view,
+                                  int64_t* in_type, uint8_t* in_mask, int64_t* out_value, int64_t* out_label, uint8_t* out_mask,
+                                  int32_t* n_tokens, double* lines_out, uint8_t* views_out, uint8_t* types_out,
+                                  int32_t* n_lines_out, int32_t* flags_out, void* stream) {
+    if (!plank_off || !coords || !index || !in_value || !in_pos || !in_coord || !in_view || !in_mask || !n_tokens || !flags_out)
+        return PA_EINVAL;
+    if (N <= 0 || B <= 0 || S <= 0 || max_planks < 0) return PA_EINVAL;
+    if (with_type && !in_type) return PA_EINVAL;
+    const bool outputs = out_value || out_label || out_mask;
+    if (outputs && (!out_value || !out_label || !out_mask || !attach || T <= 0)) return PA_EINVAL;
+    if (n_bits < 1 || n_bits > TK_Q_BITS) return PA_ESHAPE;
+    if ((S - 1) / 4 > TK_MAX_LINES) return PA_ESHAPE;                        // the row cannot hold more lines than the sort keys
+    if (max_planks > PA_RENDER_MAX_PLANKS) return PA_ESHAPE;                 // nothing is launched, nothing written
+    if (!(aug_ratio >= 0.0) || !(noise_ratio >= 0.0) || !(noise_length >= 0.0)) return PA_EINVAL;
+    RdArgs r;
+    TkArgs& a = r.t;
+    a.line_off = nullptr; a.box = nullptr; a.seg = nullptr; a.view = nullptr; a.type = nullptr;
+    a.plank_off = plank_off; a.coords = coords; a.attach = attach; a.index = index;
+    a.N = N; a.S = S; a.T = T; a.n_bits = n_bits; a.tok_end = tok_end; a.tok_pad = tok_pad; a.vocab = vocab;
+    a.with_type = with_type; a.augment = augmentation;
+    a.aug_ratio = aug_ratio; a.noise_ratio = noise_ratio; a.noise_length = noise_length; a.seed = seed; a.epoch = epoch;
+    a.in_value = in_value; a.in_pos = in_pos; a.in_coord = in_coord; a.in_view = in_view; a.in_type = in_type;
+    a.in_mask = in_mask; a.out_value = outputs ? out_value : nullptr; a.out_label = out_label; a.out_mask = out_mask; a.n_tokens = n_tokens;
+    r.plank_cnt = plank_cnt; r.skip_first = skip_first;
+    r.lines_out = lines_out; r.views_out = views_out; r.types_out = types_out; r.n_lines_out = n_lines_out; r.flags_out = flags_out;
+    PA_LAUNCH(render_kernel, dim3(B), dim3(TK_THREADS), 0, ST(stream), r);
     return 0;
 }

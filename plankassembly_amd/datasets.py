@@ -17,6 +17,15 @@ that meet at end points - as a face trace with comparisons only (``extract_sidef
 semantics, csrc/sideface.h runs them on the device).  It is pinned to an independent flood-fill oracle
 (tests/sideface_reference.py), not to GEOS.  ``SidefaceDataset`` extracts when the info file stores no ``faces`` /
 ``faceviews`` and whenever it augments; stored faces without augmentation are read as before.
+
+* ``render_drawing`` / ``render_info``                     reference dataset/data_utils.py:49-205, prepare_info.py:36-70
+
+The drawing itself (PythonOCC hidden-line removal of a compound of boxes, shapely noding) is restated for what the planks are -
+axis-aligned boxes seen along the axes - as interval algebra on the coordinate values (``render_drawing``; section 27 fixes the
+semantics, csrc/render.h runs them on the device).  It is pinned to an independent raster oracle (tests/render_reference.py), not
+to OpenCASCADE / GEOS.  ``LineDataset`` renders on access where the info file stores no ``lines``, ``SidefaceDataset``
+where it stores neither ``faces`` / ``faceviews`` nor ``svgs`` (``DATA.RENDER_DRAWINGS``: auto | true | false; ``stores_input``); a
+file that stores what the dataset consumes - boxes without ``svgs``, faces without lines - is read exactly as before.
 """
 from __future__ import annotations
 
@@ -317,7 +326,163 @@ def two_point_segments(svgs, where=""):
     return seg
 
 
+# ------------------------------------------------------------------- the drawing from the planks
+RENDER_OUT_OF_DOMAIN, RENDER_TRUNCATED, RENDER_DEGENERATE = 1, 2, 8
+RENDER_OVERFLOW = 16                   # the device only: more lines than the kernel sorts, the kept ones are not the defined ones
+RENDER_MODES = ("auto", "true", "false")
+# THE view table (reference dataset/data_utils.py:15-25, 104-110; unverified against OpenCASCADE): per view the axis of the 2D
+# point's first coordinate, the axis whose NEGATION is its second coordinate, the depth axis, and the sign that turns a depth
+# coordinate into nearness (larger = nearer to the viewer).
+#   view 0 (f): (x, -z), smaller y nearer;  view 1 (t): (x, -y), larger z nearer;  view 2 (s): (y, -z), larger x nearer
+RENDER_VIEWS = ((0, 2, 1, -1.0), (0, 1, 2, 1.0), (1, 2, 0, 1.0))
+
+
+def render_mode(value):
+    """``DATA.RENDER_DRAWINGS``: ``auto`` (default; render only where a file stores nothing the dataset consumes, ``stores_input``), ``true`` (always render from
+    ``coords``), ``false`` (stored lines only).  YAML booleans are accepted for true / false."""
+    if value is None:
+        return "auto"
+    if isinstance(value, bool):
+        return "true" if value else "false"
+    if isinstance(value, str) and value.lower() in RENDER_MODES:
+        return value.lower()
+    raise ValueError(f"DATA.RENDER_DRAWINGS must be one of {RENDER_MODES}, got {value!r}")
+
+
+def _merge_closed(intervals):
+    """Union of closed intervals; intervals that touch become one."""
+    out = []
+    for lo, hi in sorted(intervals):
+        if out and lo <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], hi)
+        else:
+            out.append([lo, hi])
+    return out
+
+
+def project_planks(coords, skip_first=True):
+    """``coords`` [P, 6] (lo xyz, hi xyz) -> (per view a list of rectangles (u0, v0, u1, v1, near, far) with near / far as
+    nearness, flags).  A plank with lo >= hi on an axis is dropped (RENDER_DEGENERATE); any coordinate that is not finite or
+    not in [-1, 1] puts the whole drawing out of the domain (RENDER_OUT_OF_DOMAIN, no rectangle)."""
+    c = np.asarray(coords, dtype=np.float64).reshape(-1, 6)[1 if skip_first else 0:] + 0.0
+    if c.size and not (np.isfinite(c).all() and c.min() >= -1.0 and c.max() <= 1.0):
+        return [[], [], []], RENDER_OUT_OF_DOMAIN
+    flags, views = 0, [[], [], []]
+    for box in c:
+        lo, hi = [float(v) for v in box[:3]], [float(v) for v in box[3:]]
+        if any(l >= h for l, h in zip(lo, hi)):
+            flags |= RENDER_DEGENERATE
+            continue
+        for view, (ua, va, da, sign) in enumerate(RENDER_VIEWS):
+            d0, d1 = sign * lo[da] + 0.0, sign * hi[da] + 0.0
+            views[view].append((lo[ua], -hi[va] + 0.0, hi[ua], -lo[va] + 0.0, max(d0, d1), min(d0, d1)))
+    return views, flags
+
+
+def _render_view(rects):
+    """The noded arrangement of one view's rectangle edges with the type of every atomic segment: [(xmin, ymin, xmax, ymax,
+    type)].  Interval algebra on the coordinate values: collinear edges are united, a line is cut where a perpendicular line
+    has a point of it, and a segment is hidden (1) unless an edge covering it is visible there."""
+    lines = ({}, {})                                               # [0] horizontal: v -> u intervals; [1] vertical: u -> v intervals
+    for u0, v0, u1, v1, _, _ in rects:
+        for v in (v0, v1):
+            lines[0].setdefault(v, []).append((u0, u1))
+        for u in (u0, u1):
+            lines[1].setdefault(u, []).append((v0, v1))
+    lines = tuple({c: _merge_closed(iv) for c, iv in side.items()} for side in lines)
+    hidden_spans = {}
+
+    def hidden(vertical, c, depth):
+        """The open spans of the line at ``c`` that lie inside the union of the rectangles nearer than ``depth``: where the
+        union covers the strip on both sides of the line."""
+        if (vertical, c, depth) not in hidden_spans:
+            sides = ([], [])
+            for r in rects:
+                if r[4] > depth:
+                    lo, hi, a0, a1 = (r[1], r[3], r[0], r[2]) if vertical else (r[0], r[2], r[1], r[3])
+                    if a0 <= c < a1:
+                        sides[0].append((lo, hi))
+                    if a0 < c <= a1:
+                        sides[1].append((lo, hi))
+            one, two = _merge_closed(sides[0]), _merge_closed(sides[1])
+            hidden_spans[vertical, c, depth] = [(max(p, r), min(q, s)) for p, q in one for r, s in two if max(p, r) < min(q, s)]
+        return hidden_spans[vertical, c, depth]
+
+    out = []
+    for vertical in (0, 1):
+        for c, spans in lines[vertical].items():
+            for lo, hi in spans:
+                cuts = sorted({lo, hi} | {x for x, other in lines[1 - vertical].items()
+                                          if lo < x < hi and any(a <= c <= b for a, b in other)})
+                for a, b in zip(cuts[:-1], cuts[1:]):
+                    visible = False
+                    for r in rects:
+                        rlo, rhi, a0, a1 = (r[1], r[3], r[0], r[2]) if vertical else (r[0], r[2], r[1], r[3])
+                        if c in (a0, a1) and rlo <= a and b <= rhi:          # both faces of the box have this edge
+                            visible = visible or any(not any(p <= a and b <= q for p, q in hidden(vertical, c, depth))
+                                                     for depth in (r[4], r[5]))
+                    out.append((c, a, c, b, int(not visible)) if vertical else (a, c, b, c, int(not visible)))
+    return sorted(out)
+
+
+def render_token_order(lines, views, num_bits):
+    """The order of the row's tokens over lines in canonical order: (view, column 0, column 2, column 1, column 3, number)."""
+    q = quantize_values(np.asarray(lines, dtype=np.float64).reshape(-1, 4), num_bits)
+    return sorted(range(len(q)), key=lambda i: (int(views[i]), int(q[i, 0]), int(q[i, 2]), int(q[i, 1]), int(q[i, 3]), i))
+
+
+def render_drawing(coords, skip_first=True, max_lines=None, num_bits=9):
+    """The three-view line drawing of a plank program: ``coords`` [P, 6] -> (lines float64 [n, 4]
+    bounds xmin ymin xmax ymax, views int64 [n], types int64 [n] (0 visible, 1 hidden), flags) in the canonical order
+    (view, xmin, ymin, xmax, ymax).  Plank 0 (the overall bounding box) is skipped as the reference's ``build`` does.
+    ``max_lines``: the row's capacity; a longer drawing keeps the lines that sort first in the order of the row's tokens
+    (``num_bits`` quantisation) and gets RENDER_TRUNCATED.  Never raises on the geometry."""
+    rects, flags = project_planks(coords, skip_first)
+    rows = [(view,) + seg for view in range(3) for seg in _render_view(rects[view])]
+    lines = np.asarray([r[1:5] for r in rows], dtype=np.float64).reshape(-1, 4)
+    views = np.asarray([r[0] for r in rows], dtype=np.int64)
+    types = np.asarray([r[5] for r in rows], dtype=np.int64)
+    if max_lines is not None and len(lines) > max_lines:
+        keep = sorted(render_token_order(lines, views, num_bits)[:max(int(max_lines), 0)])
+        lines, views, types, flags = lines[keep], views[keep], types[keep], flags | RENDER_TRUNCATED
+    return lines, views, types, flags
+
+
+def render_info(name, coords, attach):
+    """The info dict of the reference's dataset/prepare_info.py:59-70 with the drawing rendered from ``coords``."""
+    lines, views, types, flags = render_drawing(coords)
+    if flags & RENDER_OUT_OF_DOMAIN:
+        raise ValueError(f"{name}: plank coordinates must be finite and in [-1, 1] (DESIGN.md section 27)")
+    return {"name": name, "lines": lines.tolist(), "views": [int(v) for v in views], "types": [int(t) for t in types],
+            "svgs": [json.dumps({"type": "LineString", "coordinates": [[ln[0], ln[1]], [ln[2], ln[3]]]}) for ln in lines.tolist()],
+            "coords": np.asarray(coords, dtype=np.float64).reshape(-1, 6).tolist(),
+            "attach": np.asarray(attach, dtype=np.int64).reshape(-1, 6).tolist()}
+
+
+def stores_input(info, kind):
+    """Whether an info dict stores what the dataset of ``kind`` consumes: ``lines`` for the line kind; ``faces`` / ``faceviews``,
+    or the ``svgs`` to extract them from, for the sideface kind.  (``svgs`` alone is not asked of a line file: a file with
+    boxes only is read as it is and merely cannot be augmented.)"""
+    if kind == "sideface":
+        return ("faces" in info and "faceviews" in info) or "svgs" in info
+    return "lines" in info
+
+
+def rendered(info, mode, kind="line", where=""):
+    """``info`` with ``lines`` / ``views`` / ``types`` / ``svgs`` rendered from its planks where ``mode`` (``render_mode``)
+    says so: ``true`` always (stored ``faces`` are dropped with the stored drawing), ``auto`` only where the file stores
+    nothing the dataset of ``kind`` consumes (``stores_input``), ``false`` never.  A file that stores its input is returned
+    as it is: nothing is synthesised beside stored data."""
+    if mode == "true" or (mode == "auto" and not stores_input(info, kind)):
+        kept = {k: v for k, v in info.items() if k not in ("faces", "faceviews")}
+        return {**kept, **render_info(where + str(info.get("name", "")), info["coords"], info["attach"]), "name": info["name"]}
+    return info
+
+
 class _TokenisedDataset(torch.utils.data.Dataset):
+    render = "false"                                               # the classes that render set it from DATA.RENDER_DRAWINGS
+    kind = "line"                                                  # what ``stores_input`` asks of an info file
+
     def __init__(self, root, info_files, token, cfg, augmentation=False):
         self.root = root
         self.info_files = info_files
@@ -377,11 +542,19 @@ class _TokenisedDataset(torch.utils.data.Dataset):
 
     def _read_info(self, index):
         with open(os.path.join(self.root, self.info_files[index]), "r") as f:
-            return json.loads(f.read())
+            info = json.loads(f.read())
+        return info if self.render == "false" else rendered(info, self.render, self.kind, f"{self.info_files[index]}: ")
 
 
 class LineDataset(_TokenisedDataset):
-    """reference plankassembly/datasets/line_data.py:12-142."""
+    """reference plankassembly/datasets/line_data.py:12-142.  ``render`` (default: ``DATA.RENDER_DRAWINGS``, else ``auto``):
+    see ``render_mode`` - the drawing is rendered from the planks on access where the info file stores no ``lines``."""
+
+    def __init__(self, root, info_files, token, cfg, augmentation=False, render=None):
+        super().__init__(root, info_files, token, cfg, augmentation)
+        if render is None:
+            render = cfg.get("RENDER_DRAWINGS", None) if hasattr(cfg, "get") else getattr(cfg, "RENDER_DRAWINGS", None)
+        self.render = render_mode(render)
 
     def prepare_input_sequence(self, lines, views, types):
         value, pos, coord, view, typ = self._sorted_tokens(lines, views, types)
@@ -433,12 +606,16 @@ class SidefaceDataset(_TokenisedDataset):
     """reference plankassembly/datasets/sideface_data.py:85-254.  ``extract`` (default: ``DATA.EXTRACT_SIDEFACE``, else
     ``auto``): see ``extract_mode``.  The input is extracted from ``svgs`` when the mode says so, and - mode ``auto`` or
     ``true`` - whenever the sample is augmented (the noise acts on the lines, sideface_data.py:233-245)."""
+    kind = "sideface"
 
-    def __init__(self, root, info_files, token, cfg, augmentation=False, extract=None):
+    def __init__(self, root, info_files, token, cfg, augmentation=False, extract=None, render=None):
         super().__init__(root, info_files, token, cfg, augmentation)
         if extract is None:
             extract = cfg.get("EXTRACT_SIDEFACE", None) if hasattr(cfg, "get") else getattr(cfg, "EXTRACT_SIDEFACE", None)
         self.extract = extract_mode(extract)
+        if render is None:
+            render = cfg.get("RENDER_DRAWINGS", None) if hasattr(cfg, "get") else getattr(cfg, "RENDER_DRAWINGS", None)
+        self.render = render_mode(render)
         self._cfg = cfg
 
     def extract_sideface(self, segments, views):

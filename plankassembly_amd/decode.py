@@ -686,3 +686,48 @@ def consensus_select(sample_tokens, end_token, threshold=0.5):
     # (a device tensor as the divisor: torch divides by a host scalar as a multiplication by its reciprocal, one rounding too many)
     others = torch.full((), float(max(N - 1, 1)), dtype=torch.float64, device=dev)
     return {"consensus_index": index, "consensus_f1": utility.double() / 2.0 ** 40 / others}
+
+
+def redraw_planks(tokens, end_token, num_bits, dof=6):
+    """Decoded rows -> the planks they state: ``tokens`` integer [B, n] (any device) -> (coords float64 [B, n // dof, dof],
+    n_planks int64 [B]).  A row is cut at its first ``end_token`` (its whole length without one) into L // dof planks; every
+    token is dequantised as ``datasets.dequantize_values`` does (q * 2 / (2^bits - 1) - 1, each operation rounded on its own),
+    whatever it is - a token that is no coordinate lands outside [-1, 1] and puts the row out of the renderer's domain.  torch
+    ops only, nothing is read back."""
+    B, n = tokens.shape
+    dev = tokens.device
+    is_end = tokens == end_token
+    length = torch.full((B,), n, dtype=torch.int64, device=dev)
+    if n > 0:                                          # (argmax over an empty dimension raises)
+        length = torch.where(is_end.any(1), is_end.long().argmax(1), length)
+    P = n // dof
+    # (a device tensor as the divisor: torch divides by a host scalar as a multiplication by its reciprocal, one rounding too many)
+    rq = torch.full((), float(2 ** int(num_bits) - 1), dtype=torch.float64, device=dev)
+    coords = (tokens[:, :P * dof].to(torch.float64) * 2.0) / rq + (-1.0)
+    return coords.reshape(B, P, dof).contiguous(), torch.div(length, dof, rounding_mode="floor")
+
+
+def _redraw(tokens, end_token, pad_token, num_bits, dof, max_input_length, with_type=True):
+    """``redraw`` on plain values.  A row wider than the render kernel's plank cap is not refused for its width: the planks
+    tensor is cut at the cap, and a row that STATES more planks than the cap renders the first ones and gets
+    PA_RENDER_TRUNCATED - the flag is set here with torch ops, so nothing is read back."""
+    from . import ops
+    coords, n_planks = redraw_planks(tokens, end_token, num_bits, dof)
+    cap = ops.RENDER_MAX_PLANKS
+    out = ops.render_drawings(coords[:, :cap].contiguous(), n_planks.clamp(max=cap), max_input_length=max_input_length,
+                              num_bits=num_bits, end_token=end_token, pad_token=pad_token, with_type=with_type)
+    if coords.shape[1] > cap:
+        over = (n_planks > cap).to(torch.int32) * 2                # include/plank_hip.h PA_RENDER_TRUNCATED
+        out["_render_flags"] = out["_render_flags"] | over
+    return out
+
+
+def redraw(tokens, token, data_cfg):
+    """The model's input for the programs it decoded: ``tokens`` int64 [B, n] on the device
+    (``output_value`` of a decode: values, END, PAD) are cut into planks and dequantised (``redraw_planks``), rendered on the
+    device (``ops.render_drawings``; plank 0 is the bounding box and is not drawn) and returned as an input batch the model
+    accepts, with ``_render_flags`` / ``_lines`` / ``_views`` / ``_types`` / ``_n_lines``.  Rows of any width are taken; a row
+    that states more than PA_RENDER_MAX_PLANKS (32) planks renders its first 32 and is flagged PA_RENDER_TRUNCATED.  Nothing
+    is read back."""
+    return _redraw(tokens, int(token.END), int(token.PAD), int(data_cfg.NUM_BITS), int(data_cfg.get("NUM_OUTPUT_DOF", 6)),
+                   int(data_cfg.MAX_INPUT_LENGTH))

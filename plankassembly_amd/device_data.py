@@ -17,6 +17,10 @@ What differs from the CPU classes, all of it in the augmentation (``LineDataset`
     ``pa_tokenise_sideface_drawings`` (csrc/sideface.h) extracts the side faces of every batch row on the device - faces
     of each view, centre lines, merge, boxes - then tokenises them; such a set can be augmented (the noise acts on the
     lines) and returns ``_extract_flags``; stored ``faces`` (the default) are tokenised as they are and never augmented;
+  - rendered drawings: with ``pack_infos(..., "line", render=True)`` only the PLANKS are packed and
+    ``pa_render_drawings`` (csrc/render.h) draws the three views of every batch row on the device - hidden-line rendering,
+    then the same noise (draws keyed by the canonical line number) and tokens; such a batch returns ``_render_flags``.  A
+    drawing of plank 0 alone tokenises as the empty case ``[END, PAD, ...]``, where ``LineDataset`` raises;
   - a drawing whose every line the noise deleted tokenises as the empty case ``[END, PAD, ...]`` - ``LineDataset`` (and
     the reference) raise there, a kernel cannot; ``num_select`` is capped at the number of lines (``NOISE_RATIO`` > 1
     raises in numpy's ``choice``), and ``NOISE_RATIO`` 0 leaves a drawing as it is (numpy's ``randint(1, 1)`` raises).
@@ -31,10 +35,14 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .datasets import (EXTRACT_OUT_OF_DOMAIN, _DOMAIN, _segment_points, extract_sideface_flags, sideface_thresholds,
-                       two_point_segments, view_faces)
+from .datasets import (EXTRACT_OUT_OF_DOMAIN, RENDER_OUT_OF_DOMAIN, RENDER_TRUNCATED, _DOMAIN, _segment_points,
+                       extract_sideface_flags, render_drawing, rendered, sideface_thresholds, stores_input, two_point_segments,
+                       view_faces)
 
 MAX_LINES = 1024                      # include/plank_hip.h PA_TOKENISE_MAX_LINES: the kernel's LDS key array
+RENDER_MAX_PLANKS = 32                # include/plank_hip.h PA_RENDER_MAX_PLANKS: the render kernel's box arrays
+_SIDEFACE_RENDER = ("rendering on the device (render=True / DATA.RENDER_DRAWINGS) is for kind='line': a sideface file that stores neither "
+                    "'faces' / 'faceviews' nor 'svgs' is rendered and extracted on the host (datasets.SidefaceDataset) - DEVICE_DATASET: false")
 _SIDEFACE_MISSING = (
     "this info file stores no side faces ('faces' [[xmin, ymin, xmax, ymax]] and 'faceviews' [0|1|2]); side-face extraction "
     "from the line drawing (reference sideface_data.py:21-135) is pack_infos(..., 'sideface', extract=True) / "
@@ -58,7 +66,35 @@ def sideface_count(seg, view, data_cfg, where=""):
     return len(faces)
 
 
-def pack_infos(root, info_files, kind="line", extract=False, data_cfg=None):
+def _check_rendered(where, n_planks, n_lines, data_cfg):
+    """A drawing the device is to render, against the render kernel's plank cap and - with ``data_cfg`` - the row."""
+    if n_planks > RENDER_MAX_PLANKS:
+        raise ValueError(f"{where}{n_planks} planks, the render kernel draws at most {RENDER_MAX_PLANKS} (PA_RENDER_MAX_PLANKS)")
+    if data_cfg is not None:
+        room = (int(data_cfg.MAX_INPUT_LENGTH) - 2) // 4
+        if n_lines > room:
+            raise ValueError(f"{where}the rendered drawing has {n_lines} lines ({4 * n_lines} input tokens), which do not fit "
+                             f"MAX_INPUT_LENGTH={int(data_cfg.MAX_INPUT_LENGTH)} ({room} lines)")
+
+
+def render_count(coords, data_cfg, where=""):
+    """The number of lines ``render_drawing`` draws for one drawing's planks, checked against the render kernel's domain and
+    the row: what the host knows of a rendering set without augmentation.  Raises ValueError naming ``where``."""
+    coords = np.asarray(coords, dtype=np.float64).reshape(-1, 6)
+    if len(coords) > RENDER_MAX_PLANKS:
+        raise ValueError(f"{where}{len(coords)} planks, the render kernel draws at most {RENDER_MAX_PLANKS} (PA_RENDER_MAX_PLANKS)")
+    room = (int(data_cfg.MAX_INPUT_LENGTH) - 2) // 4
+    lines, _, _, flags = render_drawing(coords, True, room, int(data_cfg.NUM_BITS))
+    if flags & RENDER_OUT_OF_DOMAIN:
+        raise ValueError(f"{where}plank coordinates must be finite and in [-1, 1] to be rendered (DESIGN.md section 27)")
+    if flags & RENDER_TRUNCATED:
+        n = len(render_drawing(coords)[0])
+        raise ValueError(f"{where}the rendered drawing has {n} lines ({4 * n} input tokens), which do not fit "
+                         f"MAX_INPUT_LENGTH={int(data_cfg.MAX_INPUT_LENGTH)} ({room} lines)")
+    return len(lines)
+
+
+def pack_infos(root, info_files, kind="line", extract=False, data_cfg=None, render=False):
     """Read every info JSON once -> dict of numpy arrays, CSR over the drawings: ``line_off`` int32 [N+1], ``box`` f64
     [L,4] (``lines`` / ``faces`` as stored), ``seg`` f64 [L,4] (x0 y0 x1 y1 of ``svgs``; lines only, None when the files
     carry no svgs), ``view`` u8 [L], ``type`` u8 [L] (lines only), ``plank_off`` int32 [N+1], ``coords`` f64 [P,6],
@@ -68,9 +104,23 @@ def pack_infos(root, info_files, kind="line", extract=False, data_cfg=None):
     ``svgs`` (``box`` their bounds) and the side faces are extracted on the device, batch by batch; every drawing is
     checked against the extraction's domain here, by file name.  With ``data_cfg`` (the ``DATA`` node) the extraction
     also runs once per drawing on the host: ``n_faces`` int64 [N], checked against the row; without it
-    ``DeviceDrawings`` does that.  ``extract="auto"``: True unless every file stores ``faces`` / ``faceviews``."""
+    ``DeviceDrawings`` does that.  ``extract="auto"``: True unless every file stores ``faces`` / ``faceviews``.
+
+    ``kind="line"`` with ``render=True``: only the PLANKS are packed (``name``, ``coords``, ``attach`` are
+    all a file needs) and ``pa_render_drawings`` (csrc/render.h) draws the three views of every batch row on the device.  Every
+    drawing is rendered once on the host here when ``data_cfg`` is given (else by ``DeviceDrawings``): its domain and its line
+    count against the row, by file name -> ``n_lines`` int64 [N].  ``render="auto"`` renders only where a file stores nothing the
+    kind consumes (``datasets.stores_input``), decided file by file in the one packing pass: a file that stores ``lines`` - with
+    or without ``svgs`` - is packed exactly as with ``render=False``; when NO file stores lines the planks-only set above is
+    returned; in a mixed set the files without lines are rendered once here, on the host, and packed beside the stored ones.
+    For ``kind="sideface"`` ``auto`` only refuses, by name, a file that stores neither faces nor ``svgs``."""
     if kind not in ("line", "sideface"):
         raise ValueError(f"kind must be 'line' or 'sideface', got {kind!r}")
+    if render is True and kind != "line":
+        raise ValueError(_SIDEFACE_RENDER)
+    if render is True:
+        return _pack_rendering(root, info_files, data_cfg)
+    auto = render == "auto"
     if extract == "auto":
         def stored(fn):
             with open(os.path.join(root, fn), "r") as f:
@@ -80,13 +130,19 @@ def pack_infos(root, info_files, kind="line", extract=False, data_cfg=None):
     if extract and kind != "sideface":
         raise ValueError("extract=True is for kind='sideface'")
     if extract:
-        return _pack_extracting(root, info_files, data_cfg)
+        return _pack_extracting(root, info_files, data_cfg, auto)
     line_off, plank_off = [0], [0]
     box, seg, view, typ, coords, attach, names = [], [], [], [], [], [], []
     have_seg = kind == "line"
+    n_rendered = 0
     for fn in info_files:
         with open(os.path.join(root, fn), "r") as f:
             info = json.loads(f.read())
+        if auto and not stores_input(info, kind):
+            if kind == "sideface":
+                raise ValueError(f"{fn}: {_SIDEFACE_RENDER}")
+            info = rendered(info, "auto", kind, f"{fn}: ")         # (raises by name outside the renderer's domain)
+            n_rendered += 1
         if kind == "sideface":
             if "faces" not in info or "faceviews" not in info:
                 raise NotImplementedError(_SIDEFACE_MISSING)
@@ -128,6 +184,15 @@ def pack_infos(root, info_files, kind="line", extract=False, data_cfg=None):
     def cat(parts, width, dtype):
         return np.concatenate(parts).astype(dtype) if parts else np.zeros((0, width) if width else (0,), dtype)
 
+    if n_rendered and n_rendered == len(info_files):               # no file stores a drawing: the device renders every batch
+        n_lines = np.diff(line_off).astype(np.int64)
+        for i, fn in enumerate(info_files):
+            _check_rendered(f"{fn}: ", len(coords[i]), int(n_lines[i]), data_cfg)
+        out = {"kind": "line", "render": True, "names": names, "files": list(info_files),
+               "plank_off": np.asarray(plank_off, np.int32), "coords": cat(coords, 6, np.float64), "attach": cat(attach, 6, np.int32)}
+        if data_cfg is not None:
+            out["n_lines"] = n_lines
+        return out
     out = {"kind": kind, "names": names, "files": list(info_files),
            "line_off": np.asarray(line_off, np.int32), "box": cat(box, 4, np.float64), "view": cat(view, 0, np.uint8),
            "plank_off": np.asarray(plank_off, np.int32), "coords": cat(coords, 6, np.float64),
@@ -138,12 +203,14 @@ def pack_infos(root, info_files, kind="line", extract=False, data_cfg=None):
     return out
 
 
-def _pack_extracting(root, info_files, data_cfg):
+def _pack_extracting(root, info_files, data_cfg, auto_render=False):
     line_off, plank_off = [0], [0]
     seg, view, coords, attach, names, n_faces = [], [], [], [], [], []
     for fn in info_files:
         with open(os.path.join(root, fn), "r") as f:
             info = json.loads(f.read())
+        if auto_render and not stores_input(info, "sideface"):
+            raise ValueError(f"{fn}: {_SIDEFACE_RENDER}")
         s = two_point_segments(info.get("svgs") or [], f"{fn}: ")
         v = np.array(info["views"], dtype="long").reshape(-1)
         if len(v) != len(s) or (len(v) and (v.min() < 0 or v.max() > 254)):
@@ -179,6 +246,33 @@ def _pack_extracting(root, info_files, data_cfg):
     return out
 
 
+def _pack_rendering(root, info_files, data_cfg):
+    plank_off, coords, attach, names, n_lines = [0], [], [], [], []
+    for fn in info_files:
+        with open(os.path.join(root, fn), "r") as f:
+            info = json.loads(f.read())
+        c = np.array(info["coords"], dtype="float").reshape(-1)
+        a = np.array(info["attach"], dtype="long").reshape(-1)
+        if len(c) % 6 or len(a) != len(c):
+            raise ValueError(f"{fn}: coords ({len(c)} values) and attach ({len(a)}) must hold 6 values per plank")
+        if not _in_unit_range(c):
+            raise ValueError(f"{fn}: coordinates outside [-1, 1]")
+        if len(c) // 6 > RENDER_MAX_PLANKS:
+            raise ValueError(f"{fn}: {len(c) // 6} planks, the render kernel draws at most {RENDER_MAX_PLANKS} (PA_RENDER_MAX_PLANKS)")
+        if data_cfg is not None:
+            n_lines.append(render_count(c, data_cfg, f"{fn}: "))
+        coords.append(c.reshape(-1, 6)); attach.append(a.reshape(-1, 6))
+        plank_off.append(plank_off[-1] + len(c) // 6)
+        names.append(info["name"])
+    out = {"kind": "line", "render": True, "names": names, "files": list(info_files),
+           "plank_off": np.asarray(plank_off, np.int32),
+           "coords": np.concatenate(coords).astype(np.float64) if coords else np.zeros((0, 6), np.float64),
+           "attach": np.concatenate(attach).astype(np.int32) if attach else np.zeros((0, 6), np.int32)}
+    if data_cfg is not None:
+        out["n_lines"] = np.asarray(n_lines, np.int64)
+    return out
+
+
 def _get(cfg, key, default):
     return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
 
@@ -201,9 +295,18 @@ class DeviceDrawings:
         self.seed = int(seed)
         if int(data_cfg.NUM_INPUT_DOF) != 4:
             raise ValueError(f"the device dataset writes 4 tokens per primitive, NUM_INPUT_DOF is {data_cfg.NUM_INPUT_DOF}")
-        self.n_lines = np.diff(packed["line_off"]).astype(np.int64)
         n_planks = np.diff(packed["plank_off"]).astype(np.int64)
         files = packed.get("files") or self.names
+        self.render = bool(packed.get("render", False))                # the drawing from the planks, on the device (section 27)
+        if not self.render:
+            self.n_lines = np.diff(packed["line_off"]).astype(np.int64)
+        elif packed.get("n_lines") is not None:
+            self.n_lines = np.asarray(packed["n_lines"], dtype=np.int64)
+        else:
+            off = packed["plank_off"]
+            self.n_lines = np.asarray([render_count(packed["coords"][off[i]:off[i + 1]], data_cfg, f"{files[i]}: ")
+                                       for i in range(len(self.names))], np.int64)
+        self.max_planks = int(n_planks.max()) if len(n_planks) else 0
         self.extract = bool(packed.get("extract", False))              # side faces from the lines, on the device (section 26)
         self.n_prims = self.n_lines                                    # primitives in a row without augmentation
         if self.extract:
@@ -227,9 +330,13 @@ class DeviceDrawings:
                 a = np.zeros((1,) + a.shape[1:], a.dtype)
             return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
 
-        self._line_off, self._plank_off = up(packed["line_off"]), up(packed["plank_off"])
-        self._box, self._view = up(packed["box"]), up(packed["view"])
+        self._plank_off = up(packed["plank_off"])
         self._coords, self._attach = up(packed["coords"]), up(packed["attach"])
+        if self.render:                                                # planks only: there are no stored lines
+            self._line_off = self._box = self._view = self._seg = self._type = None
+            return
+        self._line_off = up(packed["line_off"])
+        self._box, self._view = up(packed["box"]), up(packed["view"])
         self._seg = up(packed["seg"]) if packed.get("seg") is not None else None
         self._type = up(packed["type"]) if self.kind == "line" else None
 
@@ -257,7 +364,7 @@ class DeviceDrawings:
         if len(host_index) != index.numel() or (len(host_index) and (host_index.min() < 0 or host_index.max() >= len(self))):
             raise IndexError(f"drawing numbers must be {index.numel()} values in [0, {len(self)})")
         aug = self.augments(augmentation)
-        if aug and self._seg is None:
+        if aug and self._seg is None and not self.render:
             raise ValueError("augmentation needs the segments of the info files ('svgs'), which this dataset does not hold")
         B, S, T, dev = index.numel(), self.max_input_length - 1, self.max_output_length, self.device
         with_type = self.kind == "line"
@@ -272,6 +379,8 @@ class DeviceDrawings:
         n_tokens = torch.empty(B, dtype=torch.int32, device=dev)
         if self.extract:
             return self._extract_batch(out, index, host_index, n_tokens, aug, epoch, seed)
+        if self.render:
+            return self._render_batch(out, index, host_index, n_tokens, aug, epoch, seed)
         L.check(L.lib().pa_tokenise_drawings(
             L.ptr(self._line_off), L.ptr(self._box), L.ptr(self._seg), L.ptr(self._view), L.ptr(self._type),
             L.ptr(self._plank_off), L.ptr(self._coords), L.ptr(self._attach), len(self), L.ptr(index), B, S, T,
@@ -281,6 +390,23 @@ class DeviceDrawings:
             L.ptr(out.get("input_type")), L.ptr(out["input_mask"]), L.ptr(out["output_value"]), L.ptr(out["output_label"]),
             L.ptr(out["output_mask"]), L.ptr(n_tokens), L.stream()), "pa_tokenise_drawings")
         out["_n_tokens"] = n_tokens
+        if not aug:
+            out["_n_valid"] = int((4 * self.n_lines[host_index] + 1).sum())
+        return out
+
+    def _render_batch(self, out, index, host_index, n_tokens, aug, epoch, seed):
+        """The rendering line set: one launch of ``pa_render_drawings``.  Beside the batch: ``_render_flags`` int32 [B]
+        (include/plank_hip.h PA_RENDER_*); the host has checked every drawing, so they are 0 or PA_RENDER_DEGENERATE."""
+        B, S, T, dev = index.numel(), self.max_input_length - 1, self.max_output_length, self.device
+        flags = torch.empty(B, dtype=torch.int32, device=dev)
+        L.check(L.lib().pa_render_drawings(
+            L.ptr(self._plank_off), None, L.ptr(self._coords), L.ptr(self._attach), len(self), L.ptr(index), B, self.max_planks, 1,
+            S, T, self.num_bits, int(self.token.END), int(self.token.PAD), self.vocab_size, 1, int(aug),
+            self.aug_ratio, self.noise_ratio, self.noise_length, int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+            L.ptr(out["input_value"]), L.ptr(out["input_pos"]), L.ptr(out["input_coord"]), L.ptr(out["input_view"]),
+            L.ptr(out["input_type"]), L.ptr(out["input_mask"]), L.ptr(out["output_value"]), L.ptr(out["output_label"]),
+            L.ptr(out["output_mask"]), L.ptr(n_tokens), None, None, None, None, L.ptr(flags), L.stream()), "pa_render_drawings")
+        out["_n_tokens"], out["_render_flags"] = n_tokens, flags
         if not aug:
             out["_n_valid"] = int((4 * self.n_lines[host_index] + 1).sum())
         return out

@@ -963,6 +963,22 @@ class PlankModel(nn.Module):
         return self._decode_dict(batch, {"tokens": output, "attach": attach, "prefix_scores": dec.last_prefix_scores,
                                          "prefix_logprobs": dec.last_prefix_logprobs}, prefix, parse)
 
+    def redraw(self, output_value, num_bits=None):
+        """The model's own input for programs it decoded: ``output_value`` int [B, n] - of ``eval_step``,
+        ``sample`` or a batch - is cut at each row's first END into planks, dequantised and rendered as the three-view drawing on
+        the device (decode.redraw_planks, ops.render_drawings; plank 0, the bounding box, is not drawn).  Returns an input batch
+        ``eval_step`` / ``score`` accept, with ``_render_flags`` int32 [B] (a row whose tokens are no coordinates renders nothing,
+        PA_RENDER_OUT_OF_DOMAIN) and the lines as ``_lines`` / ``_views`` / ``_types`` / ``_n_lines``.  ``num_bits``: the
+        quantisation (default: from the vocabulary, 2^bits values + END + PAD).  Rows of any width are taken; a row that states
+        more than PA_RENDER_MAX_PLANKS (32) planks renders its first 32 and is flagged PA_RENDER_TRUNCATED.  Nothing is read back."""
+        self._require_gpu()
+        from .decode import _redraw
+        if num_bits is None:
+            num_bits = (int(self.vocab_size) - 2).bit_length() - 1
+        tokens = output_value.to(device=self._flat.device, dtype=torch.int64)
+        return _redraw(tokens, int(self.token.END), int(self.token.PAD), int(num_bits), self.num_output_dof, self.max_input_length,
+                       with_type="input_embeddings.input_type.weight" in self._shapes)
+
     def score(self, batch, tokens=None, attach=None, lengths=None):
         """Log-likelihood of given sequences under the model, on the GPU: the greedy decode step with every position forced
         (DESIGN.md section 14), one sequence per batch row, max(lengths) steps.

@@ -621,6 +621,66 @@ def plank_match(seq_a, seq_b, pairs=None, *, end_token, filter_a, filter_b, thre
     return out
 
 
+RENDER_MAX_PLANKS = 32                # include/plank_hip.h PA_RENDER_MAX_PLANKS
+
+
+def render_drawings(coords, n_planks=None, *, max_input_length, num_bits, end_token, pad_token, skip_first=True, with_type=True,
+                    augmentation=False, aug_ratio=0.0, noise_ratio=0.0, noise_length=0.0, seed=0, epoch=0, lines=True):
+    """The three-view line drawing of every row's planks, rendered and tokenised by one launch (pa_render_drawings,
+    csrc/render.h).
+
+    ``coords`` float64 [B, P, 6] on the device (lo xyz, hi xyz per plank, in [-1, 1]); ``n_planks`` integer [B] on the device
+    (default: P for every row) - the planks of row b are ``coords[b, :n_planks[b]]``; plank 0 is not drawn with ``skip_first``.
+    P above PA_RENDER_MAX_PLANKS raises PA_ESHAPE; nothing is read back.  The noise draws of an augmented call are keyed by
+    the row number.  Returns the encoder rows of the batch contract (``input_value`` / ``input_pos`` / ``input_coord`` /
+    ``input_view`` / ``input_type`` int64 [B, S], ``input_mask`` bool [B, S], S = ``max_input_length`` - 1), ``_n_tokens`` int32
+    [B], ``_render_flags`` int32 [B] (PA_RENDER_* bits) and - with ``lines`` - ``_lines`` float64 [B, F, 4] (xmin ymin xmax
+    ymax), ``_views`` / ``_types`` uint8 [B, F] and ``_n_lines`` int32 [B], F = (S - 1) // 4: the lines before the noise in the
+    canonical order, zero behind each row's count."""
+    if not (torch.is_tensor(coords) and coords.is_cuda and coords.dtype == torch.float64 and coords.dim() == 3 and coords.shape[2] == 6):
+        raise TypeError("coords must be a float64 [B, P, 6] device tensor")
+    B, P, dev = int(coords.shape[0]), int(coords.shape[1]), coords.device
+    S = int(max_input_length) - 1
+    F = max((S - 1) // 4, 0)
+    if B == 0 or S <= 0:
+        raise ValueError("render_drawings needs at least one row and MAX_INPUT_LENGTH >= 2")
+    coords = coords.contiguous()
+    if P == 0:                                         # never an empty allocation: the ABI takes no NULL arrays
+        coords = torch.zeros(B, 1, 6, dtype=torch.float64, device=dev)
+    stride = int(coords.shape[1])
+    if n_planks is None:
+        cnt = torch.full((B,), P, dtype=torch.int32, device=dev)
+    else:
+        if not (torch.is_tensor(n_planks) and n_planks.is_cuda and n_planks.shape == (B,)):
+            raise TypeError("n_planks must be an integer [B] device tensor")
+        cnt = n_planks.to(torch.int32).clamp(0, P).contiguous()
+    off = torch.arange(B + 1, dtype=torch.int32, device=dev) * stride
+    index = torch.arange(B, dtype=torch.int32, device=dev)
+    out = {k: torch.empty(B, S, dtype=torch.int64, device=dev) for k in ("input_value", "input_pos", "input_coord", "input_view")}
+    if with_type:
+        out["input_type"] = torch.empty(B, S, dtype=torch.int64, device=dev)
+    out["input_mask"] = torch.empty(B, S, dtype=torch.bool, device=dev)
+    n_tokens = torch.empty(B, dtype=torch.int32, device=dev)
+    flags = torch.empty(B, dtype=torch.int32, device=dev)
+    ln = vw = ty = nl = None
+    if lines:
+        ln = torch.empty(B, max(F, 1), 4, dtype=torch.float64, device=dev)
+        vw = torch.empty(B, max(F, 1), dtype=torch.uint8, device=dev)
+        ty = torch.empty(B, max(F, 1), dtype=torch.uint8, device=dev)
+        nl = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().pa_render_drawings(
+            L.ptr(off), L.ptr(cnt), L.ptr(coords), None, B, L.ptr(index), B, P, int(bool(skip_first)), S, 0, int(num_bits),
+            int(end_token), int(pad_token), 0, int(bool(with_type)), int(bool(augmentation)), float(aug_ratio), float(noise_ratio),
+            float(noise_length), int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, L.ptr(out["input_value"]), L.ptr(out["input_pos"]),
+            L.ptr(out["input_coord"]), L.ptr(out["input_view"]), L.ptr(out.get("input_type")), L.ptr(out["input_mask"]), None, None, None,
+            L.ptr(n_tokens), L.ptr(ln), L.ptr(vw), L.ptr(ty), L.ptr(nl), L.ptr(flags), L.stream()), "pa_render_drawings")
+    out["_n_tokens"], out["_render_flags"] = n_tokens, flags
+    if lines:
+        out["_lines"], out["_views"], out["_types"], out["_n_lines"] = ln[:, :F], vw[:, :F], ty[:, :F], nl
+    return out
+
+
 SEQ_OBJECTIVES = ("reinforce", "risk")
 SEQ_BASELINES = ("none", "mean", "greedy")
 

@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from .config import CfgNode, load_cli_config
 from .data import SynthSpec, synth_sample
-from .datasets import LineDataset, SidefaceDataset, extract_mode, parse_splits_list  # noqa: F401  (parse_splits_list re-exported)
+from .datasets import LineDataset, SidefaceDataset, extract_mode, parse_splits_list, render_mode  # noqa: F401  (parse_splits_list re-exported)
 from .metric import DevicePlankScorer, PlankScorer, planks_of_row, valid_planks
 from .models import build_model
 
@@ -88,6 +88,7 @@ class Trainer(torch.nn.Module):
         self.recipe = recipe_options(self.hparams_dict)  # weight decay / LR schedule / EMA keys of the hparams, validated
         self.seq_train = seq_train_options(self.hparams_dict)   # the SEQ_TRAIN block, validated; None: plain NLL steps only
         self.extract_sideface = extract_option(self.hparams_dict)      # DATA.EXTRACT_SIDEFACE, validated (sideface kind only)
+        self.render_drawings = render_option(self.hparams_dict)        # DATA.RENDER_DRAWINGS, validated
         self._train_reward = None
 
     # ------------------------------------------------------------------ logging (self.log of Lightning)
@@ -128,8 +129,11 @@ class Trainer(torch.nn.Module):
         cache = self.__dict__.setdefault("_device_drawings", {})       # a split is read and uploaded once, not per validation
         if (split_key, dev) not in cache:
             extract = {"auto": "auto", "true": True, "false": False}[self.extract_sideface] if self.device_kind == "sideface" else False
+            render = {"auto": "auto", "true": True, "false": False}[self.render_drawings]
+            # (pack_infos decides file by file, in its one pass: "auto" leaves a file that stores its input as it is)
+            line = self.device_kind == "line"
             packed = pack_infos(str(self.cfg.get("ROOT", "")), parse_splits_list(self.cfg.get(split_key)), self.device_kind,
-                                extract=extract, data_cfg=self.cfg.DATA if extract else None)
+                                extract=extract, data_cfg=self.cfg.DATA if (extract or (line and render)) else None, render=render)
             cache[split_key, dev] = DeviceDrawings(packed, self.cfg.TOKEN, self.cfg.DATA, dev)
         return DeviceLoader(cache[split_key, dev], self.cfg.BATCH_SIZE, shuffle, drop_last, augmentation, seed)
 
@@ -524,6 +528,14 @@ def extract_option(hparams):
     (stored ``faces`` only).  Read by the sideface kind's CPU dataset and device dataset alike."""
     data = hparams.get("DATA") or {}
     return extract_mode(data.get("EXTRACT_SIDEFACE") if hasattr(data, "get") else None)
+
+
+def render_option(hparams):
+    """``DATA.RENDER_DRAWINGS`` of the hparams, validated -> ``auto`` (default: the drawing is rendered from the planks where the
+    info files store none), ``true`` (always rendered) or ``false`` (stored lines only).  Read by the CPU datasets and the line
+    kind's device dataset alike."""
+    data = hparams.get("DATA") or {}
+    return render_mode(data.get("RENDER_DRAWINGS") if hasattr(data, "get") else None)
 
 
 def seq_train_seed(seed, global_step, rank):
