@@ -715,13 +715,27 @@ int pa_model_set_upstream(pa_model* m, const float* upstream);
 int pa_model_set_loss(pa_model* m, const pa_loss_ext* e);
 int pa_model_train_num_segments(const pa_model* m);
 int pa_model_train_bwd(pa_model* m, int32_t seg_lo, int32_t seg_hi, float gscale, void* stream);
-/* Gradient finality lag in segments.  With PA_SIDE_STREAM=1 (experimental, off by default: slower on MI355X) the model
- * owns one extra HIP stream: the work queued at
- * the end of a layer's backward segment (grouped weight-gradient GEMM, split-K reductions, bias column sums,
- * LayerNorm finishes - all independent of the dX chain) runs there, fenced with events against `stream`, while
- * `stream` continues with the next segment.  The gradients of segment s are then final, in `stream` order, once
- * segment s+2 has been enqueued or the last segment has returned (which joins everything): returns 2; 0 otherwise. */
-int pa_model_grad_lag(const pa_model* m);
+/* Dry run of the training step's host side: the status pa_model_create / pa_model_train_ws_bytes would answer for `cfg` and a batch
+ * of B drawings, S input positions, T output positions and n_valid packed encoder rows (0: unpacked, B * S rows; outside 0..B*S:
+ * PA_EINVAL) and, when that is 0, the workspace and what pa_model_train_bwd plans before each segment: the weight gradients the
+ * segment queues for its one grouped launch, in queue order, each with its split-K and its slab inside the split-K area of the
+ * workspace.  Three kinds of segment queue any: 0 heads, 1 a decoder layer, 2 an encoder layer (reported whether or not cfg has such
+ * layers).  Made by the layout function and the plan function the real calls run, under the caller's bf16x3 mode
+ * (pa_gemm_split_config / pa_split_ctx_enter).  It needs no handle and no GPU and launches nothing. */
+typedef struct {
+    int32_t rows, cols;         /* dW[rows][cols] */
+    int32_t k;                  /* contraction length: the activation rows */
+    int32_t splitk;             /* effective split-K (pa_gemm_effective_splitk) */
+    int64_t slab;               /* offset of its splitk x rows x cols slabs in the split-K area, in floats; -1: not split */
+} pa_train_plan_member;
+typedef struct {
+    int64_t ws_bytes;           /* = pa_model_train_ws_bytes(handle of cfg, B, S, T) */
+    int64_t splitws_floats;     /* the split-K area of the workspace */
+    int32_t n_segments;         /* = pa_model_train_num_segments */
+    int32_t n_members[3];
+    pa_train_plan_member member[3][PA_MAX_GROUP];
+} pa_train_plan_info;
+int pa_train_plan(const pa_model_cfg* cfg, int32_t B, int32_t S, int32_t T, int32_t n_valid, pa_train_plan_info* out);
 /* introspection for parity tests: device pointer + element count of an activation of the last forward */
 int pa_model_tensor(pa_model* m, int32_t which, void** ptr, int64_t* numel);
 

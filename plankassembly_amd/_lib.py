@@ -90,6 +90,16 @@ class DecodePlanInfo(C.Structure):
                 ("mq_sp_bytes", C.c_int64), ("ws_bytes", C.c_int64), ("scr_row", C.c_int64)]
 
 
+class TrainPlanMember(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("k", C.c_int32), ("splitk", C.c_int32), ("slab", C.c_int64)]
+
+
+class TrainPlanInfo(C.Structure):
+    """include/plank_hip.h pa_train_plan_info: what pa_train_plan (the dry run of the training step's host side) reports."""
+    _fields_ = [("ws_bytes", C.c_int64), ("splitws_floats", C.c_int64), ("n_segments", C.c_int32), ("n_members", C.c_int32 * 3),
+                ("member", TrainPlanMember * 8 * 3)]
+
+
 class DecodeGroupInfo(C.Structure):
     """include/plank_hip.h pa_decode_group_info: the decode group pa_decode_group_plan reports beside the plan."""
     _fields_ = [("rows", C.c_int32), ("rows_per_block", C.c_int32), ("units", C.c_int32), ("pad_", C.c_int32), ("mem_rows", C.c_int64)]
@@ -258,7 +268,7 @@ def lib():
             "pa_model_train_num_segments": (I, [P]),
             "pa_model_stats_floats": (I, []),
             "pa_model_train_bwd": (I, [P, I, I, F, P]),
-            "pa_model_grad_lag": (I, [P]),
+            "pa_train_plan": (I, [P, I, I, I, I, P]),
             "pa_model_tensor": (I, [P, I, P, P]),
             "pa_decode_plan": (I, [P, I, I, I, P]),
             "pa_decode_ws_bytes": (I64, [P, I, I, I]),

@@ -44,6 +44,11 @@ int nll_bwd_launch(void* dvocab, void* dptr, int32_t out_dtype, float* dsw, cons
                    const float* vocab, int32_t ldv, const float* ptr, const float* sw, const int64_t* label, int32_t B, int32_t T,
                    int32_t V, int32_t pad, float gscale, const float* upstream, const pa_loss_ext* e, void* stream);
 
+// One weight gradient of a backward segment, dW[rows][cols] contracted over k activation rows, and what runtime.hip's plan_dw
+// decides for a segment's members: each one's effective split-K and its slab offset in floats inside splitws (-1: not split).
+struct DwShape { int rows, cols, k; };
+struct DwPlan { int splitk[PA_MAX_GROUP]; int64_t slab[PA_MAX_GROUP]; };
+
 struct DecodeLayout;
 struct pa_model {
     pa_model_cfg cfg;
@@ -74,26 +79,13 @@ struct pa_model {
     size_t splitws_floats = 0;
     void* gBs[3] = {nullptr, nullptr, nullptr}; void* gCs[3] = {nullptr, nullptr, nullptr};   // per-site LN-backward outputs (ffn, cross, self)
     float* lnp[3] = {nullptr, nullptr, nullptr}; pa_ln_finish_desc lnq[PA_MAX_LN_FINISH]; int nlnq = 0;   // queued LayerNorm-backward finishes
+    DwShape dw_shape[PA_MAX_GROUP]; int dw_n = 0; DwPlan dw_plan;               // the current segment's weight gradients and their plan
     pa_gemm_args dwq[PA_MAX_GROUP]; int ndwq = 0;                               // queued weight-gradient GEMMs of the current segment
     pa_colsum_desc cs[PA_MAX_COLSUM]; int ncs = 0; bool defer_ok = false;       // queued bias-gradient column sums of the current segment
-    pa_reduce_desc defer[PA_MAX_REDUCE]; int ndefer = 0; size_t slab_used = 0;   // queued split-K reductions of the current segment
+    pa_reduce_desc defer[PA_MAX_REDUCE]; int ndefer = 0;                        // queued split-K reductions of the current segment
     bool dmem_written = false;
     void* kv_all = nullptr;            // [rows][n_dec * 2d]: cross-attention K|V of every decoder layer (one batched GEMM over the memory)
     void* gKV_all = nullptr; const void* kvT_all = nullptr;   // packed cross-attention K/V path (pa_model_bind_cross_kv_t)
-    // Two copies ("parity sets") of every buffer the queued end-of-segment work reads: with the side stream on, that
-    // work of segment s runs concurrently with the main stream's segments s+1 (other set) and is joined before s+2.
-    struct SegSet { void* gBs[3]; void* gCs[3]; void *gE, *gF, *gQ3, *gKV; float* lnp[3]; float* splitws; };
-    SegSet seg_set[2];
-    void select_set(int par) {
-        const SegSet& s = seg_set[par];
-        for (int i = 0; i < 3; ++i) { gBs[i] = s.gBs[i]; gCs[i] = s.gCs[i]; lnp[i] = s.lnp[i]; }
-        gE = s.gE; gF = s.gF; gQ3 = s.gQ3; gKV = s.gKV; splitws = s.splitws;
-    }
-    bool side_on = false;                        // PA_SIDE_STREAM (default on): queued segment work goes to `side`
-    void* side = nullptr;                        // hipStream_t
-    void* ev_ready[2] = {nullptr, nullptr};      // main -> side: the segment's dY buffers are complete
-    void* ev_done[2] = {nullptr, nullptr};       // side -> main: the segment's queued work is complete
-    bool ev_pending[2] = {false, false};
     // ---- greedy decode state (decode.hip) ----
     struct DecodeLayout* dec = nullptr;
 
@@ -103,5 +95,3 @@ struct pa_model {
     int dec_norm() const { return enc_norm() + 2 + cfg.n_dec * D_COUNT; }
     int tail() const { return dec_norm() + 2; }
 };
-
-

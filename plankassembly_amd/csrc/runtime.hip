@@ -3,7 +3,6 @@
 // plankassembly/models.py:190-233, train_step) and a hand-derived backward, over one caller-owned
 // workspace ("arena").  Host-only logic: no device allocation, no synchronisation, enqueue-only
 // (hipGraph capturable).  See include/plank_hip.h (pa_model_*).
-#include <stdlib.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <new>
@@ -16,6 +15,72 @@
 namespace {
 
 #define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
+// The weight gradients each kind of backward segment queues, in the order its body calls linear_dw: dW[rows][cols], contracted over
+// BT decoder rows or NE encoder rows (packed: the valid ones).
+enum { SEG_HEADS = 0, SEG_DEC, SEG_ENC, SEG_KINDS };
+int dw_members(const pa_model_cfg& c, int kind, int BT, int NE, DwShape* o) {
+    const int d = c.d_model, ff = c.d_ff;
+    switch (kind) {
+    case SEG_HEADS:                    // vocab head, pointer head
+        o[0] = {c.vocab, d, BT}; o[1] = {d, d, BT};
+        return 2;
+    case SEG_DEC:                      // linear2, linear1, cross out, cross-in Q, cross-in K|V (over the memory), self out, self in
+        o[0] = {d, ff, BT}; o[1] = {ff, d, BT}; o[2] = {d, d, BT}; o[3] = {d, d, BT}; o[4] = {2 * d, d, NE}; o[5] = {d, d, BT};
+        o[6] = {3 * d, d, BT};
+        return 7;
+    case SEG_ENC:                      // linear2, linear1, out, in
+        o[0] = {d, ff, NE}; o[1] = {ff, d, NE}; o[2] = {d, d, NE}; o[3] = {3 * d, d, NE};
+        return 4;
+    default:
+        return 0;                      // embeddings, encoder.norm: no Linear
+    }
+}
+
+// Split-K and slab of every weight gradient of one segment: a pure function of the members (x3: the caller's
+// pa_gemm_split_active(), the bf16x3 mode - planned like bf16 over 3 K rows).  A unit is (128 x 128 tile, K slice).
+//   bf16 / x3: the members run as ONE grouped launch, one block per CU, whose duration is its longest K slice: starting from no split,
+//     the member with the longest slice (the first on ties) gets one more slice for as long as the launch still fits whole rounds of
+//     the 256 CUs - the rounds its unsplit tiles need.  A member of 256 tiles or more fills a round alone and stays whole.
+//   exact f32 (the parity path): pa_gemm_group takes no f32 members, flush_segment launches them one by one on the
+//     two-blocks-per-CU kernel, so each wants the whole chip for itself: 512 units (planned like a grouped launch, the weight
+//     gradients were half of the f32 step: profiles/r04_train_kernel_trace_summary.txt).
+// A split is at most 16 and leaves every slice at least 4 K tiles.  Split members take consecutive slabs of splitk x rows x cols floats.
+void plan_dw(int dtype, bool x3, const DwShape* mem, int n, size_t splitws_floats, DwPlan* out) {
+    const int ktile = (dtype == PA_BF16 || x3) ? 64 : 16;
+    int tiles[PA_MAX_GROUP], nkt[PA_MAX_GROUP], cap[PA_MAX_GROUP], total = 0;
+    int* sk = out->splitk;
+    for (int i = 0; i < n; ++i) {
+        tiles[i] = ((mem[i].rows + 127) / 128) * ((mem[i].cols + 127) / 128);
+        nkt[i] = ((x3 ? 3 * mem[i].k : mem[i].k) + ktile - 1) / ktile;
+        cap[i] = tiles[i] >= 256 ? 1 : nkt[i] / 4 < 1 ? 1 : nkt[i] / 4 > 16 ? 16 : nkt[i] / 4;
+        sk[i] = 1;
+        total += tiles[i];
+    }
+    if (dtype == PA_BF16 || x3) {
+        const int budget = (total + 255) / 256 * 256;
+        for (;;) {
+            int best = -1, len = 0;
+            for (int i = 0; i < n; ++i) {
+                const int li = (nkt[i] + sk[i] - 1) / sk[i];
+                if (li > len) { len = li; best = i; }
+            }
+            if (best < 0 || sk[best] >= cap[best] || total + tiles[best] > budget) break;
+            ++sk[best]; total += tiles[best];
+        }
+    } else {
+        for (int i = 0; i < n; ++i) { const int s = 512 / tiles[i]; sk[i] = s < 1 ? 1 : s > cap[i] ? cap[i] : s; }
+    }
+    size_t used = 0;
+    int ndefer = 0;
+    for (int i = 0; i < n; ++i) {
+        sk[i] = pa_gemm_effective_splitk(mem[i].k, dtype, sk[i]);               // slabs actually written
+        const size_t need = (size_t)sk[i] * mem[i].rows * mem[i].cols;
+        if (sk[i] > 1 && (ndefer == PA_MAX_REDUCE || used + need > splitws_floats)) sk[i] = 1;      // no room: whole
+        out->slab[i] = sk[i] > 1 ? (int64_t)used : -1;
+        if (sk[i] > 1) { ++ndefer; used += (need + 3) / 4 * 4; }
+    }
+}
 
 struct Ctx {   // convenience wrapper for kernel calls in the model's dtype
     pa_model* m; void* st;
@@ -57,52 +122,26 @@ struct Ctx {   // convenience wrapper for kernel calls in the model's dtype
         g.alpha = 1.f; g.aux_scale = aux_scale; g.splitk = 1;
         return pa_gemm(&g, st);
     }
-    // dW[N][K] = dY[M,N]^T x X[M,K] (f32 out, split-K over the rows), db[N] = colsum(dY) unless db == NULL
+    // dW[N][K] = dY[M,N]^T x X[M,K] (f32 out, split-K over the rows), db[N] = colsum(dY) unless db == NULL.  Nothing is launched here:
+    // the call is the next member of the segment's plan (backward_segment), queued with the split and slab planned for it; the
+    // segment's flush launches all members together and its tail reduces their slabs.
     int linear_dw(const void* dY, int lddy, const void* Xin, int ldx, float* dW, float* db, int M, int N, int K) const {
-        pa_gemm_args g; memset(&g, 0, sizeof(g));
+        const int i = m->ndwq;
+        if (i >= m->dw_n) return PA_EINVAL;                 // not a member the segment planned (dw_n <= PA_MAX_GROUP: the queue's size)
+        const DwShape& s = m->dw_shape[i];
+        if (s.rows != N || s.cols != K || s.k != M) return PA_EINVAL;
+        pa_gemm_args& g = m->dwq[m->ndwq++]; memset(&g, 0, sizeof(g));
         g.A = dY; g.B = Xin; g.C = dW;
         g.M = N; g.N = K; g.K = M; g.lda = lddy; g.ldb = ldx; g.ldc = K;
         g.batch = 1; g.a_kcontig = 0; g.b_kcontig = 0;
         g.in_dtype = dt(); g.out_dtype = PA_F32;
         g.alpha = 1.f; g.aux_scale = 1.f;
-        const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
-        const bool x3 = dt() == PA_F32 && pa_gemm_split_active();          // bf16x3: the bf16 kernels over 3 M stacked rows
-        const int ktile = (dt() == PA_BF16 || x3) ? 64 : 16;
-        const int nkt = ((x3 ? 3 * M : M) + ktile - 1) / ktile;
-        static const bool plan = !(getenv("PA_DW_PLAN") && atoi(getenv("PA_DW_PLAN")) == 0);
-        if (plan && m->defer_ok && tiles < 256 && m->ndwq < PA_MAX_GROUP) {
-            // member of the segment's grouped launch: its split is chosen at the flush, when all members are known
-            // (plan_group: one round of the one-block-per-CU kernel with the longest K slice as short as possible)
-            g.splitk = 0; g.ws = nullptr;
-            m->dwq[m->ndwq++] = g;
-            return queue_bias(dY, lddy, db, M, N);
-        }
-        int sk = 1;
-        if (tiles < 256) {
-            // a lone launch wants one round of the one-block-per-CU kernel (256 tiles x slices); the members of a grouped
-            // launch share the CUs, so each is split 4x less (measured: 64 -> 6.61 ms/step, 256 -> 6.73, 32 -> 6.63)
-            static const int target_env = getenv("PA_DW_UNITS") ? atoi(getenv("PA_DW_UNITS")) : 0;
-            const int target = target_env > 0 ? target_env : (m->defer_ok ? 64 : 256);
-            sk = target / tiles > 0 ? target / tiles : 1;
-            if (sk > 16) sk = 16;
-            if (sk > nkt / 4) sk = nkt / 4 > 0 ? nkt / 4 : 1;
-            while (sk > 1 && (size_t)sk * N * K > m->splitws_floats) --sk;
-        }
-        sk = pa_gemm_effective_splitk(M, dt(), sk);             // slabs actually written
-        g.splitk = sk; g.ws = m->splitws;
-        // queue the reduction: all weight gradients of a segment are reduced by one launch at its end (flush_reduce)
-        const size_t need = (size_t)sk * N * K;
-        if (sk > 1 && m->ndefer < PA_MAX_REDUCE && m->slab_used + need <= m->splitws_floats && (K & 3) == 0) {
-            g.ws = m->splitws + m->slab_used;
+        g.splitk = m->dw_plan.splitk[i]; g.ws = m->splitws;
+        if (m->dw_plan.slab[i] >= 0) {
+            g.ws = m->splitws + m->dw_plan.slab[i];
             g.splitk_defer = 1;
             pa_reduce_desc& rd = m->defer[m->ndefer++];
-            rd.ws = m->splitws + m->slab_used; rd.out = dW; rd.rows = N; rd.cols = K; rd.ld_out = K; rd.splitk = sk;
-            m->slab_used += (need + 3) / 4 * 4;
-        }
-        if (m->defer_ok && g.splitk_defer == (sk > 1 ? 1 : 0) && m->ndwq < PA_MAX_GROUP) {
-            m->dwq[m->ndwq++] = g;                               // launched with the segment's other weight gradients (flush)
-        } else {
-            RC(pa_gemm(&g, st));
+            rd.ws = (const float*)g.ws; rd.out = dW; rd.rows = N; rd.cols = K; rd.ld_out = K; rd.splitk = g.splitk;
         }
         return queue_bias(dY, lddy, db, M, N);
     }
@@ -121,22 +160,10 @@ struct Ctx {   // convenience wrapper for kernel calls in the model's dtype
         }
         return 0;
     }
-    // z = R + drop(A W^T + bias), y = LayerNorm(z): the post-norm sublayer tail of a decoder layer.  PLANK_TRAIN_FUSE_LN=<rows>
-    // sends launches of at most that many rows to the one-launch row-block kernel pa_gemm_ln (bit-identical to the two
-    // launches, round 2).  OFF by default: measured in round 4 at the decoder's 2 048 rows (18 sites per step) the step is
-    // 5.29 ms with it against 5.07 ms without - 64 blocks each pulling a whole 512 x K weight through their own CU take ~26 us
-    // where gemm3s + LayerNorm take ~14 (the same per-CU weight streaming that made it lose at 256 and at 7 940 rows).
+    // z = R + drop(A W^T + bias), y = LayerNorm(z): the post-norm sublayer tail of a decoder layer
     int linear_ln(const void* A, int lda, const void* W, const float* bias, const void* R, void* z, void* y, const float* g,
                   const float* b, float* mean, float* rstd, int M, int K, float drop_p, uint32_t seed, float eps) const {
-        static const int fuse_max = getenv("PLANK_TRAIN_FUSE_LN") ? atoi(getenv("PLANK_TRAIN_FUSE_LN")) : 0;
         const int d = m->cfg.d_model;
-        if (dt() == PA_BF16 && d == 512 && M <= fuse_max && M <= pa_gemm_ln_max_rows() && K % 64 == 0) {
-            pa_gemm_ln_args a; memset(&a, 0, sizeof(a));
-            a.A = A; a.W = W; a.bias = bias; a.R = R; a.Z = z; a.Y = y; a.gamma = g; a.beta = b; a.mean = mean; a.rstd = rstd;
-            a.M = M; a.N = d; a.K = K; a.lda = lda; a.ldw = K; a.ldr = d; a.ldz = d; a.ldy = d;
-            a.eps = eps; a.drop_p = drop_p; a.drop_seed = seed;
-            return pa_gemm_ln(&a, st);
-        }
         RC(linear(A, lda, W, bias, z, d, M, d, K, 0, drop_p, seed, R, d));
         return ln_fwd(y, z, g, b, mean, rstd, M, eps);
     }
@@ -174,8 +201,7 @@ struct Ctx {   // convenience wrapper for kernel calls in the model's dtype
         pa_attn_args a; memset(&a, 0, sizeof(a));
         a.cu_q = cu_q; a.cu_k = cu_k;
         // packed encoder rows: dispatch the batch elements longest first (pa_pack_rows left that order behind cu_in)
-        static const bool use_order = !(getenv("PA_ATTN_ORDER") && atoi(getenv("PA_ATTN_ORDER")) == 0);
-        if (use_order && cu_k && cu_k == m->batch.cu_in) a.order = cu_k + m->B + 1;
+        if (cu_k && cu_k == m->batch.cu_in) a.order = cu_k + m->B + 1;
         if (cu_q && cu_q == cu_k) { a.ws = m->attn_ws; a.ws_bytes = m->attn_ws_bytes; }      // packed self-attention: range blocks
         const int d = m->cfg.d_model, H = m->cfg.n_head;
         a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.kpm = kpm;
@@ -241,11 +267,6 @@ size_t pa_train_layout(pa_model* m, char* base, int B, int S, int T) {
     m->gPre = c.activation == 2 ? a.take(R * ff * e) : nullptr;
     m->gKV = a.take(BS * 2 * d * e); m->dmem = a.take(BS * d * e);
     m->gKV_all = a.take(BS * 2 * d * e * (c.n_dec > 0 ? c.n_dec : 1));     // d(K|V) of every decoder layer side by side (packed K/V shadow mode)
-    {   // parity set 1 (set 0 = the buffers above)
-        pa_model::SegSet& s1 = m->seg_set[1];
-        for (int s_ = 0; s_ < 3; ++s_) { s1.gBs[s_] = a.take(R * d * e); s1.gCs[s_] = a.take(R * d * e); }
-        s1.gE = a.take(R * d * e); s1.gF = a.take(R * ff * e); s1.gQ3 = a.take(R * 3 * d * e); s1.gKV = a.take(BS * 2 * d * e);
-    }
     m->dvlog = a.take(BT * m->ldv * e); m->dplog = a.take(BT * T * e); m->dsw = (float*)a.take(BT * 4);
     m->delta = (float*)a.take((size_t)B * H * R * 4);
     size_t part = (size_t)pa_layernorm_ws_floats((int64_t)R, (int)d);
@@ -254,24 +275,14 @@ size_t pa_train_layout(pa_model* m, char* base, int B, int S, int T) {
     if (cs > part) part = cs;
     m->partial = (float*)a.take(part * 4);
     for (int s_ = 0; s_ < 3; ++s_) m->lnp[s_] = (float*)a.take((size_t)pa_layernorm_ws_floats((int64_t)R, (int)d) * 4);   // queued LN-backward partials
-    for (int s_ = 0; s_ < 3; ++s_) m->seg_set[1].lnp[s_] = (float*)a.take((size_t)pa_layernorm_ws_floats((int64_t)R, (int)d) * 4);
     // split-K slabs of every weight gradient of one backward segment (they are reduced together at its end):
     // a decoder layer is the largest segment (self in/out, cross in/out, two FFN weights), <= 16 slices each
     const size_t wmax = (3 * d * d > d * ff ? 3 * d * d : d * ff);
     const size_t wlayer = 8 * d * d + 2 * d * ff + (size_t)m->ldv * d;
     m->splitws_floats = 16 * (wlayer > wmax ? wlayer : wmax);
     m->splitws = (float*)a.take(m->splitws_floats * 4);
-    m->seg_set[1].splitws = (float*)a.take(m->splitws_floats * 4);
-    {   // record set 0 and make it current
-        pa_model::SegSet& s0 = m->seg_set[0];
-        for (int s_ = 0; s_ < 3; ++s_) { s0.gBs[s_] = m->gBs[s_]; s0.gCs[s_] = m->gCs[s_]; s0.lnp[s_] = m->lnp[s_]; }
-        s0.gE = m->gE; s0.gF = m->gF; s0.gQ3 = m->gQ3; s0.gKV = m->gKV; s0.splitws = m->splitws;
-    }
     return a.off;
 }
-namespace {
-
-}  // namespace
 // --------------------------------------------------------------------------------------------------
 int pa_train_forward_impl(pa_model* m, void* st) {
     const pa_model_cfg& c = m->cfg;
@@ -323,8 +334,7 @@ int pa_train_forward_impl(pa_model* m, void* st) {
         bool uniform = ws > 0 && bs > 0 && ws % (ptrdiff_t)e == 0 && bs % 16 == 0;
         for (int i = 2; i < c.n_dec && uniform; ++i)
             uniform = (const char*)PL(m->dec_base(i) + D_CA_IN_W) - w0 == ws * i && (const char*)PF(m->dec_base(i) + D_CA_IN_B) - (const char*)b0 == bs * i;
-        static const bool fuse_env = !(getenv("PLANK_CROSS_KV_FWD") && atoi(getenv("PLANK_CROSS_KV_FWD")) == 0);
-        if (uniform && fuse_env) {
+        if (uniform) {
             pa_gemm_args g; memset(&g, 0, sizeof(g));
             g.A = memory; g.B = w0 + (size_t)d * d * e; g.C = m->kv_all; g.bias = b0 + d;
             g.M = BS; g.N = 2 * d; g.K = d; g.lda = d; g.ldb = d; g.ldc = c.n_dec * 2 * d;
@@ -529,118 +539,35 @@ int bwd_enc_layer(pa_model* m, int i, void* st) {
 }
 
 int backward_segment_body(pa_model* m, int seg, float gscale, void* st);
-#define HC(x) do { hipError_t he_ = (x); if (he_ != hipSuccess) return (int)he_; } while (0)
-// enqueue the segment's queued work (grouped weight-gradient GEMM, split-K reductions, bias column sums, LayerNorm
-// finishes) on stream `q`
-// Split-K plan for the queued weight-gradient GEMMs of a segment (members queued with splitk == 0).  The grouped launch
-// runs one block per CU and a unit is (128x128 tile, K slice), so its duration is the longest K slice: starting from no
-// split, the member with the longest slice gets one more slice for as long as the launch still fits one round of the CUs.
-// Encoder layer (K = 7 940 rows, 128 tiles): every member split in two -> 256 units of 63 K tiles; decoder layer: only the
-// cross-attention K/V gradient (K = encoder rows) is split.  Slabs of the split members are reduced by the segment tail.
-void plan_group(pa_model* m) {
-    const int n = m->ndwq;
-    int tiles[PA_MAX_GROUP], nkt[PA_MAX_GROUP], cap[PA_MAX_GROUP], sk[PA_MAX_GROUP];
-    const bool x3 = m->cfg.dtype == PA_F32 && pa_gemm_split_active();     // bf16x3: planned like the bf16 grouped launch, 3 K rows each
-    const int ktile = (m->cfg.dtype == PA_BF16 || x3) ? 64 : 16;
-    int total = 0, planned = 0;
-    for (int i = 0; i < n; ++i) {
-        const pa_gemm_args& g = m->dwq[i];
-        tiles[i] = ((g.M + 127) / 128) * ((g.N + 127) / 128);
-        nkt[i] = ((x3 ? 3 * g.K : g.K) + ktile - 1) / ktile;
-        sk[i] = g.splitk > 0 ? g.splitk : 1;
-        cap[i] = g.splitk > 0 ? sk[i] : ((g.N & 3) ? 1 : (nkt[i] / 4 < 16 ? (nkt[i] / 4 > 0 ? nkt[i] / 4 : 1) : 16));
-        total += tiles[i] * sk[i];
-        planned += g.splitk == 0;
-    }
-    if (!planned) return;
-    if (m->cfg.dtype != PA_BF16 && !x3) {
-        // f32 (the parity path): pa_gemm_group takes bf16 members only, so flush_segment launches these one by one on the
-        // two-blocks-per-CU kernel - each member then wants the whole chip for itself (512 units), not its share of one grouped
-        // round.  Rounds 1-3 planned them like a grouped launch: the encoder's out_proj gradient ran on 32 of the 512 block
-        // slots, in_proj on 96, and the weight gradients were HALF of the f32 step (30 of 60 ms, 21 TFLOP/s = 0.13 of the f32
-        // MFMA peak; profiles/r04_train_kernel_trace_summary.txt before / after).
-        static const int lone_env = getenv("PA_DW_UNITS") ? atoi(getenv("PA_DW_UNITS")) : 0;
-        const int want = lone_env > 0 ? lone_env : 512;
-        for (int i = 0; i < n; ++i)
-            if (m->dwq[i].splitk == 0) { const int s = want / tiles[i]; sk[i] = s < 1 ? 1 : (s > cap[i] ? cap[i] : s); }
-    } else {
-    static const int budget_env = getenv("PA_DW_BUDGET") ? atoi(getenv("PA_DW_BUDGET")) : 0;
-    // whole rounds of the 256 CUs: one round for the benchmark model, more when the unsplit tiles already exceed it
-    const int budget = budget_env > 0 ? budget_env : (total + 255) / 256 * 256;
-    for (;;) {
-        int best = -1, len = 0;
-        for (int i = 0; i < n; ++i) {
-            const int li = (nkt[i] + sk[i] - 1) / sk[i];
-            if (li > len) { len = li; best = i; }
-        }
-        if (best < 0 || sk[best] >= cap[best] || total + tiles[best] > budget) break;
-        ++sk[best]; total += tiles[best];
-    }
-    }
-    for (int i = 0; i < n; ++i) {
-        pa_gemm_args& g = m->dwq[i];
-        if (g.splitk > 0) continue;
-        int s = pa_gemm_effective_splitk(g.K, g.in_dtype, sk[i]);
-        const size_t need = (size_t)s * g.M * g.N;
-        if (s > 1 && !(m->ndefer < PA_MAX_REDUCE && m->slab_used + need <= m->splitws_floats)) s = 1;
-        g.splitk = s; g.ws = m->splitws; g.splitk_defer = 0;
-        if (s > 1) {
-            g.ws = m->splitws + m->slab_used;
-            g.splitk_defer = 1;
-            pa_reduce_desc& rd = m->defer[m->ndefer++];
-            rd.ws = (const float*)g.ws; rd.out = (float*)g.C; rd.rows = g.M; rd.cols = g.N; rd.ld_out = g.ldc; rd.splitk = s;
-            m->slab_used += (need + 3) / 4 * 4;
-        }
-    }
-}
+// enqueue the segment's queued work: the grouped weight-gradient GEMM (one by one where pa_gemm_group declines: exact f32), then
+// LayerNorm gamma/beta finishes + bias column sums + split-K slab reductions in one launch
 int flush_segment(pa_model* m, void* q) {
-    if (m->ndwq > 0) {                                     // all weight-gradient GEMMs of the segment: one ring-kernel launch
-        plan_group(m);
+    if (m->ndwq > 0) {
         int rc = m->ndwq > 1 ? pa_gemm_group(m->dwq, m->ndwq, q) : PA_EINVAL;
         if (rc == PA_EINVAL) { rc = 0; for (int i = 0; i < m->ndwq && !rc; ++i) rc = pa_gemm(&m->dwq[i], q); }
         m->ndwq = 0;
         RC(rc);
     }
-    // LayerNorm gamma/beta finishes + bias column sums + split-K slab reductions of the segment: one launch
     if (m->nlnq > 0 || m->ncs > 0 || m->ndefer > 0) {
         RC(pa_segment_tail(m->lnq, m->nlnq, m->cfg.d_model, m->cs, m->ncs, m->cfg.dtype, m->defer, m->ndefer, q));
-        m->nlnq = 0; m->ncs = 0; m->ndefer = 0; m->slab_used = 0;
+        m->nlnq = 0; m->ncs = 0; m->ndefer = 0;
     }
     return 0;
 }
-// main stream waits for the side-stream work of parity `par` (if any is outstanding)
-int join_side(pa_model* m, int par, void* st) {
-    if (m->ev_pending[par]) {
-        HC(hipStreamWaitEvent((hipStream_t)st, (hipEvent_t)m->ev_done[par], 0));
-        m->ev_pending[par] = false;
-    }
-    return 0;
+int segment_kind(const pa_model_cfg& c, int seg) {
+    const int es = seg - (c.n_dec + 3);
+    return seg == 0 ? SEG_HEADS : seg <= c.n_dec ? SEG_DEC : es >= 0 && es < c.n_enc ? SEG_ENC : SEG_KINDS;
 }
 int backward_segment(pa_model* m, int seg, float gscale, void* st) {
-    const int par = seg & 1;
-    m->ndefer = 0; m->slab_used = 0; m->ncs = 0; m->ndwq = 0; m->nlnq = 0;
+    m->ndefer = 0; m->ncs = 0; m->ndwq = 0; m->nlnq = 0;
     // heads and layer segments: every buffer the queued work reads (dY of the weight / bias gradients, LayerNorm partials)
     // is written once per segment and stays untouched until its end
     m->defer_ok = seg != m->cfg.n_dec + 1 && seg != m->cfg.n_dec + 2;
-    if (m->side_on) {
-        RC(join_side(m, par, st));             // segment seg-2 used this parity set: its queued work must be finished
-        m->select_set(par);
-    }
+    m->dw_n = dw_members(m->cfg, segment_kind(m->cfg, seg), m->B * m->T, m->NE, m->dw_shape);
+    plan_dw(m->cfg.dtype, m->cfg.dtype == PA_F32 && pa_gemm_split_active(), m->dw_shape, m->dw_n, m->splitws_floats, &m->dw_plan);
     RC(backward_segment_body(m, seg, gscale, st));
     m->defer_ok = false;
-    const bool queued = m->ndwq > 0 || m->nlnq > 0 || m->ncs > 0 || m->ndefer > 0;
-    // (bf16x3 mode: the queued GEMMs cut their operands into the process-wide split scratch, which the next segment's GEMMs on
-    // the main stream reuse - the queued work stays on the main stream)
-    if (queued && m->side_on && !pa_gemm_split_active()) {
-        HC(hipEventRecord((hipEvent_t)m->ev_ready[par], (hipStream_t)st));
-        HC(hipStreamWaitEvent((hipStream_t)m->side, (hipEvent_t)m->ev_ready[par], 0));
-        RC(flush_segment(m, m->side));
-        HC(hipEventRecord((hipEvent_t)m->ev_done[par], (hipStream_t)m->side));
-        m->ev_pending[par] = true;
-    } else if (queued) {
-        RC(flush_segment(m, st));
-    }
-    return 0;
+    return flush_segment(m, st);
 }
 int backward_segment_body(pa_model* m, int seg, float gscale, void* st) {
     const pa_model_cfg& c = m->cfg;
@@ -711,8 +638,7 @@ int backward_segment_body(pa_model* m, int seg, float gscale, void* st) {
 
 }  // namespace
 
-extern "C" int pa_model_create(const pa_model_cfg* cfg, pa_model** out) {
-    if (!cfg || !out) return PA_EINVAL;
+static int check_cfg(const pa_model_cfg* cfg) {
     if (cfg->d_model <= 0 || cfg->n_head <= 0 || cfg->d_model % cfg->n_head) return PA_EINVAL;
     const int dh = cfg->d_model / cfg->n_head;
     if (dh != 16 && dh != 32 && dh != 64) return PA_ESHAPE;
@@ -720,29 +646,18 @@ extern "C" int pa_model_create(const pa_model_cfg* cfg, pa_model** out) {
     if (cfg->dtype != PA_F32 && cfg->dtype != PA_BF16) return PA_EINVAL;
     if (cfg->dropout < 0.f || cfg->dropout >= 1.f) return PA_EINVAL;
     if (cfg->activation < 0 || cfg->activation > 2) return PA_EINVAL;
+    return 0;
+}
+
+extern "C" int pa_model_create(const pa_model_cfg* cfg, pa_model** out) {
+    if (!cfg || !out) return PA_EINVAL;
+    RC(check_cfg(cfg));
     pa_model* m = new (std::nothrow) pa_model();
     if (!m) return PA_EINVAL;
     m->cfg = *cfg;
     m->n_params = P_FIXED_HEAD + cfg->n_enc * E_COUNT + 2 + cfg->n_dec * D_COUNT + 2 + T_COUNT;
     m->pf.assign(m->n_params, nullptr); m->pl.assign(m->n_params, nullptr); m->gr.assign(m->n_params, nullptr);
     m->plT.assign(m->n_params, nullptr);
-    // Optional side stream for the queued end-of-segment backward work (PA_SIDE_STREAM=1).  Off by default: measured
-    // on MI355X the event fences cost more than the overlap gains (7.68 vs 7.49 ms/step, profiles/README.md).
-    const char* ss = getenv("PA_SIDE_STREAM");
-    if (ss && atoi(ss) != 0) {
-        hipStream_t q = nullptr;
-        bool ok = hipStreamCreateWithFlags(&q, hipStreamNonBlocking) == hipSuccess;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int i = 0; i < 4 && ok; ++i) ok = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
-        if (ok) {
-            m->side = q; m->ev_ready[0] = ev[0]; m->ev_ready[1] = ev[1]; m->ev_done[0] = ev[2]; m->ev_done[1] = ev[3];
-            m->side_on = true;
-        } else {
-            for (int i = 0; i < 4; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
-            if (q) (void)hipStreamDestroy(q);
-            (void)hipGetLastError();
-        }
-    }
     *out = m;
     return 0;
 }
@@ -750,13 +665,32 @@ extern "C" int pa_model_create(const pa_model_cfg* cfg, pa_model** out) {
 void pa_decode_free_layout(pa_model* m);   // decode.hip
 extern "C" void pa_model_destroy(pa_model* m) {
     if (!m) return;
-    for (int i = 0; i < 2; ++i) {
-        if (m->ev_ready[i]) (void)hipEventDestroy((hipEvent_t)m->ev_ready[i]);
-        if (m->ev_done[i]) (void)hipEventDestroy((hipEvent_t)m->ev_done[i]);
-    }
-    if (m->side) (void)hipStreamDestroy((hipStream_t)m->side);
     pa_decode_free_layout(m);
     delete m;
+}
+
+// The dry run of the step's host side (include/plank_hip.h): the layout function and the plan function of the real calls, over a
+// model object of its own.
+static_assert(sizeof(pa_train_plan_info) == 32 + 3 * PA_MAX_GROUP * 24, "pa_train_plan_info (plankassembly_amd/_lib.py mirrors it)");
+extern "C" int pa_train_plan(const pa_model_cfg* cfg, int32_t B, int32_t S, int32_t T, int32_t n_valid, pa_train_plan_info* out) {
+    if (!cfg || !out) return PA_EINVAL;
+    RC(check_cfg(cfg));
+    if (B <= 0 || S <= 0 || T <= 0 || n_valid < 0 || n_valid > (int64_t)B * S) return PA_EINVAL;
+    pa_model m;
+    m.cfg = *cfg;
+    memset(out, 0, sizeof(*out));
+    out->ws_bytes = (int64_t)pa_train_layout(&m, nullptr, B, S, T) + 256;
+    out->splitws_floats = (int64_t)m.splitws_floats;
+    out->n_segments = cfg->n_dec + cfg->n_enc + 4;
+    const bool x3 = cfg->dtype == PA_F32 && pa_gemm_split_active();
+    for (int kind = 0; kind < SEG_KINDS; ++kind) {
+        DwShape sh[PA_MAX_GROUP]; DwPlan pl;
+        const int n = dw_members(*cfg, kind, B * T, n_valid ? n_valid : B * S, sh);
+        plan_dw(cfg->dtype, x3, sh, n, m.splitws_floats, &pl);
+        out->n_members[kind] = n;
+        for (int i = 0; i < n; ++i) out->member[kind][i] = {sh[i].rows, sh[i].cols, sh[i].k, pl.splitk[i], pl.slab[i]};
+    }
+    return 0;
 }
 
 extern "C" int pa_model_num_params(const pa_model* m) { return m ? m->n_params : PA_EINVAL; }
@@ -840,12 +774,8 @@ extern "C" int pa_model_train_bwd(pa_model* m, int32_t seg_lo, int32_t seg_hi, f
     const int nseg = m->cfg.n_dec + m->cfg.n_enc + 4;
     if (seg_lo < 0 || seg_hi > nseg || seg_lo > seg_hi) return PA_EINVAL;
     for (int s = seg_lo; s < seg_hi; ++s) RC(backward_segment(m, s, gscale, stream));
-    if (seg_hi == nseg && m->side_on) { RC(join_side(m, 0, stream)); RC(join_side(m, 1, stream)); m->select_set(0); }
     return 0;
 }
-// Segments by which gradient finality lags behind pa_model_train_bwd: with the side stream on, the gradients of segment
-// s are final (in `stream` order) once segment s+2 has been enqueued, or after the last segment.  0 = immediately.
-extern "C" int pa_model_grad_lag(const pa_model* m) { return (m && m->side_on) ? 2 : 0; }
 
 extern "C" int pa_model_tensor(pa_model* m, int32_t which, void** ptr, int64_t* numel) {
     if (!m || !ptr || !numel || m->B == 0) return PA_EINVAL;

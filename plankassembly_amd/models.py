@@ -893,8 +893,6 @@ class PlankModel(nn.Module):
         # buffer accumulated so far was already summed over the ranks - and is added to _gflat after the last slice
         hook = self._grad_hook
         self._sync_target = target
-        # with the library's side stream the gradients of segment s are final once segment s + lag is enqueued
-        lag = int(L.lib().pa_model_grad_lag(self._handle))
         for s in range(nseg):
             self._split(True, retain=True)
             try:
@@ -902,10 +900,7 @@ class PlankModel(nn.Module):
                         "pa_model_train_bwd")
             finally:
                 self._split(False)
-            if hook is not None and s - lag >= 0:
-                hook(s - lag, *slices[s - lag])
-        if hook is not None:
-            for s in range(max(0, nseg - lag), nseg):       # the last segment joined everything
+            if hook is not None:
                 hook(s, *slices[s])
         if accumulate:
             self._gflat.add_(self._gtmp)        # (the hook of the last segment waited for every collective)

@@ -3,8 +3,6 @@ run A=0
 run PA_GEMM_SMALL_MAX=64
 run PA_GEMM_SMALL_MAX=192
 run PA_GEMM_SMALL_MAX=256
-run PA_DW_BUDGET=512
-run PA_DW_BUDGET=384
 run A=0
 run PA_ATTN_BWD_MERGE_MAX=256
 run PA_ATTN_KSPLIT=0
