@@ -136,6 +136,30 @@ int pa_gemm_split_cache_use(void* cache);                     /* NULL: none */
 int32_t pa_gemm_split_cache_entries(void* cache);
 int pa_gemm_split_cache_refresh(void* cache, void* stream);
 int64_t pa_gemm_split_cache_hits(void);
+/* Dry run of the mode's cut plan: what pa_gemm(args) (n == 1) or pa_gemm_group(args, n) (n > 1) would plan in the calling thread's
+ * context, made by the same plan functions the real calls run.  It launches nothing, needs no GPU and never dereferences an operand,
+ * scratch or cache pointer: only their values count.  commit != 0 advances the context (offsets, image lists, the cache's list, the
+ * process counters) exactly as the real call does, so a whole sequence of calls can be replayed.  `out`: one entry per member.
+ * Outside the mode, or for a product that is not f32, nothing is planned: taken = 0 and the caller's own arguments come back. */
+#define PA_SPLIT_SRC_CALLER 0     /* not cut: the caller's own buffer (declined, or no such operand) */
+#define PA_SPLIT_SRC_SEGMENT 1    /* found: retained by this backward segment (on = 2) */
+#define PA_SPLIT_SRC_FORWARD 2    /* found: retained by the forward (on = 3) */
+#define PA_SPLIT_SRC_MADE 3       /* found: written by the operand's producer (pa_gemm_split_reserve) */
+#define PA_SPLIT_SRC_CACHE 4      /* found in the weight-image cache */
+#define PA_SPLIT_SRC_CACHE_CUT 5  /* a cache miss: cut into the cache */
+#define PA_SPLIT_SRC_SCRATCH 6    /* cut into the scratch */
+typedef struct {
+    int32_t taken;                        /* 1: runs as bf16x3; 0: declined (pa_gemm runs it exact, pa_gemm_group returns PA_EINVAL) */
+    int32_t pat;                          /* parts pattern of A: 0 (hi, hi, lo), 1 (hi, lo, hi); B has the other one */
+    int32_t drop_seg, drop_fwd;           /* image lists the call empties to make room */
+    int32_t source[3], mode[3], blocks[3];/* A, B, aux: PA_SPLIT_SRC_*; split mode 0 .. 4 and blocks of the cut job (blocks 0: no cut) */
+    int32_t M, N, K, lda, ldb, splitk;    /* the inner call: the bf16 product over 3 K, or the exact call of a declined product */
+    int32_t nkeep, nkeepL, long_closed;   /* the context after the call: images of the segment / the forward, forward list closed */
+    int64_t off[3], bytes[3];             /* A, B, aux: image offset from the scratch base (PA_SPLIT_SRC_CACHE*: the cache base); bytes cut */
+    int64_t sA, sB;
+    int64_t keep_off, long_off;           /* the context after the call: end of the retained images / of the forward's */
+} pa_split_plan_info;
+int pa_gemm_split_plan(const pa_gemm_args* args, int32_t n, int32_t commit, pa_split_plan_info* out);
 /* Measurement hook (bench.py's roofline census; no reference counterpart): pa_gemm_record(1) starts appending every
  * pa_gemm() argument block to a host-side list; pa_gemm_record(0) returns the count so far; pa_gemm_recorded() copies
  * up to `cap` recorded blocks out and stops recording.  Replaying the blocks re-launches the same GEMMs. */
@@ -158,7 +182,8 @@ int pa_gemm_recorded_groups(int32_t* out, int32_t cap);
  * predicted) and, when that is 0, the kernel family (PA_GEMM_KIND_*), tile, grid, block size and effective split-K it would use.
  * Made by the same selection function the real calls run, under the same PA_GEMM_* switches and reserved CUs.  It launches nothing,
  * needs no GPU and never dereferences the operand pointers: only their values count, for the alignment rules.  It plans the plain
- * path and ignores the bf16x3 mode (where an f32 product is re-planned as a bf16 one over 3 K).  pa_gemm_group has no dry run. */
+ * path and ignores the bf16x3 mode (where an f32 product is re-planned as a bf16 one over 3 K: pa_gemm_split_plan reports that
+ * re-planned block).  pa_gemm_group has no dry run of its kernel choice. */
 typedef struct {
     int32_t kind;               /* PA_GEMM_KIND_* ("tall" tiles report PA_GEMM_KIND_WIDE, as the recorder does) */
     int32_t tile_h, tile_w;

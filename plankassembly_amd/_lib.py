@@ -48,6 +48,19 @@ class GemmPlanInfo(C.Structure):
                 ("block", C.c_int32), ("splitk", C.c_int32), ("units", C.c_int32), ("pad_", C.c_int32)]
 
 
+class SplitPlanInfo(C.Structure):
+    """include/plank_hip.h pa_split_plan_info: what pa_gemm_split_plan (the dry run of the bf16x3 cut plan) reports per member."""
+    _fields_ = [("taken", C.c_int32), ("pat", C.c_int32), ("drop_seg", C.c_int32), ("drop_fwd", C.c_int32),
+                ("source", C.c_int32 * 3), ("mode", C.c_int32 * 3), ("blocks", C.c_int32 * 3),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("lda", C.c_int32), ("ldb", C.c_int32), ("splitk", C.c_int32),
+                ("nkeep", C.c_int32), ("nkeepL", C.c_int32), ("long_closed", C.c_int32),
+                ("off", C.c_int64 * 3), ("bytes", C.c_int64 * 3), ("sA", C.c_int64), ("sB", C.c_int64),
+                ("keep_off", C.c_int64), ("long_off", C.c_int64)]
+
+
+SPLIT_SRC = ("caller", "segment", "forward", "made", "cache", "cache_cut", "scratch")     # PA_SPLIT_SRC_*
+
+
 class GemmLnArgs(C.Structure):
     _fields_ = [("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("R", C.c_void_p),
                 ("Z", C.c_void_p), ("Y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
@@ -201,6 +214,7 @@ def lib():
             "pa_gemm_split_cache_use": (I, [P]),
             "pa_gemm_split_cache_entries": (I, [P]),
             "pa_gemm_split_cache_refresh": (I, [P, P]),
+            "pa_gemm_split_plan": (I, [P, I, I, P]),
             "pa_layernorm_fwd_img": (I, [P, P, P, P, P, P, I64, I, F, I, P, I, P]),
             "pa_layernorm_bwd_can_img": (I, [I, I]),
             "pa_layernorm_bwd_partial_img": (I, [P, P, P, P, P, P, P, I, P, I64, I, I, F, U, P, I, P]),

@@ -2681,18 +2681,20 @@ struct SplitKeep { const void* src; int rows, cols, ld, pat; bf16* dst; int made
 // was written by its producer needs no split launch at all.
 constexpr int SPLIT_CACHE_MAX = 320, SPLIT_CACHE_HEAD = 32768;         // (the head of the buffer holds the device copy of the job table)
 struct SplitCache { char* buf; long long bytes, used; int n; bool table_stale; SplitKeep e[SPLIT_CACHE_MAX]; };
-struct SplitState {
+constexpr int KEEP_SEG_MAX = 16, KEEP_FWD_MAX = 128;
+// what a cut plan advances: the scratch offsets, the lengths of the two image lists, the forward list closed by an overflow
+struct SplitPos { long long long_off = 0, keep_off = 0; int nkeep = 0, nkeepL = 0; bool long_closed = false; };
+struct SplitState : SplitPos {
     std::atomic<int> on{0}; char* ws = nullptr; long long bytes = 0;
     std::atomic<int> attn{0};                  // the attention launches of this context run split too (pa_attn_split_config)
     // Retained images.  A k-contiguous operand cut as [rows][3 cols] and read as [3 rows][cols] IS its stacked form with the planes
     // interleaved row by row, so the image one GEMM built serves a later GEMM that contracts over the ROWS of the same buffer:
     //   retain 1 (pa_gemm_split_config(2, ..): a backward segment): dY of every dX GEMM stays at [long_off, keep_off) until the next
-    //            config call - the segment's grouped weight-gradient launch finds it already cut (gemm_group_split3);
+    //            config call - the segment's grouped weight-gradient launch finds it already cut (plan_group_split3);
     //   retain 2 (pa_gemm_split_config(3, ..): the forward): X of every Linear stays at [0, long_off) until the next forward (config 3)
     //            or a plain config (1) - the same grouped launch finds its OTHER operand already cut as well.
     // Forward images are (hi, hi, lo); a backward segment cuts dY as (hi, lo, hi) so that the two meet in one product.
-    int retain = 0; long long long_off = 0, keep_off = 0; bool long_closed = false;
-    SplitKeep keep[16]; int nkeep = 0; SplitKeep keepL[128]; int nkeepL = 0; SplitCache* cache = nullptr;
+    int retain = 0; SplitKeep keep[KEEP_SEG_MAX]; SplitKeep keepL[KEEP_FWD_MAX]; SplitCache* cache = nullptr;
     // a weight gradient's dY operand is looked up among this segment's images only, its X operand among the forward's only: backward
     // buffers may reuse addresses of forward buffers that are dead by then
     static const SplitKeep* find_in(const SplitKeep* t, int n, const void* src, int rows, int cols, int ld) {
@@ -2826,6 +2828,193 @@ __global__ __launch_bounds__(256) void split_many_kernel(const SplitJob* jobs, c
     const SplitJob J = jobs[lo];
     split_job(J, blockIdx.x - begin[lo], begin[lo + 1] - begin[lo]);
 }
+
+// ---- the cut plan (DESIGN.md "bf16x3 plan"): plan_*split3 decide, commit_split3 advances the context, launch_cuts launches, pa_gemm_split_plan reports
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+inline long long img_bytes(long long bf16_elems) { return (bf16_elems * 2 + 255) / 256 * 256; }    // regions of the scratch are 256-byte aligned
+// blocks of one cut job: one 8-element vector per thread up to `cap` blocks (measured for pa_gemm: 2 per thread / 2 048 blocks 12.25 ms
+// per step, 1 / 8 192 12.14).  Each call site keeps the cap it was measured with; nobody has measured one cap for all.
+constexpr int CUT_CAP_GEMM = 16384, CUT_CAP_GROUP = 8192, CUT_CAP_REFRESH = 4096;
+inline int cut_blocks(const SplitJob& j, int cap) {
+    const long long blocks = ((long long)j.rows * (j.cols >> 3) * j.batch + 255) / 256;
+    return (int)(blocks < 1 ? 1 : blocks > cap ? cap : blocks);
+}
+// Room to retain one more image when the call needs `need` bytes behind the retained ones.  The forward (retain 2) keeps while its list
+// is open and a quarter of the buffer stays free for the segments' own cuts; a segment (retain 1) up to its list's length, and an
+// image made by its producer only below 7/8 of the buffer.
+inline bool keep_room(const SplitState& st, const SplitPos& p, long long need, bool producer) {
+    if (st.retain == 2) return !p.long_closed && p.nkeepL < KEEP_FWD_MAX && p.long_off + need <= st.bytes - st.bytes / 4;
+    return st.retain == 1 && p.nkeep < KEEP_SEG_MAX && (!producer || p.keep_off + need <= st.bytes - st.bytes / 8);
+}
+// the positions after an image of `src` was retained at keep_off (a buffer cut again replaces its older image), and the list entry itself
+inline void keep_advance(SplitPos& p, const SplitState& st, const void* src, long long bytes) {
+    const bool fwd = st.retain == 2;
+    const SplitKeep* t = fwd ? st.keepL : st.keep;
+    int& n = fwd ? p.nkeepL : p.nkeep;
+    n += std::none_of(t, t + n, [src](const SplitKeep& e) { return e.src == src; });
+    p.keep_off += bytes;
+    if (fwd) p.long_off = p.keep_off;
+}
+inline void keep_put(SplitState& st, const SplitKeep& e) { SplitState::put(st.retain == 2 ? st.keepL : st.keep, st.retain == 2 ? st.nkeepL : st.nkeep, e); }
+struct SplitPlan {
+    bool taken = false, group = false, drop_seg = false, drop_fwd = false;      // drop_*: image lists the call empties to make room
+    int n = 1; SplitPos after; SplitKeep kept = {}, cached = {};   // after: the positions after the call; (src != NULL) the image it retains / the cache learns
+    int made_hits = 0, cache_hits = 0, reused = 0, exact_want = 0;       // counter increments; declined deferred split-K: slabs the reducer reads
+    pa_split_plan_info info[PA_MAX_GROUP_];              // per member: parts pattern, and per operand (A, B, aux) source, offset, bytes cut, mode
+    SplitJob job[PA_MAX_GROUP_][3];                      // .. and its cut job (info.bytes > 0) or just the image (dst)
+    pa_gemm_args inner[PA_MAX_GROUP_];                   // taken: the bf16 products over 3 K; declined: the exact call
+};
+// operand k of member i: its image `at` an address of the scratch / cache that starts at `base`, found there (bytes 0) or cut there by job j
+inline bf16* set_image(SplitPlan& p, int i, int k, int source, const char* base, const void* at, long long bytes = 0, SplitJob j = SplitJob()) {
+    pa_split_plan_info& o = p.info[i];
+    j.dst = static_cast<bf16*>(const_cast<void*>(at));
+    o.source[k] = source; o.off[k] = static_cast<const char*>(at) - base; o.bytes[k] = bytes; o.mode[k] = j.mode;
+    o.blocks[k] = bytes ? cut_blocks(j, p.group ? CUT_CAP_GROUP : CUT_CAP_GEMM) : 0;
+    p.job[i][k] = j;
+    return j.dst;
+}
+// Retained images of a product whose operands both have a strided contraction index (a weight gradient dY^T X): either may have been cut
+// before as the k-contiguous operand of an earlier GEMM - dY ([K rows][M features]) by this segment's dX GEMM, X by the forward's Linear,
+// in the opposite parts pattern - and [K][3 M] read as [3 K][M] IS the stacked operand with the planes interleaved row by row.  Whichever
+// is missing is then cut into the matching interleaving (split modes 0 / 1) instead of the plane-stacked modes 2 / 3.
+struct SplitHits { const SplitKeep *a, *b; int pat; };
+inline SplitHits find_stacked(const SplitState& st, const pa_gemm_args& a, int pat_default) {
+    SplitHits h{st.find_seg(a.A, a.K, a.M, a.lda), st.find_fwd(a.B, a.K, a.N, a.ldb), pat_default};
+    if (h.a) h.pat = h.a->pat; else if (h.b) h.pat = 1 - h.b->pat;
+    if (h.b && h.b->pat == h.pat) h.b = nullptr;
+    return h;
+}
+// The cuts of one pa_gemm call.  false: declined (what p holds by then is still committed: images dropped for room stay dropped)
+bool plan_cuts(SplitPlan& p, const pa_gemm_args& a, const SplitState& st) {
+    SplitPos& pos = p.after; pa_gemm_args& b = p.inner[0];
+    const bool akc = a.a_kcontig != 0, bkc = a.b_kcontig != 0;
+    const int M = a.M, N = a.N, K = a.K, nb = a.batch;
+    const int ar = akc ? M : K, ac = akc ? K : M, br = bkc ? N : K, bc = bkc ? K : N;             // source rows / cols of each operand as stored
+    if ((ac & 7) || (bc & 7) || (a.lda & 3) || (a.ldb & 3) || (a.sA & 3) || (a.sB & 3) || !al16(a.A) || !al16(a.B)) return false;
+    if ((long long)ar * ac * nb >= (1ll << 33) || (long long)br * bc * nb >= (1ll << 33) || (long long)M * N * nb >= (1ll << 33)) return false;   // (split_kernel indexes 8-element vectors in 32 bits)
+    if ((akc && bkc && (K & 63)) || a.C_lp) return false;     // the bf16 fast paths want whole K tiles per part
+    if (a.aux && ((N & 7) || (a.ldaux & 3) || (a.sAux & 3) || !al16(a.aux))) return false;
+    const int a_nb = nb > 1 && a.sA == 0 ? 1 : nb, b_nb = nb > 1 && a.sB == 0 ? 1 : nb;            // (an operand shared by the batch is cut once)
+    const long long a_el = (long long)ar * ac * 3, b_el = (long long)br * bc * 3, x_el = a.aux ? (long long)M * N : 0;
+    // parts pattern: the forward and plain mode cut A as (hi, hi, lo) and B as (hi, lo, hi), a backward segment the other way round
+    // (its retained dY images then meet the forward's retained X images in the weight-gradient product)
+    const int pat_default = st.retain == 1 ? 1 : 0;
+    const bool stacked2 = !akc && !bkc && nb == 1;
+    const SplitHits none{nullptr, nullptr, pat_default};
+    SplitHits h = stacked2 ? find_stacked(st, a, pat_default) : none;
+    // a k-contiguous A whose image was written by the kernel that produced A (pa_gemm_split_reserve) ..
+    const SplitKeep* made = !akc || nb != 1 || !st.retain ? nullptr : st.retain == 2 ? SplitState::find_in(st.keepL, st.nkeepL, a.A, ar, ac, a.lda)
+                                                                                         : st.find_seg(a.A, ar, ac, a.lda);
+    if (made && made->made && made->pat == h.pat) { h.a = made; p.made_hits = 1; } else made = nullptr;
+    // .. and a constant k-contiguous B (a weight) held in the model's cache; a miss is cut INTO the cache
+    const SplitCache* const wc = bkc && nb == 1 ? st.cache : nullptr;
+    const SplitKeep* cache_b = nullptr;
+    for (int k = 0; wc && k < wc->n && !cache_b; ++k) {
+        const SplitKeep& e = wc->e[k];
+        if (e.src == a.B && e.rows == br && e.cols == bc && e.ld == a.ldb && e.pat == 1 - h.pat) { cache_b = &e; p.cache_hits = 1; }
+    }
+    if (wc && !cache_b && wc->n < SPLIT_CACHE_MAX && wc->used + img_bytes(b_el) <= wc->bytes)
+        p.cached = SplitKeep{a.B, br, bc, a.ldb, 1 - h.pat, reinterpret_cast<bf16*>(wc->buf + wc->used), 0};
+    const long long a_bytes = img_bytes(a_el * a_nb), b_bytes = cache_b || p.cached.src ? 0 : img_bytes(b_el * b_nb), x_bytes = img_bytes(x_el * nb);
+    long long all = a_bytes + b_bytes + x_bytes, need = (h.a ? 0 : a_bytes) + (h.b ? 0 : b_bytes) + x_bytes;
+    if (st.retain == 2) {
+        // forward: does not fit behind the retained images - drop them and close the list (the images found may be the dropped ones)
+        if (pos.long_off + need > st.bytes) {
+            pos.long_off = 0; pos.nkeepL = 0; pos.long_closed = true; p.drop_fwd = true; h = none; need = all;
+            if (need > st.bytes) return false;
+        }
+        pos.keep_off = pos.long_off;
+    } else if (pos.keep_off + need > st.bytes) {
+        // drop this segment's images, then the forward's (stream order keeps their earlier readers safe)
+        pos.keep_off = pos.long_off; pos.nkeep = 0; p.drop_seg = true; h = none; need = all;
+        if (pos.keep_off + need > st.bytes) {
+            pos.long_off = 0; pos.nkeepL = 0; pos.keep_off = 0; p.drop_fwd = true;
+            if (need > st.bytes) return false;
+        }
+    }
+    const bool keep_a = !h.a && akc && nb == 1 && keep_room(st, pos, need, false);
+    // split-K: callers size their slabs with pa_gemm_effective_splitk(K, PA_F32, .), which in this mode already counts whole
+    // 64-wide tiles of the 3 K long bf16 contraction - the request passes through unchanged
+    if (a.splitk > 1 && !a.ws) return false;
+    const bool inter = stacked2 && (h.a || h.b);               // row-interleaved stacking: split modes 0 / 1 instead of 2 / 3
+    if (inter) p.reused = (h.a ? 1 : 0) + (h.b ? 1 : 0);
+    const int a_mode = (akc || inter ? 0 : 2) + h.pat, b_mode = (bkc || inter ? 0 : 2) + (1 - h.pat);
+    const SplitJob ja{static_cast<const float*>(a.A), nullptr, ar, ac, a.lda, a_mode, a.sA, a_el, a_nb, 0};
+    const SplitJob jb{static_cast<const float*>(a.B), nullptr, br, bc, a.ldb, b_mode, a.sB, b_el, b_nb, 0};
+    const SplitJob jx{static_cast<const float*>(a.aux), nullptr, M, N, a.ldaux, 4, a.sAux, x_el, nb, 0};
+    const char* at = st.ws + pos.keep_off;
+    p.info[0].pat = h.pat;
+    b.A = h.a ? set_image(p, 0, 0, h.a == made ? PA_SPLIT_SRC_MADE : PA_SPLIT_SRC_SEGMENT, st.ws, h.a->dst) : set_image(p, 0, 0, PA_SPLIT_SRC_SCRATCH, st.ws, at, a_bytes, ja);
+    if (keep_a) { p.kept = SplitKeep{a.A, ar, ac, a.lda, h.pat, static_cast<bf16*>(const_cast<void*>(b.A)), 0}; keep_advance(pos, st, a.A, a_bytes); }
+    if (!h.a) at += a_bytes;
+    if (p.cached.src) b.B = set_image(p, 0, 1, PA_SPLIT_SRC_CACHE_CUT, wc->buf, p.cached.dst, img_bytes(b_el), jb);
+    else if (cache_b) b.B = set_image(p, 0, 1, PA_SPLIT_SRC_CACHE, wc->buf, cache_b->dst);
+    else if (h.b) b.B = set_image(p, 0, 1, PA_SPLIT_SRC_FORWARD, st.ws, h.b->dst);
+    else { b.B = set_image(p, 0, 1, PA_SPLIT_SRC_SCRATCH, st.ws, at, b_bytes, jb); at += b_bytes; }
+    if (a.aux) { b.aux = set_image(p, 0, 2, PA_SPLIT_SRC_SCRATCH, st.ws, at, x_bytes, jx); b.ldaux = N; b.sAux = x_el; }
+    b.in_dtype = PA_BF16; b.K = 3 * K; b.splitk = a.splitk > 1 ? a.splitk : 1;
+    b.lda = akc ? 3 * K : M; b.ldb = bkc ? 3 * K : N; b.sA = a_nb < nb ? 0 : a_el; b.sB = b_nb < nb ? 0 : b_el;
+    return true;
+}
+SplitPlan plan_split3(const pa_gemm_args& a, const SplitState& st) {
+    SplitPlan p; p.after = st; p.info[0] = pa_split_plan_info(); p.inner[0] = a;
+    p.taken = plan_cuts(p, a, st);
+    if (!p.taken && a.splitk > 1 && a.splitk_defer && a.ws) {
+        // the caller's reduction descriptor counts pa_gemm_effective_splitk(K, PA_F32, splitk) slabs in THIS mode's (bf16) tiling; the exact
+        // kernel writes the f32 tiling's count: it runs with a request that yields no more than that, and the reducer gets zeros for the rest
+        int& req = p.inner[0].splitk = p.exact_want = eff_splitk((3 * a.K + 63) / 64, a.splitk);
+        while (req > 1 && eff_splitk((a.K + 15) / 16, req) > p.exact_want) --req;
+    }
+    return p;
+}
+// The cuts of one pa_gemm_group call: every member's two operands go into their stacked forms in consecutive regions behind the
+// images this segment retained, by ONE split launch; the members then run as one grouped bf16 launch over 3 K rows each.  All or none.
+SplitPlan plan_group_split3(const pa_gemm_args* args, int n, const SplitState& st) {
+    SplitPlan p; p.group = true; p.n = n; p.after = st;
+    long long off = st.keep_off;
+    for (int i = 0; i < n; ++i) {
+        const pa_gemm_args& a = args[i];
+        if (a.in_dtype != PA_F32 || a.out_dtype != PA_F32 || a.a_kcontig || a.b_kcontig || a.batch != 1) return p;
+        if (a.bias || a.R || a.aux || a.relu || a.drop_p > 0.f || a.alpha != 1.f || a.C_lp) return p;
+        if ((a.M & 7) || (a.N & 7) || (a.lda & 3) || (a.ldb & 3) || !al16(a.A) || !al16(a.B)) return p;
+        if ((long long)a.K * a.M >= (1ll << 33) || (long long)a.K * a.N >= (1ll << 33)) return p;
+        const SplitHits h = find_stacked(st, a, 0);
+        const long long a_bytes = h.a ? 0 : img_bytes((long long)a.K * a.M * 3), b_bytes = h.b ? 0 : img_bytes((long long)a.K * a.N * 3);
+        if (off + a_bytes + b_bytes > st.bytes) return p;
+        const int mode = h.a || h.b ? 0 : 2;
+        pa_gemm_args& b = p.inner[i] = a;
+        p.info[i] = pa_split_plan_info(); p.info[i].pat = h.pat;
+        b.A = h.a ? set_image(p, i, 0, PA_SPLIT_SRC_SEGMENT, st.ws, h.a->dst) : set_image(p, i, 0, PA_SPLIT_SRC_SCRATCH, st.ws, st.ws + off, a_bytes,
+                        SplitJob{static_cast<const float*>(a.A), nullptr, a.K, a.M, a.lda, mode + h.pat, 0, 0, 1, 0});
+        b.B = h.b ? set_image(p, i, 1, PA_SPLIT_SRC_FORWARD, st.ws, h.b->dst) : set_image(p, i, 1, PA_SPLIT_SRC_SCRATCH, st.ws, st.ws + off + a_bytes, b_bytes,
+                        SplitJob{static_cast<const float*>(a.B), nullptr, a.K, a.N, a.ldb, mode + 1 - h.pat, 0, 0, 1, 0});
+        off += a_bytes + b_bytes;
+        p.reused += (h.a ? 1 : 0) + (h.b ? 1 : 0);            // (counted only if the whole group is taken: commit_split3)
+        b.in_dtype = PA_BF16; b.K = 3 * a.K; b.lda = a.M; b.ldb = a.N;
+    }
+    p.taken = true;
+    return p;
+}
+// The only place that advances a context, its cache's list and the process counters.
+void commit_split3(SplitState& st, const SplitPlan& p) {
+    if (p.drop_seg) st.nkeep = 0;
+    if (p.drop_fwd) st.nkeepL = 0;
+    if (p.kept.src) keep_put(st, p.kept);                    // (after the drops: the kept image is the call's own)
+    static_cast<SplitPos&>(st) = p.after;
+    if (p.cached.src) { SplitCache& c = *st.cache; c.e[c.n++] = p.cached; c.used += img_bytes((long long)p.cached.rows * p.cached.cols * 3); c.table_stale = true; }
+    if (p.taken) g_cnt.taken.fetch_add(p.n); else if (!p.group) g_cnt.declined.fetch_add(1);
+    if (p.taken && p.reused) g_cnt.reused.fetch_add(p.reused);
+    if (p.made_hits) g_cnt.made_hits.fetch_add(p.made_hits);
+    if (p.cache_hits) g_cnt.cache_hits.fetch_add(p.cache_hits);
+}
+int launch_cuts(const SplitPlan& p, void* stream) {
+    SplitTab tb; tb.n = 0; tb.begin[0] = 0;
+    for (int i = 0; i < p.n; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (p.info[i].bytes[k]) { tb.j[tb.n] = p.job[i][k]; tb.begin[tb.n + 1] = tb.begin[tb.n] + p.info[i].blocks[k]; ++tb.n; }
+    if (tb.n) PA_LAUNCH(split_kernel, dim3(tb.begin[tb.n]), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tb);
+    return 0;
+}
 }  // namespace
 extern "C" int pa_gemm_split_config(int32_t on, void* ws, int64_t bytes) {
     if (on && (!ws || bytes <= 0 || (reinterpret_cast<uintptr_t>(ws) & 255))) return PA_EINVAL;
@@ -2846,24 +3035,17 @@ extern "C" int64_t pa_gemm_split_cache_hits(void) { return g_cnt.cache_hits.load
 // its cut image ([rows][3 cols], parts pattern *pat: 0 (hi, hi, lo), 1 (hi, lo, hi)) to the returned address, and the GEMM that
 // consumes `src` as its k-contiguous A operand skips its own cut.  NULL: no image wanted (mode off, no retain mode, no room).
 extern "C" void* pa_gemm_split_reserve(const void* src, int32_t rows, int32_t cols, int32_t ld, int32_t* pat) {
-    if (!split_on() || !g_split.retain || !src || rows <= 0 || cols <= 0 || (cols & 7)) return nullptr;
-    static const bool off = getenv("PA_SPLIT_RESERVE") && atoi(getenv("PA_SPLIT_RESERVE")) == 0;
-    if (off) return nullptr;
-    const long long bytes = ((long long)rows * cols * 6 + 255) / 256 * 256;
-    bf16* dst;
-    if (g_split.retain == 2) {
-        if (g_split.long_closed || g_split.nkeepL >= 128 || g_split.long_off + bytes > g_split.bytes - g_split.bytes / 4) return nullptr;
-        dst = reinterpret_cast<bf16*>(g_split.ws + g_split.long_off);
-        SplitState::put(g_split.keepL, g_split.nkeepL, SplitKeep{src, rows, cols, ld, 0, dst, 1});
-        g_split.long_off += bytes; g_split.keep_off = g_split.long_off;
-        if (pat) *pat = 0;
-    } else {
-        if (g_split.nkeep >= 16 || g_split.keep_off + bytes > g_split.bytes - g_split.bytes / 8) return nullptr;
-        dst = reinterpret_cast<bf16*>(g_split.ws + g_split.keep_off);
-        SplitState::put(g_split.keep, g_split.nkeep, SplitKeep{src, rows, cols, ld, 1, dst, 1});
-        g_split.keep_off += bytes;
-        if (pat) *pat = 1;
-    }
+    SplitState& st = cur_split();
+    if (!split_on() || !st.retain || !src || rows <= 0 || cols <= 0 || (cols & 7)) return nullptr;
+    const long long bytes = img_bytes((long long)rows * cols * 3);
+    if (!keep_room(st, st, bytes, true)) return nullptr;
+    bf16* dst = reinterpret_cast<bf16*>(st.ws + st.keep_off);  // (the forward's images lie back to back: keep_off == long_off in its mode)
+    const int p = st.retain == 2 ? 0 : 1;                      // the parts pattern the consuming GEMM of this mode cuts A in
+    SplitPos after = st;
+    keep_advance(after, st, src, bytes);
+    keep_put(st, SplitKeep{src, rows, cols, ld, p, dst, 1});
+    static_cast<SplitPos&>(st) = after;
+    if (pat) *pat = p;
     return dst;
 }
 extern "C" int pa_gemm_split_cache_create(void* buf, int64_t bytes, void** out) {
@@ -2893,18 +3075,10 @@ extern "C" int pa_gemm_split_cache_refresh(void* h, void* stream) {
     std::vector<SplitJob> jobs(c->n);
     for (int k = 0; k < c->n; ++k) {
         const SplitKeep& e = c->e[k];
-        SplitJob& j = jobs[k];
-        j.src = static_cast<const float*>(e.src); j.dst = e.dst; j.rows = e.rows; j.cols = e.cols; j.ld = e.ld; j.mode = e.pat;
-        j.sstride = 0; j.dstride = 0; j.batch = 1; j.pad_ = 0;
-        long long blocks = ((long long)e.rows * (e.cols >> 3) + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 4096) blocks = 4096;
-        begin[k + 1] = begin[k] + (int)blocks;
+        jobs[k] = SplitJob{static_cast<const float*>(e.src), e.dst, e.rows, e.cols, e.ld, e.pat, 0, 0, 1, 0};
+        begin[k + 1] = begin[k] + cut_blocks(jobs[k], CUT_CAP_REFRESH);
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static const bool dbg = getenv("PA_SPLIT_DEBUG") && atoi(getenv("PA_SPLIT_DEBUG"));
-    if (dbg) fprintf(stderr, "[pa_gemm x3 cache] refresh: %d images, %lld of %lld bytes, table %s, %d blocks\n", c->n, c->used, c->bytes,
-                     c->table_stale ? "uploaded" : "resident", begin[c->n]);
     if (c->table_stale) {
         // (only while the list is still growing: the first two steps)
         if (hipMemcpyAsync(dj, jobs.data(), jobs.size() * sizeof(SplitJob), hipMemcpyHostToDevice, st) != hipSuccess) return PA_EINVAL;
@@ -2920,170 +3094,46 @@ extern "C" int pa_gemm_split_stats(int64_t* out2, int32_t reset) {
     if (reset) { g_cnt.taken.store(0); g_cnt.declined.store(0); g_cnt.reused.store(0); g_cnt.made_hits.store(0); g_cnt.cache_hits.store(0); }
     return 0;
 }
-// Returns 0 and *taken = true when the product ran as bf16x3, 0 and *taken = false when the caller must run it exact, or an error
-// (a negative PA_E* or a positive hipError_t of the cut / inner launch - ADVICE r5: the status used to share the return value
-// with the 'taken' flag, so hipErrorInvalidValue = 1 read as success).
-static int gemm_split3(const pa_gemm_args* a, void* stream, bool* taken) {
-    *taken = false;
-    const bool akc = a->a_kcontig != 0, bkc = a->b_kcontig != 0;
-    const int M = a->M, N = a->N, K = a->K, nb = a->batch;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    // source rows / cols of each operand as stored
-    const int ar = akc ? M : K, ac = akc ? K : M, br = bkc ? N : K, bc = bkc ? K : N;
-    if ((ac & 7) || (bc & 7) || (a->lda & 3) || (a->ldb & 3) || (a->sA & 3) || (a->sB & 3) || !al16(a->A) || !al16(a->B)) return 0;
-    if ((long long)ar * ac * nb >= (1ll << 33) || (long long)br * bc * nb >= (1ll << 33) || (long long)M * N * nb >= (1ll << 33)) return 0;   // (split_kernel indexes 8-element vectors in 32 bits)
-    if (akc && bkc && (K & 63)) return 0;                 // the bf16 fast paths want whole K tiles per part
-    if (a->C_lp) return 0;
-    if (a->aux && ((N & 7) || (a->ldaux & 3) || (a->sAux & 3) || !al16(a->aux))) return 0;
-    const bool a_shared = nb > 1 && a->sA == 0, b_shared = nb > 1 && a->sB == 0;
-    const long long a_el = (long long)ar * ac * 3, b_el = (long long)br * bc * 3, x_el = a->aux ? (long long)M * N : 0;
-    auto up = [](long long v) { return (v + 255) / 256 * 256; };
-    // parts pattern: the forward and plain mode cut A as (hi, hi, lo) and B as (hi, lo, hi), a backward segment the other way round
-    // (its retained dY images then meet the forward's retained X images in the weight-gradient product)
-    int pa = g_split.retain == 1 ? 1 : 0;
-    // both operands with a strided contraction index (a weight gradient): either may have been cut before, as the k-contiguous
-    // operand of an earlier GEMM, and kept (SplitState) - the other one is then cut into the same row-interleaved stacking
-    const bool stacked2 = !akc && !bkc && nb == 1;
-    const SplitKeep* ha = stacked2 ? g_split.find_seg(a->A, ar, ac, a->lda) : nullptr;
-    const SplitKeep* hb = stacked2 ? g_split.find_fwd(a->B, br, bc, a->ldb) : nullptr;
-    if (ha) pa = ha->pat; else if (hb) pa = 1 - hb->pat;
-    if (hb && hb->pat == pa) hb = nullptr;
-    // a k-contiguous A whose image was written by the kernel that produced A (pa_gemm_split_reserve) ..
-    if (akc && nb == 1 && g_split.retain) {
-        const SplitKeep* e = g_split.retain == 2 ? SplitState::find_in(g_split.keepL, g_split.nkeepL, a->A, ar, ac, a->lda)
-                                                 : g_split.find_seg(a->A, ar, ac, a->lda);
-        if (e && e->made && e->pat == pa) { ha = e; g_cnt.made_hits.fetch_add(1); }
+static int gemm_body(const pa_gemm_args* a, void* stream);
+static int gemm_group_body(const pa_gemm_args* args, int32_t n, void* stream);
+// Dry run (include/plank_hip.h): the plan pa_gemm (n == 1) / pa_gemm_group (n > 1) would make in the calling thread's context.
+extern "C" int pa_gemm_split_plan(const pa_gemm_args* args, int32_t n, int32_t commit, pa_split_plan_info* out) {
+    static_assert(sizeof(pa_split_plan_info) == 22 * 4 + 10 * 8, "pa_split_plan_info (plankassembly_amd/_lib.py mirrors it)");
+    if (!args || !out || n <= 0 || n > PA_MAX_GROUP) return PA_EINVAL;
+    const pa_gemm_args& a0 = args[0];
+    if (n == 1 && (!a0.A || !a0.B || !a0.C || a0.M <= 0 || a0.N <= 0 || a0.K <= 0 || a0.batch <= 0)) return PA_EINVAL;
+    SplitState& st = cur_split();
+    const bool x3 = split_on() && a0.in_dtype == PA_F32;
+    SplitPlan idle; idle.after = st; idle.n = n;             // (mode off / not an f32 product: nothing is planned)
+    const SplitPlan p = !x3 ? idle : n == 1 ? plan_split3(a0, st) : plan_group_split3(args, n, st);     // (a copy of some KB: dry run only)
+    if (x3 && commit) commit_split3(st, p);
+    for (int i = 0; i < n; ++i) {
+        // (only a taken plan filled info[i] and - but for a declined single call - inner[i]: otherwise zeros (source: caller) and the caller's block)
+        const pa_gemm_args& b = p.taken || (x3 && n == 1) ? p.inner[i] : args[i];
+        pa_split_plan_info& o = out[i] = p.taken ? p.info[i] : pa_split_plan_info();
+        o.taken = p.taken; o.drop_seg = p.drop_seg; o.drop_fwd = p.drop_fwd;
+        o.M = b.M; o.N = b.N; o.K = b.K; o.lda = b.lda; o.ldb = b.ldb; o.sA = b.sA; o.sB = b.sB; o.splitk = b.splitk;
+        o.keep_off = p.after.keep_off; o.long_off = p.after.long_off;
+        o.nkeep = p.after.nkeep; o.nkeepL = p.after.nkeepL; o.long_closed = p.after.long_closed;
     }
-    // .. and a constant k-contiguous B (a weight) held in the model's cache; a miss is cut INTO the cache
-    SplitCache* const wc = g_split.cache;
-    bf16* cache_b = nullptr; bool cache_cut = false;
-    if (wc && bkc && nb == 1) {
-        for (int k = 0; k < wc->n && !cache_b; ++k) {
-            const SplitKeep& e = wc->e[k];
-            if (e.src == a->B && e.rows == br && e.cols == bc && e.ld == a->ldb && e.pat == 1 - pa) cache_b = e.dst;
-        }
-        if (cache_b) g_cnt.cache_hits.fetch_add(1);
-        else if (wc->n < SPLIT_CACHE_MAX && wc->used + up(b_el * 2) <= wc->bytes) {
-            cache_b = reinterpret_cast<bf16*>(wc->buf + wc->used); wc->used += up(b_el * 2);
-            wc->e[wc->n++] = SplitKeep{a->B, br, bc, a->ldb, 1 - pa, cache_b, 0};
-            wc->table_stale = true; cache_cut = true;
-        }
-    }
-    long long a_bytes = ha ? 0 : up(a_el * 2 * (a_shared ? 1 : nb)), b_bytes = (hb || cache_b) ? 0 : up(b_el * 2 * (b_shared ? 1 : nb));
-    const long long x_bytes = up(x_el * 2 * nb);
-    auto forget_hits = [&]() {                               // (images dropped below may be the ones found above)
-        ha = hb = nullptr; if (stacked2) pa = g_split.retain == 1 ? 1 : 0;
-        a_bytes = up(a_el * 2 * (a_shared ? 1 : nb)); b_bytes = cache_b ? 0 : up(b_el * 2 * (b_shared ? 1 : nb));
-    };
-    bool keep_a = false;
-    if (g_split.retain == 2) {
-        // forward: images are kept while a quarter of the buffer stays free for the backward segments' own cuts
-        if (g_split.long_off + a_bytes + b_bytes + x_bytes > g_split.bytes) {
-            g_split.long_off = 0; g_split.nkeepL = 0; g_split.long_closed = true; forget_hits();
-            if (a_bytes + b_bytes + x_bytes > g_split.bytes) return 0;
-        }
-        keep_a = akc && nb == 1 && !g_split.long_closed && g_split.nkeepL < 128 &&
-                 g_split.long_off + a_bytes + b_bytes + x_bytes <= g_split.bytes - g_split.bytes / 4;
-        g_split.keep_off = g_split.long_off;
-    } else {
-        if (g_split.keep_off + a_bytes + b_bytes + x_bytes > g_split.bytes) {
-            // does not fit behind what is retained: drop this segment's images, then the forward's (stream order keeps their
-            // earlier readers safe)
-            g_split.keep_off = g_split.long_off; g_split.nkeep = 0; forget_hits();
-            if (g_split.keep_off + a_bytes + b_bytes + x_bytes > g_split.bytes) {
-                g_split.long_off = 0; g_split.nkeepL = 0; g_split.keep_off = 0;
-                if (a_bytes + b_bytes + x_bytes > g_split.bytes) return 0;
-            }
-        }
-        keep_a = g_split.retain == 1 && akc && nb == 1 && g_split.nkeep < 16;
-    }
-    // split-K: callers size their slabs with pa_gemm_effective_splitk(K, PA_F32, .), which in this mode already counts whole
-    // 64-wide tiles of the 3 K long bf16 contraction - the request passes through unchanged
-    const int sk_req = a->splitk > 1 ? a->splitk : 1;
-    if (sk_req > 1 && !a->ws) return 0;
-    static const bool dbg_split = getenv("PA_SPLIT_DEBUG") && atoi(getenv("PA_SPLIT_DEBUG")) >= 2;
-    if (dbg_split) fprintf(stderr, "[pa_gemm x3] M %d N %d K %d batch %d akc %d bkc %d splitk %d -> %d defer %d\n",
-                           M, N, K, nb, (int)akc, (int)bkc, a->splitk, sk_req, a->splitk_defer);
-    char* w0 = g_split.ws + g_split.keep_off;
-    bf16* A3 = reinterpret_cast<bf16*>(w0);
-    bf16* B3 = reinterpret_cast<bf16*>(w0 + a_bytes);
-    bf16* X1 = reinterpret_cast<bf16*>(w0 + a_bytes + b_bytes);
-    if (ha) A3 = ha->dst;
-    if (hb) B3 = hb->dst;
-    if (cache_b) B3 = cache_b;
-    if (keep_a && !ha) {
-        const SplitKeep e{a->A, ar, ac, a->lda, pa, A3, 0};
-        if (g_split.retain == 2) { SplitState::put(g_split.keepL, g_split.nkeepL, e); g_split.long_off += a_bytes; }
-        else SplitState::put(g_split.keep, g_split.nkeep, e);
-        g_split.keep_off += a_bytes;
-    }
-    if (stacked2 && (ha || hb)) g_cnt.reused.fetch_add((ha ? 1 : 0) + (hb ? 1 : 0));
-    const bool inter = stacked2 && (ha || hb);               // row-interleaved stacking: split modes 0 / 1 instead of 2 / 3
-    SplitTab tb; tb.n = 0; tb.begin[0] = 0;
-    auto add = [&](const void* src, bf16* dst, int rows, int cols, int ld, int mode, long long ss, long long ds, int batch) {
-        SplitJob& j = tb.j[tb.n];
-        j.src = static_cast<const float*>(src); j.dst = dst; j.rows = rows; j.cols = cols; j.ld = ld; j.mode = mode;
-        j.sstride = ss; j.dstride = ds; j.batch = batch; j.pad_ = 0;
-        // one 8-element vector per thread up to `cap` blocks (measured: 2 per thread / 2 048 blocks 12.25 ms per step, 1 / 8 192 12.14)
-        static const int vpt = getenv("PA_SPLIT_VPT") ? atoi(getenv("PA_SPLIT_VPT")) : 1, cap = getenv("PA_SPLIT_CAP") ? atoi(getenv("PA_SPLIT_CAP")) : 16384;
-        long long blocks = ((long long)rows * (cols >> 3) * batch + 256 * vpt - 1) / (256 * vpt);
-        if (blocks < 1) blocks = 1;
-        if (blocks > cap) blocks = cap;
-        tb.begin[tb.n + 1] = tb.begin[tb.n] + (int)blocks;
-        ++tb.n;
-    };
-    if (!ha) add(a->A, A3, ar, ac, a->lda, (akc || inter ? 0 : 2) + pa, a->sA, a_el, a_shared ? 1 : nb);
-    if (!hb && (!cache_b || cache_cut)) add(a->B, B3, br, bc, a->ldb, (bkc || inter ? 0 : 2) + (1 - pa), a->sB, b_el, b_shared ? 1 : nb);
-    if (a->aux) add(a->aux, X1, M, N, a->ldaux, 4, a->sAux, x_el, nb);
-    if (tb.n) PA_LAUNCH(split_kernel, dim3(tb.begin[tb.n]), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tb);
-    pa_gemm_args b = *a;
-    b.in_dtype = PA_BF16;
-    b.A = A3; b.B = B3; b.K = 3 * K;
-    b.lda = akc ? 3 * K : M; b.ldb = bkc ? 3 * K : N;
-    b.sA = a_shared ? 0 : a_el; b.sB = b_shared ? 0 : b_el;
-    if (a->aux) { b.aux = X1; b.ldaux = N; b.sAux = x_el; }
-    b.splitk = sk_req;
-    g_split.on.store(0, std::memory_order_relaxed);            // (the inner call is a plain bf16 GEMM)
-    const int rc = pa_gemm(&b, stream);
-    g_split.on.store(1, std::memory_order_relaxed);
-    if (rc) return rc;
-    *taken = true;
     return 0;
 }
-
 extern "C" int pa_gemm(const pa_gemm_args* a, void* stream) {
     if (!a || !a->A || !a->B || !a->C) return PA_EINVAL;
-    if (a->in_dtype == PA_F32 && g_split.on.load(std::memory_order_relaxed)) {
-        if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch <= 0) return PA_EINVAL;
-        bool took = false;
-        const int r3 = gemm_split3(a, stream, &took);
-        if (r3) return r3;
-        if (took) { g_cnt.taken.fetch_add(1); return 0; }
-        g_cnt.declined.fetch_add(1);
-        if (a->splitk > 1 && a->splitk_defer && a->ws) {
-            // the caller's reduction descriptor counts pa_gemm_effective_splitk(K, PA_F32, splitk) slabs in THIS mode's (bf16)
-            // tiling; the exact kernel below writes the f32 tiling's count: run it with a request that yields no more than that
-            // and hand the reducer zeros for the rest
-            const int want = eff_splitk((3 * a->K + 63) / 64, a->splitk), nt32 = (a->K + 15) / 16;
-            int req = want;
-            while (req > 1 && eff_splitk(nt32, req) > want) --req;
-            const int got = eff_splitk(nt32, req);
-            pa_gemm_args e = *a; e.splitk = req;
-            g_split.on.store(0, std::memory_order_relaxed);
-            const int rc = pa_gemm(&e, stream);
-            g_split.on.store(1, std::memory_order_relaxed);
-            if (rc) return rc;
-            if (got < want) {
-                const size_t slab = (size_t)a->M * a->N * sizeof(float);
-                if (hipMemsetAsync(static_cast<char*>(a->ws) + (size_t)got * slab, 0, (size_t)(want - got) * slab,
-                                   reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return PA_EINVAL;
-            }
-            return 0;
-        }
-        static const bool dbg_split = getenv("PA_SPLIT_DEBUG") && atoi(getenv("PA_SPLIT_DEBUG"));
-        if (dbg_split) fprintf(stderr, "[pa_gemm x3 declined] M %d N %d K %d batch %d akc %d bkc %d lda %d ldb %d sA %lld sB %lld splitk %d aux %d ldaux %d\n",
-                               a->M, a->N, a->K, a->batch, a->a_kcontig, a->b_kcontig, a->lda, a->ldb, (long long)a->sA, (long long)a->sB, a->splitk, a->aux ? 1 : 0, a->ldaux);
-    }
+    if (a->in_dtype != PA_F32 || !split_on()) return gemm_body(a, stream);
+    if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch <= 0) return PA_EINVAL;
+    const SplitPlan p = plan_split3(*a, cur_split());
+    commit_split3(cur_split(), p);
+    const pa_gemm_args& b = p.inner[0];                      // the bf16 product over 3 K, or the exact call of a declined one
+    int rc = p.taken ? launch_cuts(p, stream) : 0;           // (0, a negative PA_E* or a positive hipError_t of the cut / inner launch)
+    if (!rc) rc = gemm_body(&b, stream);
+    const int got = eff_splitk((b.K + 15) / 16, b.splitk);   // (declined deferred split-K: slabs the exact kernel wrote)
+    if (rc || got >= p.exact_want) return rc;
+    const size_t slab = (size_t)b.M * b.N * sizeof(float);
+    return hipMemsetAsync(static_cast<char*>(b.ws) + got * slab, 0, (p.exact_want - got) * slab, reinterpret_cast<hipStream_t>(stream)) == hipSuccess ? 0 : PA_EINVAL;
+}
+// the exact / bf16 product: what pa_gemm runs outside the bf16x3 mode and what the mode's plans run inside it
+static int gemm_body(const pa_gemm_args* a, void* stream) {
     record_args(*a);
     const GemmSwitches& sw = gemm_switches();
     const GemmPlan pl = plan_gemm(*a, sw, cus_for_gemm());      // (256 CUs minus those left to RCCL's kernels: pa_set_reserved_cus)
@@ -3218,72 +3268,16 @@ extern "C" int pa_gemm_norm_a(const pa_gemm_args* a, const pa_gemm_norm_ext* x, 
     return 0;
 }
 
-// bf16x3 mode: every member's two operands are cut into their stacked (hi, hi, lo) / (hi, lo, hi) forms by ONE split launch into
-// consecutive regions of the scratch buffer, then the members run as one grouped bf16 launch over 3 K rows each.
-// (status / 'taken' separated as in gemm_split3: 0 + *taken, 0 + !*taken = declined, or an error code)
-static int gemm_group_split3(const pa_gemm_args* args, int32_t n, void* stream, bool* taken) {
-    *taken = false;
-    pa_gemm_args b[PA_MAX_GROUP];
-    SplitTab tb; tb.n = 0; tb.begin[0] = 0;
-    long long off = g_split.keep_off;                      // behind the retained (hi, hi, lo) images of this segment's dY operands
-    auto up = [](long long v) { return (v + 255) / 256 * 256; };
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    auto job = [&](const void* src, bf16* dst, int rows, int cols, int ld, int mode) {
-        SplitJob& j = tb.j[tb.n];
-        j.src = static_cast<const float*>(src); j.dst = dst; j.rows = rows; j.cols = cols; j.ld = ld; j.mode = mode;
-        j.sstride = 0; j.dstride = 0; j.batch = 1; j.pad_ = 0;
-        long long blocks = ((long long)rows * (cols >> 3) + 255) / 256;
-        if (blocks < 1) blocks = 1;
-        if (blocks > 8192) blocks = 8192;
-        tb.begin[tb.n + 1] = tb.begin[tb.n] + (int)blocks;
-        ++tb.n;
-    };
-    int hits = 0;
-    for (int i = 0; i < n; ++i) {
-        const pa_gemm_args* a = &args[i];
-        if (a->in_dtype != PA_F32 || a->out_dtype != PA_F32 || a->a_kcontig || a->b_kcontig || a->batch != 1) return 0;
-        if (a->bias || a->R || a->aux || a->relu || a->drop_p > 0.f || a->alpha != 1.f || a->C_lp) return 0;
-        if ((a->M & 7) || (a->N & 7) || (a->lda & 3) || (a->ldb & 3) || !al16(a->A) || !al16(a->B)) return 0;
-        if ((long long)a->K * a->M >= (1ll << 33) || (long long)a->K * a->N >= (1ll << 33)) return 0;
-        const long long a_el = (long long)a->K * a->M * 3, b_el = (long long)a->K * a->N * 3;
-        // dY (the A operand: [K rows][M features]) was cut for this segment's dX GEMM as a k-contiguous operand: [K][3 M], which
-        // read as [3 K][M] is the stacked operand with the planes interleaved row by row; X (the B operand) was cut the same way
-        // by the forward's Linear, in the opposite parts pattern.  Whichever is missing goes into the matching interleaving
-        // (split modes 0 / 1) instead of the plane-stacked modes 2 / 3.
-        const SplitKeep* ha = g_split.find_seg(a->A, a->K, a->M, a->lda);
-        const SplitKeep* hb = g_split.find_fwd(a->B, a->K, a->N, a->ldb);
-        const int pa = ha ? ha->pat : hb ? 1 - hb->pat : 0;
-        if (hb && hb->pat == pa) hb = nullptr;
-        const bool inter = ha || hb;
-        const long long need = (ha ? 0 : up(a_el * 2)) + (hb ? 0 : up(b_el * 2));
-        if (off + need > g_split.bytes) return 0;
-        bf16 *A3, *B3;
-        if (ha) { A3 = ha->dst; ++hits; }
-        else { A3 = reinterpret_cast<bf16*>(g_split.ws + off); off += up(a_el * 2); job(a->A, A3, a->K, a->M, a->lda, (inter ? 0 : 2) + pa); }
-        if (hb) { B3 = hb->dst; ++hits; }
-        else { B3 = reinterpret_cast<bf16*>(g_split.ws + off); off += up(b_el * 2); job(a->B, B3, a->K, a->N, a->ldb, (inter ? 0 : 2) + 1 - pa); }
-        b[i] = *a;
-        b[i].in_dtype = PA_BF16; b[i].A = A3; b[i].B = B3; b[i].K = 3 * a->K; b[i].lda = a->M; b[i].ldb = a->N;
-    }
-    if (tb.n) PA_LAUNCH(split_kernel, dim3(tb.begin[tb.n]), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tb);
-    g_split.on.store(0, std::memory_order_relaxed);
-    const int rc = pa_gemm_group(b, n, stream);
-    g_split.on.store(1, std::memory_order_relaxed);
-    if (rc) return rc;
-    g_cnt.taken.fetch_add(n);
-    g_cnt.reused.fetch_add(hits);
-    *taken = true;
-    return 0;
-}
 extern "C" int pa_gemm_group(const pa_gemm_args* args, int32_t n, void* stream) {
     if (!args || n <= 0 || n > PA_MAX_GROUP) return PA_EINVAL;
-    if (split_on() && args[0].in_dtype == PA_F32) {
-        bool took = false;
-        const int r3 = gemm_group_split3(args, n, stream, &took);
-        if (r3) return r3;
-        if (took) return 0;
-        return PA_EINVAL;                                   // the caller launches the members one by one (pa_gemm declines or splits each)
-    }
+    if (!split_on() || args[0].in_dtype != PA_F32) return gemm_group_body(args, n, stream);
+    const SplitPlan p = plan_group_split3(args, n, cur_split());
+    commit_split3(cur_split(), p);
+    if (!p.taken) return PA_EINVAL;                         // the caller launches the members one by one (pa_gemm declines or splits each)
+    const int rc = launch_cuts(p, stream);
+    return rc ? rc : gemm_group_body(p.inner, n, stream);
+}
+static int gemm_group_body(const pa_gemm_args* args, int32_t n, void* stream) {
     static_assert(PA_MAX_GROUP == PA_MAX_GROUP_, "header / kernel table size");
     GemmGroup g; g.n = n; g.begin[0] = 0;
     int valid = 0;

@@ -191,6 +191,9 @@ class PlankModel(nn.Module):
         self.compute_mode = compute_dtype                      # what the caller asked for
         self.split3 = compute_dtype == "x3"
         self.compute_dtype = "f32" if self.split3 else compute_dtype     # storage / kernel dtype: 'x3' is f32 with split products
+        # 'x3': MB of split scratch and of the (opt-in) weight-image cache, fixed when the model is built (see _split_on)
+        self._x3_scratch_mb = int(os.environ.get("PLANK_X3_SCRATCH_MB", "2048"))
+        self._x3_wcache_mb = int(os.environ.get("PLANK_X3_WCACHE_MB", "0"))
         self.num_model, self.num_head, self.num_feedforward = num_model, num_head, num_feedforward
         self.dropout = float(dropout)
         # the reference passes normalize_before in torch's layer_norm_eps slot (models.py:60-61,66-67)
@@ -430,7 +433,6 @@ class PlankModel(nn.Module):
         dtypes): mode, scratch, retained images and counters belong to the model, not to the process (pa_split_ctx_*)."""
         if not self.split3:
             return
-        attn = os.environ.get("PLANK_X3_ATTN", "1") != "0"         # (0: attention stays on the exact-f32 kernels)
         if not on:
             if getattr(self, "_x3_ctx", None) is not None:
                 L.check(L.lib().pa_split_ctx_enter(self._x3_ctx), "pa_split_ctx_enter")
@@ -440,7 +442,7 @@ class PlankModel(nn.Module):
             L.check(L.lib().pa_split_ctx_enter(None), "pa_split_ctx_enter")
             return
         try:
-            self._split_on(attn, retain)
+            self._split_on(retain)
         except BaseException:
             #  a failure half way - scratch allocation, cache creation - must not leave the process-global mode on
             # for every other f32 model of the process
@@ -450,33 +452,30 @@ class PlankModel(nn.Module):
                 pass
             raise
 
-    def _split_on(self, attn, retain):
+    def _split_on(self, retain):
         if getattr(self, "_x3_ctx", None) is None:
             h = C.c_void_p()
             L.check(L.lib().pa_split_ctx_create(C.byref(h)), "pa_split_ctx_create")
             self._x3_ctx = h
         L.check(L.lib().pa_split_ctx_enter(self._x3_ctx), "pa_split_ctx_enter")
-        if attn:
-            L.check(L.lib().pa_attn_split_config(1), "pa_attn_split_config")
+        L.check(L.lib().pa_attn_split_config(1), "pa_attn_split_config")
         ws = getattr(self, "_x3_ws", None)
         if ws is None or ws.device != self._flat.device:
             # the cut operands of one GEMM at a time, plus (retain modes) the forward's Linear inputs for the backward's weight
             # gradients: 1.1 GB at the benchmark batch; what does not fit is simply cut again.  Owned by the model: released with it.
-            mb = int(os.environ.get("PLANK_X3_SCRATCH_MB", "2048"))
-            ws = torch.empty(mb * (1 << 20) + 256, dtype=torch.uint8, device=self._flat.device)
+            ws = torch.empty(self._x3_scratch_mb * (1 << 20) + 256, dtype=torch.uint8, device=self._flat.device)
             self._x3_ws = ws
         base = (ws.data_ptr() + 255) // 256 * 256
         # backward segments: mode 2 keeps the cut dY of every dX GEMM for the segment's grouped weight-gradient launch; the
         # forward: mode 3 keeps the cut input of every Linear for the same launch (include/plank_hip.h pa_gemm_split_config)
-        keep = os.environ.get("PLANK_X3_RETAIN", "1")
-        mode = 1 if (not retain or keep == "0") else 3 if (retain == "fwd" and keep != "bwd") else 1 if retain == "fwd" else 2
+        mode = 1 if not retain else 3 if retain == "fwd" else 2
         L.check(L.lib().pa_gemm_split_config(mode, C.c_void_p(base), C.c_int64(ws.numel() - (base - ws.data_ptr()))), "pa_gemm_split_config")
         # this model's weight images: learnt by the first step, re-cut by refresh_transposed() whenever the parameters changed
         if retain and getattr(self, "_x3_cache", None) is None:
             # OFF by default (PLANK_X3_WCACHE_MB=0): measured on MI355X the split launches it removes (28.0 -> 21.8 ms over 23 steps)
             # cost less than what the GEMMs lose reading weight images cut a whole step earlier instead of just before the launch
             # (pair GEMM 54.9 -> 62.6 us, gemm3s 18.2 -> 23.3 us): 12.07 -> 12.57 ms per step.  -1: sized from the parameters.
-            mb = int(os.environ.get("PLANK_X3_WCACHE_MB", "0"))
+            mb = self._x3_wcache_mb
             if mb < 0:
                 mb = max(64, (self._numel * 12 >> 20) + 64)
             if mb > 0:

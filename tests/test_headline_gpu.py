@@ -784,7 +784,7 @@ def test_x3_b16_step_matches_oracle(which):
 
 def test_x3_b16_step_with_a_small_scratch_buffer_still_passes_the_gate(monkeypatch):
     """256 MB of split scratch instead of 2 GB: the forward can keep only a few of its cut Linear inputs, segments drop their images
-    when a GEMM's own cuts need the room - every fallback path of gemm.hip gemm_split3 / pa_gemm_split_reserve - and the step
+    when a GEMM's own cuts need the room - every fallback path of gemm.hip plan_split3 / pa_gemm_split_reserve - and the step
     must come out the same (the images are an optimisation, never a source of data)."""
     from plankassembly_amd.models import PlankModel
     c, batch, _ = _b16_case("above")

@@ -1181,7 +1181,7 @@ def test_attention_mask_order_dispatch_leaves_results_unchanged():
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# bf16x3 ("split") GEMMs at the C ABI (csrc/gemm.hip gemm_split3 / gemm_group_split3; include/plank_hip.h pa_gemm_split_config):
+# bf16x3 ("split") GEMMs at the C ABI (csrc/gemm.hip plan_split3 / plan_group_split3; include/plank_hip.h pa_gemm_split_config):
 # f32 in / f32 out, every product as hi*hi + hi*lo + lo*hi on the bf16 matrix pipe.  Reference: float64 on the CPU.
 class _SplitMode:
     """pa_gemm_split_config bracket over a scratch tensor owned by the test."""
@@ -1219,6 +1219,9 @@ class _SplitMode:
         return self.buf[off: off + rows * cols * 6].view(torch.bfloat16).view(rows, 3 * cols)
 
 
+X3_SPLIT_TOL = 2.0 ** -15     # bound on _x3_err of a bf16x3 product: measured ~2^-17.5 .. 2^-16.5 of max |a||b|; plain bf16 sits at ~2^-9
+
+
 def _x3_err(got, a64, b64_t):
     """max |got - a b| over max(|a| |b|): the split drops lo*lo (2^-16 of a term) and rounds lo to 8 bits (2^-17)."""
     ref = a64 @ b64_t
@@ -1243,7 +1246,7 @@ def test_gemm_x3_layouts_match_float64_to_split_precision(akc, bkc, M, N, K):
     bias64 = bias.cpu().double()
     e3 = _x3_err(got - bias, a.double(), b.double().t())
     e32 = _x3_err(exact - bias, a.double(), b.double().t())
-    assert e3 < 2.0 ** -15, e3                      # measured ~2^-17.5 .. 2^-16.5 of max |a||b|; plain bf16 sits at ~2^-9
+    assert e3 < X3_SPLIT_TOL, e3
     assert e32 < 2.0 ** -20, e32
     assert not torch.equal(got, exact)               # (really a different arithmetic, not the exact kernel again)
     del bias64

@@ -3,7 +3,9 @@ path pinned to the one before the plan function existed: one forward + backward 
 tests/golden/train_launches.json - recorded by record() of this file on the commit before - in the same order with the same shapes,
 splits, kernels, groups and slab offsets; the weight gradients among them must be, member for member, what pa_train_plan reports;
 and the exact-f32 step (ordered reductions: run-to-run bit-identical, confirmed on that commit in two processes) must give the same
-loss bits and the same gradient bytes.
+loss bits and the same gradient bytes.  So must the bf16x3 step under PA_DETERMINISTIC=1 (its bias, LayerNorm and embedding-table
+sums are then ordered too): the commit before the bf16x3 cut plan (tests/test_x3_plan_cpu.py) gave the same bits in two processes,
+and those are the x3_* values of the golden file.
 
 The smallest shape with a deferred split-K member in bf16: d_model 128, 2 heads, d_ff 256, 1 encoder and 2 decoder layers, B 4,
 S 160 unpadded (640 encoder rows: 10 K tiles of 64, the first count whose cap 10 / 4 is above 1), T 24, dropout 0.1, training mode."""
@@ -11,6 +13,7 @@ import ctypes as C
 import hashlib
 import json
 import os
+import subprocess
 import sys
 import types
 
@@ -74,11 +77,23 @@ def stepped(dtype):
     return _STEPS[dtype]
 
 
+def x3_bits_in_a_child():
+    """Loss bits and gradient digest of the x3 step under PA_DETERMINISTIC=1, which is read once per process: this file as a script."""
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--x3-bits"], env=dict(os.environ, PA_DETERMINISTIC="1"),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
 def record():
-    """The golden file's content: run on the commit before the plan function (this file copied into its tests/)."""
+    """The golden file's content: run on the commit before (this file copied into its tests/).  The x3 bits come from two child
+    processes, which must agree."""
     out = {dt: step(dt)[0] for dt in DTYPES}
+    x3 = x3_bits_in_a_child()
+    assert x3 == x3_bits_in_a_child(), "the x3 step does not repeat under PA_DETERMINISTIC=1"
     print(json.dumps({"launches": {dt: out[dt]["launches"] for dt in DTYPES}, "f32_loss_bits": out["f32"]["loss_bits"],
-                      "f32_grad_sha256": out["f32"]["grad_sha256"]}, separators=(",", ":")))
+                      "f32_grad_sha256": out["f32"]["grad_sha256"], "x3_loss_bits": x3["loss_bits"],
+                      "x3_grad_sha256": x3["grad_sha256"]}, separators=(",", ":")))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -123,5 +138,15 @@ def test_exact_f32_step_is_bit_identical_to_the_recorded_one():
     assert res["loss_bits"] == gold["f32_loss_bits"] and res["grad_sha256"] == gold["f32_grad_sha256"]
 
 
+def test_x3_step_with_ordered_reductions_is_bit_identical_to_the_recorded_one():
+    gold = json.load(open(GOLDEN))
+    got = x3_bits_in_a_child()
+    assert got["loss_bits"] == gold["x3_loss_bits"] and got["grad_sha256"] == gold["x3_grad_sha256"], (got, gold["x3_loss_bits"])
+
+
 if __name__ == "__main__":
-    record()
+    if "--x3-bits" in sys.argv:
+        res = step("x3")[0]
+        print(json.dumps({"loss_bits": res["loss_bits"], "grad_sha256": res["grad_sha256"]}))
+    else:
+        record()
