@@ -1117,6 +1117,38 @@ int pa_plank_match(const int64_t* seq_a, int64_t stride_a, int32_t len_a, const 
                    const int32_t* pair_a, const int32_t* pair_b, int32_t n_pairs, int32_t end_token, int32_t dof,
                    int32_t filter_a, int32_t filter_b, double threshold, int32_t* out, void* stream);
 
+/* ---- line-set overlap (csrc/overlap.hip, core csrc/overlap_core.h; plankassembly_amd/metric.py line_overlap_counts) ----
+ * One launch, one block of 256 threads per pair: two encoder rows compared as sets of axis-aligned lines.  Defines the
+ * reprojection score's counts; reads the encoder rows of the batch contract (plankassembly_amd/datasets.py
+ * `prepare_input_sequence`; reference line_data.py:34-83 - four tokens x0 y0 x1 y1 per line, END, PAD, view and type per token),
+ * as the dataset, pa_tokenise_drawings or pa_render_drawings wrote them.  Side a is the given drawing, side b the rendering.
+ *   value_x / view_x / type_x int64 rows of len_x elements, row r of each at + r * stride_x (one stride per side, in elements,
+ *     >= 0); type_x may be NULL (every type is 0 then); pair_a / pair_b int32 [n_pairs] as for pa_plank_match (both NULL: rows
+ *     i and i); the rows named must exist;
+ *   a row holds n = L / 4 lines, L = the index of its first end_token (len without one); line i has tokens value[4i .. 4i+3], the
+ *     view view[4i] and the type type[4i]; x0 = min(t0, t2), x1 = max(t0, t2), y0 = min(t1, t3), y1 = max(t1, t3).  It is KEPT
+ *     if the four tokens are in [0, 2^num_bits), the view is 0, 1 or 2 and it is horizontal (y0 == y1, x0 < x1: c = y0, lo = x0,
+ *     hi = x1) or vertical (x0 == x1, y0 < y1: c = x0, lo = y0, hi = y1); every other line is SKIPPED and only counted;
+ *   a kept line b MATCHES a kept line a of the other side if view and orientation are equal, |c_b - c_a| <= tol and, under
+ *     PA_OVERLAP_MATCH, type_b == type_a (types saturate to int32 first); covered(a) = the length of [lo_a, hi_a] inside the
+ *     union of [lo_b - tol, hi_b + tol] over the matching b; cov(A|B) = the sum of covered(a), len(A) = the sum of hi_a - lo_a;
+ *     duplicate lines count once each.  Under PA_OVERLAP_VISIBLE only the lines of side b with type 0 take part, in both
+ *     directions (the others are neither kept nor skipped) and the types of side a are not read; under PA_OVERLAP_IGNORE no type
+ *     is read;
+ *   out int32 [n_pairs][8] = cov(A|B), len(A), cov(B|A), len(B), kept_A, kept_B, skipped_A, skipped_B.  Integers only.
+ * len / 4 above PA_TOKENISE_MAX_LINES on either side, or num_bits outside 1 .. 11: PA_ESHAPE; a null value / view / out pointer,
+ * one pair list without the other, a negative stride / len / tol / n_pairs, tol above PA_OVERLAP_MAX_TOL, a mode that is none of
+ * the three, PA_OVERLAP_MATCH with a null type row: PA_EINVAL; a failed check launches nothing.  n_pairs == 0 launches nothing
+ * and returns 0. */
+#define PA_OVERLAP_IGNORE 0
+#define PA_OVERLAP_MATCH 1
+#define PA_OVERLAP_VISIBLE 2
+#define PA_OVERLAP_MAX_TOL 255
+int pa_line_overlap(const int64_t* value_a, const int64_t* view_a, const int64_t* type_a, int64_t stride_a, int32_t len_a,
+                    const int64_t* value_b, const int64_t* view_b, const int64_t* type_b, int64_t stride_b, int32_t len_b,
+                    const int32_t* pair_a, const int32_t* pair_b, int32_t n_pairs, int32_t end_token, int32_t num_bits,
+                    int32_t tol, int32_t type_mode, int32_t* out, void* stream);
+
 /* ---- sequence-level training batches (csrc/seqtrain.hip; PlankModel.sequence_batch / seq_train_step) ----
  * One launch, one block per output row, grid (G, B): the N samples of each of B drawings, as the sample decoder left them in HBM
  * (pa_decode_buffers / pa_decode_sample_buffers, rows b*N + n, read in place), and the match counts of those rows against the

@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libplank_hip.so")
 OBJ = os.path.join(HERE, "csrc", "build")
-SOURCES = ["gemm.hip", "rowops.hip", "attention.hip", "decode.hip", "runtime.hip", "tokenise.hip", "match.hip", "seqtrain.hip"]
+SOURCES = ["gemm.hip", "rowops.hip", "attention.hip", "decode.hip", "runtime.hip", "tokenise.hip", "match.hip", "seqtrain.hip",
+           "overlap.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 

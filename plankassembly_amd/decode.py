@@ -731,3 +731,87 @@ def redraw(tokens, token, data_cfg):
     is read back."""
     return _redraw(tokens, int(token.END), int(token.PAD), int(data_cfg.NUM_BITS), int(data_cfg.get("NUM_OUTPUT_DOF", 6)),
                    int(data_cfg.MAX_INPUT_LENGTH))
+
+
+REPROJECTION_TYPES = ("ignore", "match", "visible")
+
+
+def check_reprojection(tol=1, types="ignore"):
+    """The two options of the reprojection score, validated -> (tol int in 0 .. 255, types)."""
+    if isinstance(tol, bool) or not isinstance(tol, int) or not 0 <= tol <= 255:
+        raise ValueError(f"REPROJECTION_TOL must be an integer in [0, 255], got {tol!r}")
+    if types not in REPROJECTION_TYPES:
+        raise ValueError(f"REPROJECTION_TYPES must be one of {REPROJECTION_TYPES}, got {types!r}")
+    return tol, types
+
+
+def _reprojection(batch, tokens, end_token, pad_token, num_bits, dof, max_input_length, with_type, tol, types, pairs):
+    """``reprojection_scores`` on plain values."""
+    from . import ops
+    from .metric import overlap_scores
+    tol, types = check_reprojection(tol, types)
+    given = (batch["input_value"], batch["input_view"], batch.get("input_type"))
+    if types == "match" and (given[2] is None or not with_type):
+        raise ValueError("types='match' needs input_type in the batch and a rendering with types")
+    dev = tokens.device
+    given = tuple(None if t is None else t.to(device=dev, dtype=torch.int64) for t in given)
+    drawn = _redraw(tokens, end_token, pad_token, num_bits, dof, max_input_length, with_type=with_type)
+    counts = ops.line_overlap(given, drawn, pairs, end_token=end_token, num_bits=num_bits, tol=tol, types=types, check_pairs=False)
+    rec, prec, f1 = overlap_scores(counts)
+    return {"reprojection_precision": prec, "reprojection_recall": rec, "reprojection_f1": f1, "reprojection_counts": counts,
+            "reprojection_flags": drawn["_render_flags"]}
+
+
+def reprojection_scores(batch, tokens, token, data_cfg_or_bits, *, tol=1, types="ignore", pairs=None):
+    """How well the three views of decoded programs match the drawings that were given - a score that
+    needs no ground truth and nothing of the other samples.
+
+    ``batch``: the input batch (``input_value`` / ``input_view`` / optional ``input_type`` int64 [B, S] on the device; LINE
+    drawings only - the tokens of a sideface input are faces, not lines).  ``tokens`` int64 [R, n] on the device: one program
+    per row (values, END, PAD).  They are rendered on the device (``_redraw``: plank 0, the bounding box, is not drawn) and
+    compared with the given rows by one ``ops.line_overlap``: pair i is (row i of the batch, row i of ``tokens``), or
+    ``pairs`` int [P, 2] of (batch row, tokens row) - which must exist, they are not checked.  ``data_cfg_or_bits``: the DATA
+    config (NUM_BITS, MAX_INPUT_LENGTH, NUM_OUTPUT_DOF) or the number of bits alone (the rendering is then as wide as the batch).
+    ``tol``: a rendered line counts within this many quantisation levels (default 1: the dataset quantises the mirrored
+    coordinate itself, one level off the mirrored token, on every view's second axis).  ``types``: ``ignore`` | ``match`` |
+    ``visible`` (``ops.line_overlap``).
+
+    Returns ``reprojection_recall`` = cov(given | rendered) / len(given), ``reprojection_precision`` = cov(rendered | given) /
+    len(rendered) and ``reprojection_f1`` = 2 p r / (p + r), float64 [P], each 0 where its denominator is 0;
+    ``reprojection_counts`` int32 [P, 8]; ``reprojection_flags`` int32 [R], the ``_render_flags`` of every row of ``tokens``: a
+    row outside the renderer's domain renders nothing and scores 0, truncated and overflow rows are scored as rendered.
+    Nothing is read back."""
+    if hasattr(data_cfg_or_bits, "NUM_BITS"):
+        cfg = data_cfg_or_bits
+        bits, dof, width = int(cfg.NUM_BITS), int(cfg.get("NUM_OUTPUT_DOF", 6)), int(cfg.MAX_INPUT_LENGTH)
+    else:
+        bits, dof, width = int(data_cfg_or_bits), 6, int(batch["input_value"].shape[1]) + 1
+    return _reprojection(batch, tokens, int(token.END), int(token.PAD), bits, dof, width, True, tol, types, pairs)
+
+
+@functools.lru_cache(maxsize=8)
+def _reprojection_pairs(B, N, device):
+    """(drawing b, sample row b * N + n) for every sample: int32 [B * N, 2] on ``device``."""
+    rows = torch.arange(B * N, dtype=torch.int32)
+    return torch.stack([torch.div(rows, N, rounding_mode="floor"), rows], 1).to(device)
+
+
+def _pick_reprojection(r, B, N):
+    """The flat result ``r`` of B * N pairs (b, b * N + n) as [B, N, ...] tensors, with ``reprojection_index``."""
+    out = {k: v.reshape(B, N, *v.shape[1:]) for k, v in r.items()}
+    f1 = out["reprojection_f1"]
+    best = f1.max(1, keepdim=True).values
+    out["reprojection_index"] = torch.where(f1 == best, torch.arange(N, device=f1.device)[None, :], N).min(1).values
+    return out
+
+
+def reprojection_select(batch, sample_tokens, token, data_cfg_or_bits, *, tol=1, types="ignore"):
+    """The sample of every drawing whose rendering matches the given drawing best: ``sample_tokens``
+    int64 [B, N, n] on the device with N >= 1, sample n of drawing b scored against row b of ``batch`` by
+    ``reprojection_scores`` (pairs (b, b * N + n); line drawings only).  Returns ``reprojection_index`` int64 [B] - the largest
+    F1, the lowest index (the most likely sample) among equal bits - and the keys of ``reprojection_scores`` reshaped to
+    [B, N, ...].  Nothing is read back."""
+    B, N, n = sample_tokens.shape
+    r = reprojection_scores(batch, sample_tokens.reshape(B * N, n), token, data_cfg_or_bits, tol=tol, types=types,
+                            pairs=_reprojection_pairs(B, N, sample_tokens.device))
+    return _pick_reprojection(r, B, N)

@@ -215,3 +215,82 @@ class DevicePlankScorer:
         out = tuple(float(x) for x in self.criterion.compute(sync=sync))
         self.criterion.reset()
         return out
+
+
+OVERLAP_MODES = ("ignore", "match", "visible")
+
+
+def _overlap_lines(side, end_token, num_bits, read_type, drop_hidden):
+    """One encoder row -> (kept lines int64 [k, 6] = group, c, lo, hi, type, length; number skipped).  group = view * 2 + vertical."""
+    value = np.asarray(side[0], dtype=np.int64).reshape(-1)
+    view = np.asarray(side[1], dtype=np.int64).reshape(-1)
+    hits = np.nonzero(value == end_token)[0]
+    n = (int(hits[0]) if len(hits) else len(value)) // 4
+    t = value[:4 * n].reshape(n, 4)
+    vw = view[:4 * n:4]
+    ty = np.zeros(n, dtype=np.int64)
+    if read_type and len(side) > 2 and side[2] is not None:
+        ty = np.clip(np.asarray(side[2], dtype=np.int64).reshape(-1)[:4 * n:4], -2 ** 31, 2 ** 31 - 1)
+    part = ty == 0 if drop_hidden else np.ones(n, dtype=bool)
+    x0, x1 = np.minimum(t[:, 0], t[:, 2]), np.maximum(t[:, 0], t[:, 2])
+    y0, y1 = np.minimum(t[:, 1], t[:, 3]), np.maximum(t[:, 1], t[:, 3])
+    ok = part & np.all((t >= 0) & (t < 2 ** int(num_bits)), axis=1) & (vw >= 0) & (vw <= 2)
+    hor, ver = ok & (y0 == y1) & (x0 < x1), ok & (x0 == x1) & (y0 < y1)
+    rows = np.concatenate((np.stack((vw * 2, y0, x0, x1, ty, x1 - x0), 1)[hor], np.stack((vw * 2 + 1, x0, y0, y1, ty, y1 - y0), 1)[ver]))
+    return rows.reshape(-1, 6), int(part.sum() - hor.sum() - ver.sum())
+
+
+def _overlap_cov(A, B, tol, match_type):
+    """cov(A | B) by interval algebra: per line a, the dilated intervals of its matching lines sorted, merged, clipped to a."""
+    total = 0
+    for g, c, lo, hi, ty, _ in A.tolist():
+        m = (B[:, 0] == g) & (np.abs(B[:, 1] - c) <= tol)
+        if match_type:
+            m &= B[:, 4] == ty
+        spans = sorted(zip((B[m, 2] - tol).tolist(), (B[m, 3] + tol).tolist()))
+        merged = []
+        for s, e in spans:
+            if merged and s <= merged[-1][1]:
+                merged[-1][1] = max(merged[-1][1], e)
+            else:
+                merged.append([s, e])
+        total += sum(max(0, min(e, hi) - max(s, lo)) for s, e in merged)
+    return total
+
+
+def line_overlap_counts(a, b, *, end_token, num_bits, tol=1, types="ignore"):
+    """The reprojection counts of ONE pair of line drawings on the host (``ops.line_overlap`` is the device
+    entry and computes the same integers).  ``a`` (the given drawing) and ``b`` (the rendering) are ``(value, view[, type])``
+    rows of the batch contract (``input_value`` / ``input_view`` / ``input_type`` of one drawing; line drawings only - the
+    tokens of a sideface input are faces, not lines).  A row holds (index of its first END, or its width) // 4 lines; a line
+    is kept if its four tokens are coordinates of ``num_bits`` bits, its view is 0, 1 or 2 and it is horizontal or vertical
+    with a positive length, and skipped otherwise.  A kept line b matches a kept line a of the other side at equal view and
+    orientation, ``|c_b - c_a| <= tol`` and - ``types='match'`` - equal type; covered(a) is the length of a inside the union of
+    its matching lines, each dilated by ``tol`` at both ends.  ``types='visible'``: only the type-0 lines of ``b`` take part.
+    Returns int32 [8]: cov(A|B), len(A), cov(B|A), len(B), kept_A, kept_B, skipped_A, skipped_B."""
+    if types not in OVERLAP_MODES:
+        raise ValueError(f"types must be one of {OVERLAP_MODES}, not {types!r}")
+    tol = int(tol)
+    if not 0 <= tol <= 255:
+        raise ValueError(f"tol must be in 0 .. 255, not {tol}")
+    if types == "match" and (len(a) < 3 or a[2] is None or len(b) < 3 or b[2] is None):
+        raise ValueError("types='match' needs a type row on both sides")
+    A, skip_a = _overlap_lines(a, end_token, num_bits, types == "match", False)
+    B, skip_b = _overlap_lines(b, end_token, num_bits, types != "ignore", types == "visible")
+    m = types == "match"
+    return np.asarray([_overlap_cov(A, B, tol, m), A[:, 5].sum(), _overlap_cov(B, A, tol, m), B[:, 5].sum(), len(A), len(B),
+                       skip_a, skip_b], dtype=np.int32)
+
+
+def overlap_scores(counts):
+    """recall, precision, F1 of integer [..., 8] reprojection counts (a tensor on any device) in float64, each operation rounded
+    on its own: recall = cov(A|B) / len(A), precision = cov(B|A) / len(B), f1 = 2 p r / (p + r), each 0 where its denominator
+    is 0.  The divisors are tensors: torch divides by a host scalar as a multiplication by its reciprocal."""
+    c = counts.to(torch.float64)
+    one = torch.ones((), dtype=torch.float64, device=c.device)
+    zero = torch.zeros((), dtype=torch.float64, device=c.device)
+    rec = torch.where(c[..., 1] > 0, c[..., 0] / torch.where(c[..., 1] > 0, c[..., 1], one), zero)
+    prec = torch.where(c[..., 3] > 0, c[..., 2] / torch.where(c[..., 3] > 0, c[..., 3], one), zero)
+    den = prec + rec
+    f1 = torch.where(den > 0, ((2.0 * prec) * rec) / torch.where(den > 0, den, one), zero)
+    return rec, prec, f1

@@ -136,7 +136,8 @@ class PlankModel(nn.Module):
                  normalize_before=True, num_encoder_layers=6, num_decoder_layers=6, num_view=3, num_type=2,
                  num_input_dof=4, num_output_dof=6, max_input_length=400, max_output_length=128, vocab_size=514,
                  token=None, compute_dtype=None, beam_size=1, length_penalty=0.0, num_samples=0, temperature=1.0, top_k=0,
-                 top_p=1.0, sample_seed=0, constraint=None, sample_select=None, label_smoothing=0.0, share_encoder=False):
+                 top_p=1.0, sample_seed=0, constraint=None, sample_select=None, label_smoothing=0.0, share_encoder=False,
+                 reprojection_tol=1, reprojection_types="ignore"):
         super().__init__()
         # beam search, sampling and sequence-level training decode the rows of a drawing as a decode group over ONE encoder pass and
         # memory instead of repeating the drawing; the calls' share_encoder=None means this setting
@@ -175,6 +176,14 @@ class PlankModel(nn.Module):
         self.sample_select = self._check_select(sample_select)
         if self.sample_select is not None and off:
             raise ValueError(f"SAMPLE_SELECT ({sample_select!r}) chooses among samples: it needs NUM_SAMPLES >= 1 (and so BEAM_SIZE 1)")
+        # "reprojection" = the sample whose rendered three views match the given drawing best; its tolerance
+        # in quantisation levels and its type mode also serve reprojection() and the trainers' REPROJECTION_METRIC
+        from .decode import check_reprojection
+        self.reprojection_tol, self.reprojection_types = check_reprojection(reprojection_tol, reprojection_types)
+        if self.sample_select == "reprojection" and num_output_dof != 6:
+            raise ValueError("SAMPLE_SELECT 'reprojection' renders planks of six output DOF")
+        if self.reprojection_types == "match" and num_type < 1:
+            raise ValueError("REPROJECTION_TYPES 'match' compares line types: the model has no type embedding (NUM_TYPE 0)")
         # eval_step's plank grammar (decode.plank_grammar()): None = unconstrained, True = the default grammar
         from .decode import PlankGrammar, plank_grammar
         if constraint is True:
@@ -925,8 +934,8 @@ class PlankModel(nn.Module):
     def _check_select(select):
         if select in (None, False, "none", "None", ""):
             return None
-        if select != "consensus":
-            raise ValueError(f"SAMPLE_SELECT must be 'consensus' or none, got {select!r}")
+        if select not in ("consensus", "reprojection"):
+            raise ValueError(f"SAMPLE_SELECT must be 'consensus', 'reprojection' or none, got {select!r}")
         return select
 
     def eval_step(self, batch, prefix=None, constraint=None, parse=True, share_encoder=None):
@@ -972,6 +981,31 @@ class PlankModel(nn.Module):
         tokens = output_value.to(device=self._flat.device, dtype=torch.int64)
         return _redraw(tokens, int(self.token.END), int(self.token.PAD), int(num_bits), self.num_output_dof, self.max_input_length,
                        with_type="input_embeddings.input_type.weight" in self._shapes)
+
+    def _reprojection_kw(self, tol, types):
+        """What decode._reprojection needs of this model, with a call's ``tol`` / ``types`` (None: the model's setting)."""
+        from .decode import check_reprojection
+        if self.num_output_dof != 6:
+            raise ValueError("the reprojection score renders planks of six output DOF")
+        tol, types = check_reprojection(self.reprojection_tol if tol is None else tol, self.reprojection_types if types is None else types)
+        return dict(end_token=int(self.token.END), pad_token=int(self.token.PAD), num_bits=(int(self.vocab_size) - 2).bit_length() - 1,
+                    dof=self.num_output_dof, max_input_length=self.max_input_length,
+                    with_type=self._shapes["input_embeddings.input_type.weight"][0] >= 1, tol=tol, types=types)
+
+    def reprojection(self, batch, output_value=None, tol=None, types=None):
+        """How well the three views of one program per drawing match the drawing that was given (decode.reprojection_scores;
+        DESIGN.md section 30): ``output_value`` int [B, n] - of ``eval_step``, ``sample`` or, the default, ``batch["output_value"]``,
+        which makes it a data check of every drawing against its own program - is rendered on the device (``redraw``) and
+        compared with the batch's input rows by one ``ops.line_overlap``.  Line drawings only: the tokens of a sideface input
+        are faces, not lines.  ``tol`` (quantisation levels; None: the model's REPROJECTION_TOL, default 1) and ``types``
+        (``ignore`` | ``match`` | ``visible``; None: the model's REPROJECTION_TYPES, default ``ignore``).  Returns
+        ``reprojection_precision`` / ``reprojection_recall`` / ``reprojection_f1`` float64 [B], ``reprojection_counts`` int32 [B, 8]
+        and ``reprojection_flags`` int32 [B] (the rendering's PA_RENDER_* bits); nothing is read back."""
+        self._require_gpu()
+        from .decode import _reprojection
+        tokens = batch["output_value"] if output_value is None else output_value
+        tokens = tokens.to(device=self._flat.device, dtype=torch.int64)
+        return _reprojection(batch, tokens, pairs=None, **self._reprojection_kw(tol, types))
 
     def score(self, batch, tokens=None, attach=None, lengths=None):
         """Log-likelihood of given sequences under the model, on the GPU: the greedy decode step with every position forced
@@ -1085,7 +1119,8 @@ class PlankModel(nn.Module):
         return self._decode_dict(batch, dec.run(batch, prefix=prefix, constraint=self._grammar(constraint)), prefix, parse)
 
     def sample(self, batch, num_samples, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=0.0, prefix=None,
-               constraint=None, parse=True, select=None, consensus_threshold=None, share_encoder=None):
+               constraint=None, parse=True, select=None, consensus_threshold=None, share_encoder=None, reprojection_tol=None,
+               reprojection_types=None):
         """Seeded sampling decode (decode.SampleDecoder): the eval_step dict of the best sample of every drawing (by score /
         len^length_penalty) plus ``scores`` [B, N] (log-likelihood of every sample) and ``sample_tokens`` / ``sample_attach``
         [B, N, n], samples in final-ranking order.  The same seed and batch give the same samples on every call.  ``prefix``: as in
@@ -1097,9 +1132,16 @@ class PlankModel(nn.Module):
         then also has ``consensus_f1`` float64 [B, N] (each sample's mean F1 against the others) and ``consensus_index`` int64 [B];
         ``scores`` / ``sample_tokens`` / ``sample_attach`` and their order are those of ``select=None``.
 
+        ``select="reprojection"`` (decode.reprojection_select): the sample whose rendered three views match
+        the given line drawing best - the largest reprojection F1 within ``reprojection_tol`` levels under ``reprojection_types``
+        (None: the model's settings), the most likely one among equal bits; it needs no ground truth and acts on the finished
+        samples only, so it works with ``prefix``, ``constraint`` and ``share_encoder``.  The dict then also has
+        ``reprojection_index`` int64 [B] and ``reprojection_precision`` / ``_recall`` / ``_f1`` float64 [B, N],
+        ``reprojection_counts`` int32 [B, N, 8] and ``reprojection_flags`` int32 [B, N]; the rest as under ``consensus``.
+
         ``share_encoder`` (None: the model's setting): one encoder pass and one memory per drawing for its N samples (DESIGN.md
         section 25); the draws are those of (seed, b, n, t) either way."""
-        from .decode import SampleDecoder, consensus_select
+        from .decode import SampleDecoder, _pick_reprojection, _reprojection, _reprojection_pairs, consensus_select
         select = self._check_select(select)
         share = self._share(share_encoder)
         key = ("sample", int(num_samples), float(temperature), int(top_k), float(top_p), float(length_penalty)) + self._share_key(share)
@@ -1112,8 +1154,15 @@ class PlankModel(nn.Module):
             pick = consensus_select(r["sample_tokens"], self.token.END, 0.5 if consensus_threshold is None else consensus_threshold)
             at = pick["consensus_index"][:, None, None].expand(-1, 1, r["sample_tokens"].shape[2])
             r = dict(r, tokens=r["sample_tokens"].gather(1, at)[:, 0], attach=r["sample_attach"].gather(1, at)[:, 0])
+        if select == "reprojection":
+            kw = self._reprojection_kw(reprojection_tol, reprojection_types)
+            st = r["sample_tokens"]
+            B, N, n = st.shape
+            pick = _pick_reprojection(_reprojection(batch, st.reshape(B * N, n), pairs=_reprojection_pairs(B, N, st.device), **kw), B, N)
+            at = pick["reprojection_index"][:, None, None].expand(-1, 1, n)
+            r = dict(r, tokens=st.gather(1, at)[:, 0], attach=r["sample_attach"].gather(1, at)[:, 0])
         out = self._decode_dict(batch, r, prefix, parse)
-        if select == "consensus":
+        if select is not None:
             out.update(pick)
         return out
 
@@ -1235,8 +1284,10 @@ def build_model(cfg):
     default 1), ``TOP_K`` (>= 0, 0 = off), ``TOP_P`` (in (0, 1], 1 = off) and ``SAMPLE_SEED`` (default 0).  ``CONSTRAIN_PLANKS``
     (bool, default off): eval_step decodes - in whichever mode - under the plank grammar of DESIGN.md section 15, with
     ``MIN_PLANKS`` (default 1) and ``MAX_PLANKS`` (default: the last plank boundary of the decode).  ``SAMPLE_SELECT``
-    (``consensus``; default none): which of the NUM_SAMPLES samples eval_step returns (PlankModel.sample); it needs NUM_SAMPLES
->= 1.  ``LABEL_SMOOTHING`` (a number in [0, 1), default 0): eps of train_step's label smoothing.  ``SHARE_ENCODER`` (bool, default
+    (``consensus`` | ``reprojection``; default none): which of the NUM_SAMPLES samples eval_step returns (PlankModel.sample); it
+    needs NUM_SAMPLES >= 1, ``reprojection`` also six output DOF.  ``REPROJECTION_TOL`` (an integer in [0, 255], default 1) and
+    ``REPROJECTION_TYPES`` (``ignore`` | ``match`` | ``visible``, default ``ignore``; ``match`` needs NUM_TYPE >= 1): the options of
+    the reprojection score.  ``LABEL_SMOOTHING`` (a number in [0, 1), default 0): eps of train_step's label smoothing.  ``SHARE_ENCODER`` (bool, default
     off): beam search, sampling and sequence-level training run one encoder pass and keep one memory per drawing (DESIGN.md section
     25).  A bad value, SAMPLE_SELECT without samples, or
     NUM_SAMPLES >= 1 together with BEAM_SIZE > 1, raises ValueError."""
@@ -1260,4 +1311,5 @@ def build_model(cfg):
         cfg.TOKEN, compute_dtype=dtype, beam_size=opt("BEAM_SIZE", 1), length_penalty=float(opt("LENGTH_PENALTY", 0.0)),
         num_samples=opt("NUM_SAMPLES", 0), temperature=opt("TEMPERATURE", 1.0), top_k=opt("TOP_K", 0), top_p=opt("TOP_P", 1.0),
         sample_seed=opt("SAMPLE_SEED", 0), constraint=grammar, sample_select=opt("SAMPLE_SELECT"),
-        label_smoothing=opt("LABEL_SMOOTHING", 0.0), share_encoder=opt("SHARE_ENCODER", False))
+        label_smoothing=opt("LABEL_SMOOTHING", 0.0), share_encoder=opt("SHARE_ENCODER", False),
+        reprojection_tol=opt("REPROJECTION_TOL", 1), reprojection_types=opt("REPROJECTION_TYPES", "ignore"))

@@ -621,6 +621,79 @@ def plank_match(seq_a, seq_b, pairs=None, *, end_token, filter_a, filter_b, thre
     return out
 
 
+OVERLAP_MODES = {"ignore": 0, "match": 1, "visible": 2}       # include/plank_hip.h PA_OVERLAP_*
+
+
+def _overlap_side(name, side):
+    """``side`` - a batch dict or a (value, view[, type]) tuple - as three 2-D int64 device tensors of one shape and one row
+    stride (copied only where they are not that already) and the stride."""
+    if isinstance(side, dict):
+        side = (side.get("input_value"), side.get("input_view"), side.get("input_type"))
+    if not isinstance(side, (tuple, list)) or len(side) not in (2, 3):
+        raise TypeError(f"{name} must be a dict with input_value / input_view / optional input_type, or a tuple of those")
+    rows = [side[0], side[1], side[2] if len(side) == 3 else None]
+    for key, t in zip(("value", "view", "type"), rows):
+        if t is None and key == "type":
+            continue
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 2):
+            raise TypeError(f"{name}: {key} must be a 2-D int64 device tensor")
+        if t.shape != rows[0].shape or t.device != rows[0].device:
+            raise ValueError(f"{name}: {key} {tuple(t.shape)} on {t.device} against value {tuple(rows[0].shape)} on {rows[0].device}")
+    have = [t for t in rows if t is not None]
+    if any((t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) != have[0].stride(0) for t in have):
+        rows = [None if t is None else t.contiguous() for t in rows]
+    v = rows[0]
+    return rows, (v.stride(0) if v.shape[0] > 1 else v.shape[1])
+
+
+def line_overlap(a, b, pairs=None, *, end_token, num_bits, tol=1, types="ignore", check_pairs=True):
+    """Encoder rows compared as sets of axis-aligned lines, one launch for all pairs (pa_line_overlap, csrc/overlap.hip; DESIGN.md
+    section 30): the counts behind the reprojection score.
+
+    ``a`` (the given drawings) and ``b`` (the renderings): a dict with ``input_value`` / ``input_view`` / optional ``input_type``
+    or a tuple ``(value, view[, type])`` of int64 device tensors [Ra, Sa] / [Rb, Sb], last dimension contiguous; the rows of a
+    side share one row stride (they are copied where they do not).  Line drawings only: the tokens of a sideface input are
+    faces, not lines.  ``pairs`` / ``check_pairs``: as for ``plank_match``.  ``tol``: the tolerance in quantisation levels, 0 ..
+    255.  ``types``: ``ignore`` (no type is read), ``match`` (lines match at equal type only; both sides need a type row, else
+    ValueError) or ``visible`` (only the type-0 lines of ``b`` take part).  Returns int32 [n, 8] on the device: cov(A|B), len(A),
+    cov(B|A), len(B), kept_A, kept_B, skipped_A, skipped_B (include/plank_hip.h); nothing is read back."""
+    if types not in OVERLAP_MODES:
+        raise ValueError(f"types must be one of {tuple(OVERLAP_MODES)}, not {types!r}")
+    (va, wa, ta), sa = _overlap_side("a", a)
+    (vb, wb, tb), sb = _overlap_side("b", b)
+    if types == "match" and (ta is None or tb is None):
+        raise ValueError("types='match' needs a type row on both sides")
+    if vb.device != va.device:
+        raise ValueError("a and b must be on the same device")
+    dev = va.device
+    pa = pb = None
+    if pairs is None:
+        if va.shape[0] != vb.shape[0]:
+            raise ValueError(f"without pairs both sides need the same number of rows ({va.shape[0]} != {vb.shape[0]})")
+        n = va.shape[0]
+    else:
+        p = torch.as_tensor(pairs)
+        if p.numel() == 0 and p.dim() == 1:                   # an empty list: no pairs
+            p = torch.empty(0, 2, dtype=torch.int32)
+        if p.dim() != 2 or p.shape[1] != 2 or p.dtype in (torch.bool, torch.float16, torch.bfloat16, torch.float32, torch.float64):
+            raise ValueError("pairs must be an integer [n, 2] tensor")
+        n = p.shape[0]
+        if n and (not p.is_cuda or check_pairs):
+            lo, hi = p.amin(0).tolist(), p.amax(0).tolist()
+            if min(lo) < 0 or hi[0] >= va.shape[0] or hi[1] >= vb.shape[0]:
+                raise IndexError(f"pairs name rows outside a ({va.shape[0]} rows) / b ({vb.shape[0]} rows)")
+        p = p.to(device=dev, dtype=torch.int32)
+        pa, pb = p[:, 0].contiguous(), p[:, 1].contiguous()
+    out = torch.empty(n, 8, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        L.check(L.lib().pa_line_overlap(L.ptr(va), L.ptr(wa), L.ptr(ta), C.c_int64(sa), int(va.shape[1]), L.ptr(vb), L.ptr(wb), L.ptr(tb),
+                                        C.c_int64(sb), int(vb.shape[1]), L.ptr(pa), L.ptr(pb), int(n), int(end_token), int(num_bits),
+                                        int(tol), OVERLAP_MODES[types], L.ptr(out), L.stream()), "pa_line_overlap")
+    return out
+
+
 RENDER_MAX_PLANKS = 32                # include/plank_hip.h PA_RENDER_MAX_PLANKS
 
 

@@ -28,6 +28,7 @@ from .config import CfgNode, load_cli_config
 from .data import SynthSpec, synth_sample
 from .datasets import LineDataset, SidefaceDataset, extract_mode, parse_splits_list, render_mode  # noqa: F401  (parse_splits_list re-exported)
 from .metric import DevicePlankScorer, PlankScorer, planks_of_row, valid_planks
+from .distributed import allreduce_metric_sums
 from .models import build_model
 
 
@@ -90,6 +91,10 @@ class Trainer(torch.nn.Module):
         self.extract_sideface = extract_option(self.hparams_dict)      # DATA.EXTRACT_SIDEFACE, validated (sideface kind only)
         self.render_drawings = render_option(self.hparams_dict)        # DATA.RENDER_DRAWINGS, validated
         self._train_reward = None
+        # REPROJECTION_METRIC: true (opt-in): validation / test also average the reprojection F1 of the returned programs - how well
+        # their rendered three views match the given drawings (PlankModel.reprojection), on the device
+        self.reprojection_metric = reprojection_option(self.hparams_dict, self.device_kind, cfg.DATA.NUM_OUTPUT_DOF)
+        self._reprojection_sums = None         # float64 [2] on the device: the sum of F1 and the number of drawings
 
     # ------------------------------------------------------------------ logging (self.log of Lightning)
     def log(self, name, value, **kw):
@@ -182,18 +187,32 @@ class Trainer(torch.nn.Module):
         ok = torch.all(torch.abs(pred[1:, 3:] - pred[1:, :3]) != 0, dim=1)
         return torch.concat((pred[:1], pred[1:][ok]))
 
+    def _add_reprojection(self, batch, samples):
+        """REPROJECTION_METRIC: the reprojection F1 of the returned programs joins the running sums; nothing is read back."""
+        if not self.reprojection_metric:
+            return
+        f1 = self.model.reprojection(batch, samples)["reprojection_f1"]
+        sums = torch.stack((f1.sum(), torch.full((), float(f1.numel()), dtype=torch.float64, device=f1.device)))
+        self._reprojection_sums = sums if self._reprojection_sums is None else self._reprojection_sums + sums
+
     def validation_step(self, batch, batch_idx):
         if self.device_metric:
             outputs = self.model.eval_step(batch, parse=False)
             self.scorer.add_batch(outputs["samples"], batch["output_value"])
+            self._add_reprojection(batch, outputs["samples"])
             return
         outputs = self.model(batch)
         for pred, gt in zip(outputs["predicts"], outputs["groundtruths"]):
             self.scorer.add(self._valid_pred(pred), gt)
+        self._add_reprojection(batch, outputs["samples"])
 
     def _log_means(self, stage):
         for key, value in zip(("precision", "recall", "fmeasure"), self.scorer.means()):
             self.log(f"{stage}/{key}", value)
+        if self.reprojection_metric:
+            sums, self._reprojection_sums = self._reprojection_sums, None
+            sums = allreduce_metric_sums(torch.zeros(2, dtype=torch.float64) if sums is None else sums.cpu())
+            self.log(f"{stage}/reprojection_f1", float(sums[0]) / max(float(sums[1]), 1.0))
 
     def validation_epoch_end(self, outputs=None):
         self._log_means("val")
@@ -203,6 +222,7 @@ class Trainer(torch.nn.Module):
         [n, 6], ground-truth planks, attach row, scores).  Beside the scorer's read-back of its integers, ONE device-to-host
         copy per batch: decoded tokens, attach and ground-truth tokens side by side in one tensor."""
         outputs = self.model.eval_step(batch, parse=False)
+        self._add_reprojection(batch, outputs["samples"])
         scores = self.scorer.add_batch(outputs["samples"], batch["output_value"], scores=True, keep=keep)
         end = self.cfg.TOKEN.END
         n = outputs["samples"].shape[1]
@@ -222,6 +242,7 @@ class Trainer(torch.nn.Module):
                                                       "groundtruth": gt.reshape(-1, 6).tolist(), **scores})
             return
         outputs = self.model(batch)
+        self._add_reprojection(batch, outputs["samples"])
         for name, pred, gt, atta in zip(batch["name"], outputs["predicts"], outputs["groundtruths"], outputs["attach"]):
             vp = self._valid_pred(pred)
             scores = self.scorer.add(vp, gt)
@@ -536,6 +557,23 @@ def render_option(hparams):
     kind's device dataset alike."""
     data = hparams.get("DATA") or {}
     return render_mode(data.get("RENDER_DRAWINGS") if hasattr(data, "get") else None)
+
+
+def reprojection_option(hparams, device_kind="line", num_output_dof=6):
+    """``REPROJECTION_METRIC`` of the hparams, validated -> bool (default False): validation and test also log
+    ``val/reprojection_f1`` / ``test/reprojection_f1``, the mean reprojection F1 of the returned programs (DESIGN.md section 30;
+    its tolerance and type mode are MODEL.REPROJECTION_TOL / REPROJECTION_TYPES).  The score is defined for line drawings and
+    planks of six DOF: the sideface kind and any other DOF are refused."""
+    v = hparams.get("REPROJECTION_METRIC")
+    if v is None:
+        return False
+    if not isinstance(v, bool):
+        raise ValueError(f"REPROJECTION_METRIC must be a bool, got {v!r}")
+    if v and device_kind != "line":
+        raise ValueError("REPROJECTION_METRIC compares line drawings: the tokens of a sideface input are faces, not lines")
+    if v and int(num_output_dof) != 6:
+        raise ValueError("REPROJECTION_METRIC renders planks of six output DOF")
+    return v
 
 
 def seq_train_seed(seed, global_step, rank):
