@@ -981,6 +981,11 @@ int pa_dec_cross_mq32_group(float* ctx, const float* qt, const float* mem, const
  * sit in a captured graph). */
 int pa_dec_self_mq32(float* ctx, const float* qt, const float* xcache, const int32_t* t_dev, int32_t B, int32_t Tmax, int32_t H,
                      int32_t d, void* stream);
+/* The self-attention form in both types (dtype PA_F32 / PA_BF16: the type of ctx, qt and xcache; the bf16 form is what the bf16 step
+ * runs from PLANK_DECODE_MQ_SELF_MINB rows on).  nparts 0: one block per row - with PA_F32 that is pa_dec_self_mq32, bit for bit;
+ * n > 0: n range blocks per row, or 1 where ws cannot hold them (ws as for pa_dec_cross_mq_group with units = B). */
+int pa_dec_self_mq_ws(void* ctx, const void* qt, const void* xcache, const int32_t* t_dev, int32_t B, int32_t Tmax, int32_t H, int32_t d,
+                      int32_t dtype, int32_t nparts, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- device-resident dataset (csrc/tokenise.hip; plankassembly_amd/device_data.py) ----
  * One launch, one block of 256 threads per batch element: the prepared drawings stay in HBM as CSR arrays and a batch is

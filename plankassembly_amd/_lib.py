@@ -312,6 +312,7 @@ def lib():
             "pa_dec_cross_mq_group": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, I64, P]),
             "pa_dec_cross_mq32_group": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, I64, P]),
             "pa_dec_self_mq32": (I, [P, P, P, P, I, I, I, I, P]),
+            "pa_dec_self_mq_ws": (I, [P, P, P, P, I, I, I, I, I, I, P, I64, P]),
             "pa_tokenise_drawings": (I, [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, D, D, D, U, U,
                                          P, P, P, P, P, P, P, P, P, P, P]),
             "pa_tokenise_sideface_drawings": (I, [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, D, D, D, U, U,

@@ -1699,6 +1699,21 @@ extern "C" int pa_dec_self_mq32(float* ctx, const float* qt, const float* xcache
     return launch_cross_mq32(ctx, qt, xcache, nullptr, nullptr, B, Tmax, H, d, (hipStream_t)stream, 1, decode_switches().mq32_w8, t_dev);
 }
 
+// The self-attention form in both types, with range blocks (include/plank_hip.h): what the step launches on its row cache - the bf16
+// form from PLANK_DECODE_MQ_SELF_MINB rows on - reachable on its own (tests/test_dec_mq_float64_gpu.py).
+extern "C" int pa_dec_self_mq_ws(void* ctx, const void* qt, const void* xcache, const int32_t* t_dev, int32_t B, int32_t Tmax, int32_t H,
+                                 int32_t d, int32_t dtype, int32_t nparts, void* ws, int64_t ws_bytes, void* stream) {
+    if (!ctx || !qt || !xcache || !t_dev || nparts < 0 || (dtype != PA_BF16 && dtype != PA_F32)) return PA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(qt) | reinterpret_cast<uintptr_t>(xcache) | reinterpret_cast<uintptr_t>(ctx)) & 15) return PA_EALIGN;
+    const DecodeSwitches& sw = decode_switches();
+    const int parts = nparts > 0 ? std::min(nparts, 64) : 1;
+    if (dtype == PA_BF16)
+        return launch_cross_mq((bf16*)ctx, (const bf16*)qt, (const bf16*)xcache, nullptr, nullptr, B, Tmax, H, d, (hipStream_t)stream, parts, sw.mq_nt,
+                               sw.mq_swap, ws, ws_bytes, t_dev);
+    return launch_cross_mq32((float*)ctx, (const float*)qt, (const float*)xcache, nullptr, nullptr, B, Tmax, H, d, (hipStream_t)stream, parts, sw.mq32_w8,
+                             t_dev, ws, ws_bytes);
+}
+
 extern "C" int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void** first_end, void** t_dev) {
     if (!m || !m->dec || !tokens || !attach || !first_end || !t_dev) return PA_EINVAL;
     *tokens = m->dec->tokens; *attach = m->dec->attach; *first_end = m->dec->first_end; *t_dev = m->dec->t_dev;

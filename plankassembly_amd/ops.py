@@ -575,6 +575,17 @@ def dec_self_mq32(qt, xcache, t_dev):
     return ctx
 
 
+def dec_self_mq(qt, xcache, t_dev, *, nparts=0, ws=None):
+    """The self-attention form in both types (pa_dec_self_mq_ws): qt [B, H, 512] and xcache [B, Tmax, 512] f32 or bf16, t_dev int32 device
+    scalar.  ``nparts`` 0 = one block per row, n = n range blocks per row in ``ws`` (zeroed uint8 scratch; None: one block per row)."""
+    B, H, d = qt.shape
+    ctx = torch.empty_like(qt)
+    L.check(L.lib().pa_dec_self_mq_ws(L.ptr(ctx), L.ptr(qt), L.ptr(xcache), L.ptr(t_dev), B, xcache.shape[1], H, d,
+                                      0 if qt.dtype == torch.float32 else 1, int(nparts), L.ptr(ws),
+                                      C.c_int64(ws.numel() if ws is not None else 0), L.stream()), "pa_dec_self_mq_ws")
+    return ctx
+
+
 def plank_match(seq_a, seq_b, pairs=None, *, end_token, filter_a, filter_b, threshold, check_pairs=True):
     """Token rows compared as sets of planks, one launch for all pairs (pa_plank_match, csrc/match.hip).
 
