@@ -986,6 +986,32 @@ int pa_dec_self_mq32(float* ctx, const float* qt, const float* xcache, const int
  * n > 0: n range blocks per row, or 1 where ws cannot hold them (ws as for pa_dec_cross_mq_group with units = B). */
 int pa_dec_self_mq_ws(void* ctx, const void* qt, const void* xcache, const int32_t* t_dev, int32_t B, int32_t Tmax, int32_t H, int32_t d,
                       int32_t dtype, int32_t nparts, void* ws, int64_t ws_bytes, void* stream);
+/* The kernels csrc/decode.hip itself defines, each on its own with the grid the step gives it (tests).  dtype
+ * PA_F32 / PA_BF16 is the type of the rows.
+ *   pa_dec_attn: the single-query attention over per-head caches kc / vc [B / G][H][Lmax][dh] -> out [B][d]; q rows ldq apart.  The key
+ *     count is cu[b / G + 1] - cu[b / G], else fixed_lk > 0, else *t_dev + 1 read on the device.  newkv [B][3d] (the self form): key
+ *     Lk - 1 is taken from its K / V slices and appended to row Lk - 1 of both caches.  kpm [B / G][Lmax], 1 = PAD.  Refused before any
+ *     launch: PA_EINVAL for a NULL out / q / kc / vc, no source of the key count, fixed_lk > Lmax, G < 1, B % G != 0, newkv together
+ *     with cu, kpm or G > 1; PA_ESHAPE for d / H outside {16, 32, 64}; PA_EALIGN for out / q / kc / vc / newkv off 16 bytes or ldq not a
+ *     multiple of the 16-byte vector (4 f32, 8 bf16).
+ *   pa_dec_split_heads: kv [rows][2d] (k | v) -> kc, vc [B][H][S][dh]; dense rows b S + s, or packed with cu [B + 1] and rowmap [rows]
+ *     (the dense row of a packed one; both or neither).
+ *   pa_dec_embed: x [B][d] (dtype) = value[tokens[b][t - 1]] + coord[(t - 1) % dof] + pos[(t - 1) / dof], zeros at t = *t_dev = 0; x_lp
+ *     (optional) the bf16 copy of the same f32 sums.
+ *   pa_dec_row_dist: per row, what the greedy / beam / sampling / forced tails compute before they choose: h stored into row t of
+ *     hid_cache [Tmax][rows][d], then p of every candidate index - vocab k at p_out[row][k], pointer j <= t at p_out[row][V + j]
+ *     (p_out [rows][V + Tmax]; nothing else is written, and no pointer while t + 1 < 6) - and (vmax, vsum, pmax, psum, prob) in
+ *     stats [rows][5].  0 <= *t_dev < Tmax <= 2048 is the caller's to keep. */
+int pa_dec_attn(void* out, const void* q, int32_t ldq, void* kc, void* vc, int32_t Lmax, const uint8_t* kpm, int32_t fixed_lk,
+                const int32_t* t_dev, int32_t B, int32_t H, int32_t d, int32_t dtype, const int32_t* cu, const void* newkv, int32_t G,
+                void* stream);
+int pa_dec_split_heads(void* kc, void* vc, const void* kv, int64_t rows, int32_t S, int32_t d, int32_t H, int32_t dtype, const int32_t* cu,
+                       const int32_t* rowmap, void* stream);
+int pa_dec_embed(void* x, void* x_lp, const float* value, const float* coord, const float* pos, const int64_t* tokens, int32_t Tmax,
+                 const int32_t* t_dev, int32_t B, int32_t d, int32_t dof, int32_t dtype, void* stream);
+int pa_dec_row_dist(float* p_out, float* stats, const float* vlog, int32_t ldv, const void* pfeat, const void* h, void* hid_cache,
+                    const float* sw_w, const float* sw_b, const int32_t* t_dev, int32_t rows, int32_t Tmax, int32_t d, int32_t V,
+                    int32_t dtype, void* stream);
 
 /* ---- device-resident dataset (csrc/tokenise.hip; plankassembly_amd/device_data.py) ----
  * One launch, one block of 256 threads per batch element: the prepared drawings stay in HBM as CSR arrays and a batch is

@@ -313,6 +313,10 @@ def lib():
             "pa_dec_cross_mq32_group": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, I64, P]),
             "pa_dec_self_mq32": (I, [P, P, P, P, I, I, I, I, P]),
             "pa_dec_self_mq_ws": (I, [P, P, P, P, I, I, I, I, I, I, P, I64, P]),
+            "pa_dec_attn": (I, [P, P, I, P, P, I, P, I, P, I, I, I, I, P, P, I, P]),
+            "pa_dec_split_heads": (I, [P, P, P, I64, I, I, I, I, P, P, P]),
+            "pa_dec_embed": (I, [P, P, P, P, P, P, I, P, I, I, I, I, P]),
+            "pa_dec_row_dist": (I, [P, P, P, I, P, P, P, P, P, P, I, I, I, I, I, P]),
             "pa_tokenise_drawings": (I, [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, D, D, D, U, U,
                                          P, P, P, P, P, P, P, P, P, P, P]),
             "pa_tokenise_sideface_drawings": (I, [P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, D, D, D, U, U,

@@ -466,6 +466,33 @@ __device__ __forceinline__ float row_dist_at(const RowDist& r, const float* vr, 
     return j < t ? dist_p_ptr(r, plog, t, j) : 0.f;
 }
 
+// The whole distribution of a row, stand-alone (pa_dec_row_dist): what the four tails do before they choose - the
+// hidden row stored into cache row t, row_dist_prepare, then every p row_dist_visit hands out (jend = t + 1, no constraint) written to
+// p_out [rows][V + Tmax] by its candidate index, and the RowDist fields to stats [rows][5].  No arithmetic of its own.
+template <typename T>
+__global__ __launch_bounds__(256) void dec_row_dist_kernel(float* p_out, float* stats, const float* vlog, int ldv, const T* pfeat, const T* h,
+                                                           T* hid_cache, const float* sw_w, const float* sw_b, const int32_t* t_dev,
+                                                           int Tmax, int d, int V) {
+    __shared__ float plog[MAX_T];
+    __shared__ float sh[4];
+    __shared__ float s_sw;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int t = *t_dev;
+    const T* hb = h + (int64_t)b * d;
+    const int64_t nb = gridDim.x;
+    T* cache = hid_cache + (int64_t)b * d;                          // [Tmax][rows][d], as in dec_sample_kernel
+    for (int c = tid; c < d; c += 256) cache[(int64_t)t * nb * d + c] = hb[c];
+    const float* vr = vlog + (int64_t)b * ldv;
+    const RowDist rd = row_dist_prepare<T>(vr, V, pfeat + (int64_t)b * d, hb, cache, nb, t, d, sw_w, sw_b, plog, sh, &s_sw);
+    const Allow al = make_allow(ConstraintDev{0, 0, 0, 0, 0}, nullptr, V, t);
+    float* po = p_out + (int64_t)b * (V + Tmax);
+    row_dist_visit(rd, vr, V, plog, t, t + 1, al, [&](float p, int k, bool) { po[k] = p; });
+    if (tid == 0) {
+        float* so = stats + (int64_t)b * 5;
+        so[0] = rd.vmax; so[1] = rd.vsum; so[2] = rd.pmax; so[3] = rd.psum; so[4] = rd.prob;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Forced prefixes.  The prefix arena of pa_decode_prefix_begin: per row r a length plen[r] and the forced
 // candidate of every position t < plen[r] - ptok, and patt = -1 for the vocab entry ptok or j >= 0 for the pointer candidate j -
@@ -1074,9 +1101,9 @@ size_t dec_layout(const pa_model_cfg& c, const DecodePlan& pl, DecodeLayout* L, 
 }
 
 template <typename T>
-int launch_attn(pa_model* m, T* out, const T* q, int ldq, T* kc, T* vc, int Lmax, const uint8_t* kpm,
+int launch_attn(int d, int H, T* out, const T* q, int ldq, T* kc, T* vc, int Lmax, const uint8_t* kpm,
                 int fixed_lk, const int32_t* t_dev, int B, void* st, const int32_t* cu = nullptr, const T* newkv = nullptr, int G = 1) {
-    const int d = m->cfg.d_model, H = m->cfg.n_head, dh = d / H;
+    const int dh = d / H;
     const float scale = 1.0f / sqrtf((float)dh);
     dim3 grid(H, B);
     hipStream_t s = (hipStream_t)st;
@@ -1287,14 +1314,14 @@ template <typename T>
 int self_attn(pa_model* m, int i, void* st) {
     DecodeLayout* L = m->dec;
     const int d = m->cfg.d_model;
-    return launch_attn<T>(m, (T*)L->ao, (const T*)L->qkv, 3 * d, (T*)L->self_k[i], (T*)L->self_v[i], L->Tmax, nullptr, 0, L->t_dev, L->B, st,
+    return launch_attn<T>(d, m->cfg.n_head, (T*)L->ao, (const T*)L->qkv, 3 * d, (T*)L->self_k[i], (T*)L->self_v[i], L->Tmax, nullptr, 0, L->t_dev, L->B, st,
                           nullptr, (const T*)L->qkv);
 }
 // cross-attention of layer i over the per-head K / V caches of the memory (one set per drawing: the G rows of a group share it)
 template <typename T>
 int cross_attn(pa_model* m, int i, void* st) {
     DecodeLayout* L = m->dec;
-    return launch_attn<T>(m, (T*)L->ao, (const T*)L->q, m->cfg.d_model, (T*)L->cross_k[i], (T*)L->cross_v[i], L->S, L->cu ? nullptr : L->kpm,
+    return launch_attn<T>(m->cfg.d_model, m->cfg.n_head, (T*)L->ao, (const T*)L->q, m->cfg.d_model, (T*)L->cross_k[i], (T*)L->cross_v[i], L->S, L->cu ? nullptr : L->kpm,
                           L->S, L->t_dev, L->B, st, L->cu, (const T*)nullptr, L->G);
 }
 
@@ -1712,6 +1739,71 @@ extern "C" int pa_dec_self_mq_ws(void* ctx, const void* qt, const void* xcache, 
                                sw.mq_swap, ws, ws_bytes, t_dev);
     return launch_cross_mq32((float*)ctx, (const float*)qt, (const float*)xcache, nullptr, nullptr, B, Tmax, H, d, (hipStream_t)stream, parts, sw.mq32_w8,
                              t_dev, ws, ws_bytes);
+}
+
+// ---- the step's own kernels on their own (include/plank_hip.h; tests/test_dec_step_float64_gpu.py) -------------
+static bool off16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+extern "C" int pa_dec_attn(void* out, const void* q, int32_t ldq, void* kc, void* vc, int32_t Lmax, const uint8_t* kpm, int32_t fixed_lk,
+                           const int32_t* t_dev, int32_t B, int32_t H, int32_t d, int32_t dtype, const int32_t* cu, const void* newkv, int32_t G,
+                           void* stream) {
+    if (!out || !q || !kc || !vc || (dtype != PA_BF16 && dtype != PA_F32)) return PA_EINVAL;
+    if (!cu && fixed_lk <= 0 && !t_dev) return PA_EINVAL;           // (the key count has to come from somewhere)
+    if (B <= 0 || H <= 0 || d <= 0 || d % H || Lmax <= 0 || fixed_lk > Lmax || G < 1 || B % G) return PA_EINVAL;
+    if (newkv && (cu || kpm || G > 1)) return PA_EINVAL;            // (the self form: per-row caches, no mask, no packing)
+    const int dh = d / H, vecw = dtype == PA_BF16 ? 8 : 4;
+    if (dh != 16 && dh != 32 && dh != 64) return PA_ESHAPE;
+    if (off16(out) || off16(q) || off16(kc) || off16(vc) || off16(newkv) || ldq < d || ldq % vecw) return PA_EALIGN;
+    if (dtype == PA_BF16)
+        return launch_attn<bf16>(d, H, (bf16*)out, (const bf16*)q, ldq, (bf16*)kc, (bf16*)vc, Lmax, kpm, fixed_lk, t_dev, B, stream, cu, (const bf16*)newkv, G);
+    return launch_attn<float>(d, H, (float*)out, (const float*)q, ldq, (float*)kc, (float*)vc, Lmax, kpm, fixed_lk, t_dev, B, stream, cu, (const float*)newkv, G);
+}
+
+extern "C" int pa_dec_split_heads(void* kc, void* vc, const void* kv, int64_t rows, int32_t S, int32_t d, int32_t H, int32_t dtype,
+                                  const int32_t* cu, const int32_t* rowmap, void* stream) {
+    if (!kc || !vc || !kv || (dtype != PA_BF16 && dtype != PA_F32) || (cu == nullptr) != (rowmap == nullptr)) return PA_EINVAL;
+    if (rows < 0 || S <= 0 || H <= 0 || d <= 0 || d % H) return PA_EINVAL;
+    if ((d / H) % 4) return PA_ESHAPE;                              // (a 4-element vector stays inside one head)
+    if (off16(kc) || off16(vc) || off16(kv)) return PA_EALIGN;
+    if (rows == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == PA_BF16)
+        PA_LAUNCH(dec_split_heads_kernel<bf16>, dim3(2048), dim3(256), 0, s, (bf16*)kc, (bf16*)vc, (const bf16*)kv, rows, S, d, H, cu, rowmap);
+    else
+        PA_LAUNCH(dec_split_heads_kernel<float>, dim3(2048), dim3(256), 0, s, (float*)kc, (float*)vc, (const float*)kv, rows, S, d, H, cu, rowmap);
+    return 0;
+}
+
+extern "C" int pa_dec_embed(void* x, void* x_lp, const float* value, const float* coord, const float* pos, const int64_t* tokens, int32_t Tmax,
+                            const int32_t* t_dev, int32_t B, int32_t d, int32_t dof, int32_t dtype, void* stream) {
+    if (!x || !value || !coord || !pos || !tokens || !t_dev || (dtype != PA_BF16 && dtype != PA_F32)) return PA_EINVAL;
+    if (B <= 0 || d <= 0 || dof <= 0 || Tmax <= 0) return PA_EINVAL;
+    if (d % 4) return PA_ESHAPE;
+    if (off16(x) || off16(x_lp) || off16(value) || off16(coord) || off16(pos)) return PA_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    const int g1 = (B * (d / 4) + 255) / 256;
+    if (dtype == PA_BF16)
+        PA_LAUNCH(dec_embed_kernel<bf16>, dim3(g1), dim3(256), 0, s, (bf16*)x, value, coord, pos, tokens, Tmax, t_dev, B, d, dof, (bf16*)x_lp);
+    else
+        PA_LAUNCH(dec_embed_kernel<float>, dim3(g1), dim3(256), 0, s, (float*)x, value, coord, pos, tokens, Tmax, t_dev, B, d, dof, (bf16*)x_lp);
+    return 0;
+}
+
+extern "C" int pa_dec_row_dist(float* p_out, float* stats, const float* vlog, int32_t ldv, const void* pfeat, const void* h, void* hid_cache,
+                               const float* sw_w, const float* sw_b, const int32_t* t_dev, int32_t rows, int32_t Tmax, int32_t d, int32_t V,
+                               int32_t dtype, void* stream) {
+    if (!p_out || !stats || !vlog || !pfeat || !h || !hid_cache || !sw_w || !sw_b || !t_dev || (dtype != PA_BF16 && dtype != PA_F32)) return PA_EINVAL;
+    if (rows <= 0 || Tmax <= 0 || Tmax > MAX_T || d <= 0 || V <= 0 || ldv < V) return PA_EINVAL;
+    if (d % 8) return PA_ESHAPE;
+    if (off16(pfeat) || off16(h) || off16(hid_cache) || off16(sw_w)) return PA_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == PA_BF16)
+        PA_LAUNCH(dec_row_dist_kernel<bf16>, dim3(rows), dim3(256), 0, s, p_out, stats, vlog, ldv, (const bf16*)pfeat, (const bf16*)h, (bf16*)hid_cache,
+                  sw_w, sw_b, t_dev, Tmax, d, V);
+    else
+        PA_LAUNCH(dec_row_dist_kernel<float>, dim3(rows), dim3(256), 0, s, p_out, stats, vlog, ldv, (const float*)pfeat, (const float*)h,
+                  (float*)hid_cache, sw_w, sw_b, t_dev, Tmax, d, V);
+    return 0;
 }
 
 extern "C" int pa_decode_buffers(pa_model* m, void** tokens, void** attach, void** first_end, void** t_dev) {

@@ -586,6 +586,59 @@ def dec_self_mq(qt, xcache, t_dev, *, nparts=0, ws=None):
     return ctx
 
 
+def _padt(t):
+    return 0 if t.dtype == torch.float32 else 1
+
+
+def dec_attn(q, kc, vc, *, H, d=None, kpm=None, fixed_lk=0, t_dev=None, cu=None, newkv=None, group=1):
+    """The single-query attention of the decode step over per-head caches (pa_dec_attn): q [B, ldq] rows of which the first d columns
+    are the query (``d`` defaults to ldq), kc / vc [B // group, H, Lmax, dh].  Key count: ``cu`` int32 [B // group + 1], else
+    ``fixed_lk`` > 0, else ``t_dev`` + 1 read on the device.  ``newkv`` [B, 3 d] (the self form): key Lk - 1 comes from it and is
+    appended to both caches in place.  Returns out [B, d]."""
+    B, ldq = q.shape
+    d = int(d or ldq)
+    out = torch.empty(B, d, dtype=q.dtype, device=q.device)
+    L.check(L.lib().pa_dec_attn(L.ptr(out), L.ptr(q), ldq, L.ptr(kc), L.ptr(vc), kc.shape[2], L.ptr(kpm), int(fixed_lk), L.ptr(t_dev), B, int(H),
+                                d, _padt(q), L.ptr(cu), L.ptr(newkv), int(group), L.stream()), "pa_dec_attn")
+    return out
+
+
+def dec_split_heads(kv, B, S, H, *, cu=None, rowmap=None):
+    """kv [rows, 2 d] (k | v) -> K, V [B, H, S, dh] (pa_dec_split_heads): dense rows b S + s, or packed rows with ``cu`` [B + 1] and
+    ``rowmap`` [rows].  Positions no row maps to are left as allocated (zeros here)."""
+    rows, d = kv.shape[0], kv.shape[1] // 2
+    kc = torch.zeros(B, H, S, d // H, dtype=kv.dtype, device=kv.device)
+    vc = torch.zeros_like(kc)
+    L.check(L.lib().pa_dec_split_heads(L.ptr(kc), L.ptr(vc), L.ptr(kv), C.c_int64(rows), int(S), d, int(H), _padt(kv), L.ptr(cu), L.ptr(rowmap),
+                                       L.stream()), "pa_dec_split_heads")
+    return kc, vc
+
+
+def dec_embed(value, coord, pos, tokens, t_dev, dof, *, dtype=torch.float32, low_precision_copy=False):
+    """The decode step's input embedding (pa_dec_embed): value / coord / pos f32 tables [*, d], tokens int64 [B, Tmax], t_dev int32 device
+    scalar.  Returns x [B, d] of ``dtype`` (and its bf16 copy with ``low_precision_copy``)."""
+    B, Tmax = tokens.shape
+    d = value.shape[1]
+    x = torch.empty(B, d, dtype=dtype, device=value.device)
+    x_lp = torch.empty(B, d, dtype=torch.bfloat16, device=value.device) if low_precision_copy else None
+    L.check(L.lib().pa_dec_embed(L.ptr(x), L.ptr(x_lp), L.ptr(value), L.ptr(coord), L.ptr(pos), L.ptr(tokens), Tmax, L.ptr(t_dev), B, d, int(dof),
+                                 _padt(x), L.stream()), "pa_dec_embed")
+    return (x, x_lp) if low_precision_copy else x
+
+
+def dec_row_dist(vlog, V, pfeat, h, hid_cache, sw_w, sw_b, t_dev, *, fill=0.0):
+    """The distribution the decode tails choose from (pa_dec_row_dist): vlog f32 [rows, ldv], pfeat / h [rows, d], hid_cache
+    [Tmax, rows, d] (row t is written in place), sw_w [d], sw_b [1] f32, t_dev int32 device scalar.  Returns p [rows, V + Tmax] (vocab k at
+    k, pointer j <= t at V + j; what the kernel does not write holds ``fill``) and stats [rows, 5] = vmax, vsum, pmax, psum, prob."""
+    rows, d = h.shape
+    Tmax = hid_cache.shape[0]
+    p = torch.full((rows, int(V) + Tmax), float(fill), dtype=torch.float32, device=h.device)
+    stats = torch.empty(rows, 5, dtype=torch.float32, device=h.device)
+    L.check(L.lib().pa_dec_row_dist(L.ptr(p), L.ptr(stats), L.ptr(vlog), vlog.stride(0), L.ptr(pfeat), L.ptr(h), L.ptr(hid_cache), L.ptr(sw_w),
+                                    L.ptr(sw_b), L.ptr(t_dev), rows, Tmax, d, int(V), _padt(h), L.stream()), "pa_dec_row_dist")
+    return p, stats
+
+
 def plank_match(seq_a, seq_b, pairs=None, *, end_token, filter_a, filter_b, threshold, check_pairs=True):
     """Token rows compared as sets of planks, one launch for all pairs (pa_plank_match, csrc/match.hip).
 
