@@ -324,6 +324,7 @@ def lib():
             "pa_render_drawings": (I, [P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, I, I, D, D, D, U, U,
                                        P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
             "pa_plank_match": (I, [P, I64, I, P, I64, I, P, P, I, I, I, I, I, D, P, P]),
+            "pa_plank_volume": (I, [P, I64, I, P, I64, I, P, P, I, I, I, P, P]),
             "pa_line_overlap": (I, [P, P, P, I64, I, P, P, P, I64, I, P, P, I, I, I, I, I, P, P]),
             "pa_seq_batch_args_bytes": (I64, []),
             "pa_sequence_batch": (I, [P, P]),

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libplank_hip.so")
 OBJ = os.path.join(HERE, "csrc", "build")
 SOURCES = ["gemm.hip", "rowops.hip", "attention.hip", "decode.hip", "runtime.hip", "tokenise.hip", "match.hip", "seqtrain.hip",
-           "overlap.hip"]
+           "overlap.hip", "volume.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 

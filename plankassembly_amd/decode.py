@@ -815,3 +815,71 @@ def reprojection_select(batch, sample_tokens, token, data_cfg_or_bits, *, tol=1,
     r = reprojection_scores(batch, sample_tokens.reshape(B * N, n), token, data_cfg_or_bits, tol=tol, types=types,
                             pairs=_reprojection_pairs(B, N, sample_tokens.device))
     return _pick_reprojection(r, B, N)
+
+
+def volume_scores(reference_tokens, tokens, end_token, pairs=None):
+    """Decoded programs as solids: how much of the space the reference occupies a program occupies too,
+    and how much of a program's plank volume lies inside another of its own planks.
+
+    ``tokens`` int64 [R, n] on the device: one program per row; ``reference_tokens`` int64 [Rr, m] on the device (side a, the
+    ground truth) or None.  One ``ops.plank_volume`` launch: pair i is (row i, row i), or ``pairs`` int [P, 2] of (reference
+    row, tokens row) - which must exist, they are not checked.  Returns ``volume_iou`` = inter / union, ``volume_recall`` =
+    inter / union(reference), ``volume_precision`` = inter / union(tokens), ``self_overlap`` = (sum - union) / sum of ``tokens``,
+    float64 [P], each 0 where its denominator is 0, and ``volume_counts`` int64 [P, 8].  With ``reference_tokens=None`` - no
+    ground truth is needed for it - only ``self_overlap`` and ``volume_counts`` (``pairs``: int [P] rows of ``tokens``, which are
+    then side a of the counts).  Nothing is read back."""
+    from . import ops
+    from .metric import volume_scores as scores_of
+    if reference_tokens is None:
+        counts = ops.plank_volume(tokens, None, pairs, end_token=end_token, check_pairs=False)
+        return {"self_overlap": scores_of(counts)["self_overlap_a"], "volume_counts": counts}
+    counts = ops.plank_volume(reference_tokens, tokens, pairs, end_token=end_token, check_pairs=False)
+    s = scores_of(counts)
+    return {"volume_iou": s["volume_iou"], "volume_precision": s["volume_precision"], "volume_recall": s["volume_recall"],
+            "self_overlap": s["self_overlap_b"], "volume_counts": counts}
+
+
+def _pick_volume(counts, N, iu0, iu1):
+    """``volume_select`` from the int64 [B, N (N - 1) / 2, 8] counts of the pairs (iu0[k], iu1[k]) - on any device."""
+    from .metric import volume_scores as scores_of
+    B = counts.shape[0]
+    dev = counts.device
+    q = torch.round(scores_of(counts)["volume_iou"] * 2.0 ** 40).to(torch.int64)
+    pairwise = torch.zeros(B, N, N, dtype=torch.int64, device=dev)
+    pairwise[:, iu0, iu1] = q
+    pairwise[:, iu1, iu0] = q
+    utility = pairwise.sum(2)
+    best = utility.max(1, keepdim=True).values
+    index = torch.where(utility == best, torch.arange(N, device=dev)[None, :], N).min(1).values
+    own = torch.zeros(B, N, 8, dtype=torch.int64, device=dev)              # (union, sum) of every sample, as side a of a pair
+    own[:, iu0, :2] = counts[..., 0:2]                                     # every pair of a sample states the same two integers
+    own[:, iu1, :2] = counts[..., 2:4]
+    # (a device tensor as the divisor: torch divides by a host scalar as a multiplication by its reciprocal, one rounding too many)
+    others = torch.full((), float(max(N - 1, 1)), dtype=torch.float64, device=dev)
+    return {"volume_index": index, "volume_iou": utility.double() / 2.0 ** 40 / others,
+            "self_overlap": scores_of(own)["self_overlap_a"]}
+
+
+def volume_select(sample_tokens, end_token):
+    """Minimum-Bayes-risk choice among the N samples of every drawing with the shape IoU as the utility:
+    as ``consensus_select``, with ``volume_iou(n, m)`` in place of the pairwise F1 - graded, so it still ranks where no two
+    samples share a plank at IoU > 0.5.
+
+    ``sample_tokens`` int64 [B, N, n] on the device.  One ``ops.plank_volume`` launch over the pairs n < m of every drawing.  The
+    utility of sample n is the INTEGER sum over m != n of rint(iou * 2^40); the largest wins, the lowest index among equals;
+    two samples that both occupy nothing have IoU 0 with each other.  Returns ``volume_index`` int64 [B], ``volume_iou``
+    float64 [B, N] = utility / 2^40 / max(N - 1, 1) and ``self_overlap`` float64 [B, N], every sample's (sum - union) / sum from
+    the same counts.  Nothing is read back."""
+    from . import ops
+    from .metric import volume_scores as scores_of
+    B, N, n = sample_tokens.shape
+    dev = sample_tokens.device
+    flat = sample_tokens.reshape(B * N, n)
+    if N == 1 or B == 0:
+        own = ops.plank_volume(flat, None, end_token=end_token)
+        return {"volume_index": torch.zeros(B, dtype=torch.int64, device=dev),
+                "volume_iou": torch.zeros(B, N, dtype=torch.float64, device=dev),
+                "self_overlap": scores_of(own)["self_overlap_a"].reshape(B, N)}
+    pairs, iu0, iu1 = _consensus_pairs(B, N, dev)
+    counts = ops.plank_volume(flat, flat, pairs, end_token=end_token, check_pairs=False)
+    return _pick_volume(counts.view(B, -1, 8), N, iu0, iu1)

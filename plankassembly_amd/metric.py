@@ -294,3 +294,68 @@ def overlap_scores(counts):
     den = prec + rec
     f1 = torch.where(den > 0, ((2.0 * prec) * rec) / torch.where(den > 0, den, one), zero)
     return rec, prec, f1
+
+
+def _solid_boxes(row, end_token):
+    """One token row -> its solid planks int64 [k, 6]: cut at the first END, plank 0 dropped, tokens clamped to the int16 range,
+    planks with a zero or negative extent on any axis dropped."""
+    if row is None:
+        return np.zeros((0, 6), dtype=np.int64)
+    row = np.asarray(row, dtype=np.int64).reshape(-1)
+    hits = np.nonzero(row == end_token)[0]
+    planks = (int(hits[0]) if len(hits) else len(row)) // 6
+    boxes = np.clip(row[:6 * planks].reshape(planks, 6)[1:], -32768, 32767)
+    return boxes[np.all(boxes[:, 3:] - boxes[:, :3] > 0, axis=1)]
+
+
+def _union_volume(boxes):
+    """The volume of a union of half-open integer boxes [k, 6], by coordinate compression: per slab of x between consecutive
+    bounds, the boxes that span it are painted into a grid over the compressed y and z bounds."""
+    if len(boxes) == 0:
+        return 0
+    total = 0
+    xs = np.unique(boxes[:, [0, 3]])
+    for x0, x1 in zip(xs[:-1].tolist(), xs[1:].tolist()):
+        live = boxes[(boxes[:, 0] <= x0) & (boxes[:, 3] >= x1)]
+        if len(live) == 0:
+            continue
+        ys, zs = np.unique(live[:, [1, 4]]), np.unique(live[:, [2, 5]])
+        grid = np.zeros((len(ys) - 1, len(zs) - 1), dtype=bool)
+        for j0, j1, k0, k1 in zip(np.searchsorted(ys, live[:, 1]).tolist(), np.searchsorted(ys, live[:, 4]).tolist(),
+                                  np.searchsorted(zs, live[:, 2]).tolist(), np.searchsorted(zs, live[:, 5]).tolist()):
+            grid[j0:j1, k0:k1] = True
+        total += (x1 - x0) * int(np.diff(ys) @ grid.astype(np.int64) @ np.diff(zs))
+    return total
+
+
+def plank_volume_counts(a, b, end_token):
+    """The assembly-volume counts of ONE pair of token rows on the host (``ops.plank_volume`` is the device
+    entry and computes the same integers).  A row is read as ``plank_match`` reads it - cut at its first ``end_token``, L // 6
+    planks, plank 0 dropped, tokens clamped to [-32768, 32767]; a plank is solid if hi - lo > 0 on all three axes and occupies
+    [lo, hi) on each, any other plank occupies nothing and is not counted.  ``b`` may be None (an empty side).  Returns int64
+    [8]: union_a, sum_a, union_b, sum_b, inter, union_ab, n_a, n_b - the volumes of the unions of each side's solid planks, the
+    sums of the planks' own volumes, the volume both unions share, the volume of both together, the solid planks."""
+    A, B = _solid_boxes(a, end_token), _solid_boxes(b, end_token)
+    ua, ub, uab = _union_volume(A), _union_volume(B), _union_volume(np.concatenate((A, B)))
+    own = lambda X: int(np.prod(X[:, 3:] - X[:, :3], axis=1).sum())
+    return np.asarray([ua, own(A), ub, own(B), ua + ub - uab, uab, len(A), len(B)], dtype=np.int64)
+
+
+def volume_scores(counts):
+    """The scores of integer [..., 8] assembly-volume counts (a tensor on any device, or numpy -> numpy) in float64, each ONE
+    division of two exactly converted integers and 0 where its denominator is 0: ``volume_iou`` = inter / union_ab,
+    ``volume_recall`` = inter / union_a (side a is the ground truth), ``volume_precision`` = inter / union_b, ``self_overlap_a`` =
+    (sum_a - union_a) / sum_a and ``self_overlap_b`` alike.  The divisors are tensors: torch divides by a host scalar as a
+    multiplication by its reciprocal."""
+    if not torch.is_tensor(counts):
+        return {k: v.numpy() for k, v in volume_scores(torch.from_numpy(np.asarray(counts, dtype=np.int64))).items()}
+    c = counts.to(torch.int64)
+    one = torch.ones((), dtype=torch.float64, device=c.device)
+    zero = torch.zeros((), dtype=torch.float64, device=c.device)
+
+    def ratio(num, den):
+        return torch.where(den > 0, num.to(torch.float64) / torch.where(den > 0, den.to(torch.float64), one), zero)
+
+    return {"volume_iou": ratio(c[..., 4], c[..., 5]), "volume_recall": ratio(c[..., 4], c[..., 0]),
+            "volume_precision": ratio(c[..., 4], c[..., 2]), "self_overlap_a": ratio(c[..., 1] - c[..., 0], c[..., 1]),
+            "self_overlap_b": ratio(c[..., 3] - c[..., 2], c[..., 3])}

@@ -182,6 +182,9 @@ class PlankModel(nn.Module):
         self.reprojection_tol, self.reprojection_types = check_reprojection(reprojection_tol, reprojection_types)
         if self.sample_select == "reprojection" and num_output_dof != 6:
             raise ValueError("SAMPLE_SELECT 'reprojection' renders planks of six output DOF")
+        # "volume" = the sample whose solid agrees best with the other samples' solids (shape IoU)
+        if self.sample_select == "volume" and num_output_dof != 6:
+            raise ValueError("SAMPLE_SELECT 'volume' compares planks of six output DOF")
         if self.reprojection_types == "match" and num_type < 1:
             raise ValueError("REPROJECTION_TYPES 'match' compares line types: the model has no type embedding (NUM_TYPE 0)")
         # eval_step's plank grammar (decode.plank_grammar()): None = unconstrained, True = the default grammar
@@ -934,8 +937,8 @@ class PlankModel(nn.Module):
     def _check_select(select):
         if select in (None, False, "none", "None", ""):
             return None
-        if select not in ("consensus", "reprojection"):
-            raise ValueError(f"SAMPLE_SELECT must be 'consensus', 'reprojection' or none, got {select!r}")
+        if select not in ("consensus", "reprojection", "volume"):
+            raise ValueError(f"SAMPLE_SELECT must be 'consensus', 'reprojection', 'volume' or none, got {select!r}")
         return select
 
     def eval_step(self, batch, prefix=None, constraint=None, parse=True, share_encoder=None):
@@ -1006,6 +1009,21 @@ class PlankModel(nn.Module):
         tokens = batch["output_value"] if output_value is None else output_value
         tokens = tokens.to(device=self._flat.device, dtype=torch.int64)
         return _reprojection(batch, tokens, pairs=None, **self._reprojection_kw(tol, types))
+
+    def volume(self, batch, output_value=None):
+        """One program per drawing against the drawing's ground truth, as solids (decode.volume_scores):
+        ``output_value`` int [B, n] - of ``eval_step`` or ``sample``; the default is a greedy ``eval_step`` of the batch - is
+        compared by one ``ops.plank_volume`` with ``batch["output_value"]``, the ground-truth rows that ``DevicePlankScorer``
+        takes.  Any input kind.  Returns ``volume_iou`` / ``volume_precision`` / ``volume_recall`` and ``self_overlap`` (of the
+        program) float64 [B] and ``volume_counts`` int64 [B, 8]; nothing is read back."""
+        self._require_gpu()
+        from .decode import volume_scores
+        if self.num_output_dof != 6:
+            raise ValueError("the assembly volume compares planks of six output DOF")
+        tokens = self.eval_step(batch, parse=False)["samples"] if output_value is None else output_value
+        dev = self._flat.device
+        return volume_scores(batch["output_value"].to(device=dev, dtype=torch.int64), tokens.to(device=dev, dtype=torch.int64),
+                             int(self.token.END))
 
     def score(self, batch, tokens=None, attach=None, lengths=None):
         """Log-likelihood of given sequences under the model, on the GPU: the greedy decode step with every position forced
@@ -1139,9 +1157,14 @@ class PlankModel(nn.Module):
         ``reprojection_index`` int64 [B] and ``reprojection_precision`` / ``_recall`` / ``_f1`` float64 [B, N],
         ``reprojection_counts`` int32 [B, N, 8] and ``reprojection_flags`` int32 [B, N]; the rest as under ``consensus``.
 
+        ``select="volume"`` (decode.volume_select): as ``consensus`` with the shape IoU of two samples'
+        solids in place of their plank F1 - graded, so it ranks where no two samples share a plank at IoU > 0.5; any input kind,
+        and it works with ``prefix``, ``constraint`` and ``share_encoder``.  The dict then also has ``volume_index`` int64 [B],
+        ``volume_iou`` float64 [B, N] (each sample's mean IoU with the others) and ``self_overlap`` float64 [B, N].
+
         ``share_encoder`` (None: the model's setting): one encoder pass and one memory per drawing for its N samples (DESIGN.md
         section 25); the draws are those of (seed, b, n, t) either way."""
-        from .decode import SampleDecoder, _pick_reprojection, _reprojection, _reprojection_pairs, consensus_select
+        from .decode import SampleDecoder, _pick_reprojection, _reprojection, _reprojection_pairs, consensus_select, volume_select
         select = self._check_select(select)
         share = self._share(share_encoder)
         key = ("sample", int(num_samples), float(temperature), int(top_k), float(top_p), float(length_penalty)) + self._share_key(share)
@@ -1161,6 +1184,12 @@ class PlankModel(nn.Module):
             pick = _pick_reprojection(_reprojection(batch, st.reshape(B * N, n), pairs=_reprojection_pairs(B, N, st.device), **kw), B, N)
             at = pick["reprojection_index"][:, None, None].expand(-1, 1, n)
             r = dict(r, tokens=st.gather(1, at)[:, 0], attach=r["sample_attach"].gather(1, at)[:, 0])
+        if select == "volume":
+            if self.num_output_dof != 6:
+                raise ValueError("select='volume' compares planks of six output DOF")
+            pick = volume_select(r["sample_tokens"], int(self.token.END))
+            at = pick["volume_index"][:, None, None].expand(-1, 1, r["sample_tokens"].shape[2])
+            r = dict(r, tokens=r["sample_tokens"].gather(1, at)[:, 0], attach=r["sample_attach"].gather(1, at)[:, 0])
         out = self._decode_dict(batch, r, prefix, parse)
         if select is not None:
             out.update(pick)
@@ -1284,8 +1313,8 @@ def build_model(cfg):
     default 1), ``TOP_K`` (>= 0, 0 = off), ``TOP_P`` (in (0, 1], 1 = off) and ``SAMPLE_SEED`` (default 0).  ``CONSTRAIN_PLANKS``
     (bool, default off): eval_step decodes - in whichever mode - under the plank grammar of DESIGN.md section 15, with
     ``MIN_PLANKS`` (default 1) and ``MAX_PLANKS`` (default: the last plank boundary of the decode).  ``SAMPLE_SELECT``
-    (``consensus`` | ``reprojection``; default none): which of the NUM_SAMPLES samples eval_step returns (PlankModel.sample); it
-    needs NUM_SAMPLES >= 1, ``reprojection`` also six output DOF.  ``REPROJECTION_TOL`` (an integer in [0, 255], default 1) and
+    (``consensus`` | ``reprojection`` | ``volume``; default none): which of the NUM_SAMPLES samples eval_step returns
+    (PlankModel.sample); it needs NUM_SAMPLES >= 1, ``reprojection`` and ``volume`` also six output DOF.  ``REPROJECTION_TOL`` (an integer in [0, 255], default 1) and
     ``REPROJECTION_TYPES`` (``ignore`` | ``match`` | ``visible``, default ``ignore``; ``match`` needs NUM_TYPE >= 1): the options of
     the reprojection score.  ``LABEL_SMOOTHING`` (a number in [0, 1), default 0): eps of train_step's label smoothing.  ``SHARE_ENCODER`` (bool, default
     off): beam search, sampling and sequence-level training run one encoder pass and keep one memory per drawing (DESIGN.md section

@@ -685,6 +685,57 @@ def plank_match(seq_a, seq_b, pairs=None, *, end_token, filter_a, filter_b, thre
     return out
 
 
+def plank_volume(seq_a, seq_b=None, pairs=None, *, end_token, check_pairs=True):
+    """Token rows compared as solids - the unions of their planks - one launch for all pairs (pa_plank_volume, csrc/volume.hip;
+    DESIGN.md section 33): the counts behind shape IoU, self-overlap and the volume consensus.
+
+    seq_a [Ra, len_a], seq_b [Rb, len_b]: int64 device tensors as for ``plank_match``; ``seq_b=None``: every b side is empty
+    (the self-overlap-only call; a pair's row of b is then not read).  ``pairs`` / ``check_pairs``: as for ``plank_match``
+    (without ``seq_b`` only the rows of a are range-checked; a 1-D list then names rows of a).  Returns int64 [n, 8] on the device:
+    union_a, sum_a, union_b, sum_b, inter, union_ab, n_a, n_b (include/plank_hip.h); nothing is read back."""
+    sides = (("seq_a", seq_a),) if seq_b is None else (("seq_a", seq_a), ("seq_b", seq_b))
+    for name, t in sides:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 2):
+            raise TypeError(f"{name} must be a 2-D int64 device tensor")
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError(f"{name}: the tokens of a row must be contiguous (stride {t.stride(1)})")
+    if seq_b is not None and seq_b.device != seq_a.device:
+        raise ValueError("seq_a and seq_b must be on the same device")
+    dev = seq_a.device
+    rows_b = seq_a.shape[0] if seq_b is None else seq_b.shape[0]
+    pa = pb = None
+    if pairs is None:
+        if seq_a.shape[0] != rows_b:
+            raise ValueError(f"without pairs both sides need the same number of rows ({seq_a.shape[0]} != {rows_b})")
+        n = seq_a.shape[0]
+    else:
+        p = torch.as_tensor(pairs)
+        if p.numel() == 0 and p.dim() == 1:                   # an empty list: no pairs
+            p = torch.empty(0, 2, dtype=torch.int32)
+        if seq_b is None and p.dim() == 1:                    # rows of a alone
+            p = torch.stack((p, p), 1)
+        if p.dim() != 2 or p.shape[1] != 2 or p.dtype in (torch.bool, torch.float16, torch.bfloat16, torch.float32, torch.float64):
+            raise ValueError("pairs must be an integer [n, 2] tensor")
+        n = p.shape[0]
+        if n and (not p.is_cuda or check_pairs):
+            lo, hi = p.amin(0).tolist(), p.amax(0).tolist()
+            if min(lo) < 0 or hi[0] >= seq_a.shape[0] or (seq_b is not None and hi[1] >= rows_b):
+                raise IndexError(f"pairs name rows outside seq_a ({seq_a.shape[0]} rows) / seq_b ({rows_b} rows)")
+        p = p.to(device=dev, dtype=torch.int32)
+        pa, pb = p[:, 0].contiguous(), p[:, 1].contiguous()
+    out = torch.empty(n, 8, dtype=torch.int64, device=dev)
+    if n == 0:
+        return out
+    sa = seq_a.stride(0) if seq_a.shape[0] > 1 else seq_a.shape[1]
+    sb = lb = 0
+    if seq_b is not None:
+        sb, lb = (seq_b.stride(0) if seq_b.shape[0] > 1 else seq_b.shape[1]), int(seq_b.shape[1])
+    with torch.cuda.device(dev):
+        L.check(L.lib().pa_plank_volume(L.ptr(seq_a), C.c_int64(sa), int(seq_a.shape[1]), L.ptr(seq_b), C.c_int64(sb), lb, L.ptr(pa),
+                                        L.ptr(pb), int(n), int(end_token), 6, L.ptr(out), L.stream()), "pa_plank_volume")
+    return out
+
+
 OVERLAP_MODES = {"ignore": 0, "match": 1, "visible": 2}       # include/plank_hip.h PA_OVERLAP_*
 
 

@@ -95,6 +95,10 @@ class Trainer(torch.nn.Module):
         # their rendered three views match the given drawings (PlankModel.reprojection), on the device
         self.reprojection_metric = reprojection_option(self.hparams_dict, self.device_kind, cfg.DATA.NUM_OUTPUT_DOF)
         self._reprojection_sums = None         # float64 [2] on the device: the sum of F1 and the number of drawings
+        # VOLUME_METRIC: true (opt-in): validation / test also average shape IoU / precision / recall against the ground truth and the
+        # self-overlap of the returned programs (PlankModel.volume), on the device; any input kind
+        self.volume_metric = volume_option(self.hparams_dict, cfg.DATA.NUM_OUTPUT_DOF)
+        self._volume_sums = None               # float64 [5] on the device: the four sums and the number of drawings
 
     # ------------------------------------------------------------------ logging (self.log of Lightning)
     def log(self, name, value, **kw):
@@ -195,16 +199,29 @@ class Trainer(torch.nn.Module):
         sums = torch.stack((f1.sum(), torch.full((), float(f1.numel()), dtype=torch.float64, device=f1.device)))
         self._reprojection_sums = sums if self._reprojection_sums is None else self._reprojection_sums + sums
 
+    VOLUME_KEYS = ("volume_iou", "volume_precision", "volume_recall", "self_overlap")
+
+    def _add_volume(self, batch, samples):
+        """VOLUME_METRIC: the four volume scores of the returned programs join the running sums; nothing is read back."""
+        if not self.volume_metric:
+            return
+        r = self.model.volume(batch, samples)
+        n = r["volume_iou"].numel()
+        sums = torch.stack([r[k].sum() for k in self.VOLUME_KEYS] + [torch.full((), float(n), dtype=torch.float64, device=r["volume_iou"].device)])
+        self._volume_sums = sums if self._volume_sums is None else self._volume_sums + sums
+
     def validation_step(self, batch, batch_idx):
         if self.device_metric:
             outputs = self.model.eval_step(batch, parse=False)
             self.scorer.add_batch(outputs["samples"], batch["output_value"])
             self._add_reprojection(batch, outputs["samples"])
+            self._add_volume(batch, outputs["samples"])
             return
         outputs = self.model(batch)
         for pred, gt in zip(outputs["predicts"], outputs["groundtruths"]):
             self.scorer.add(self._valid_pred(pred), gt)
         self._add_reprojection(batch, outputs["samples"])
+        self._add_volume(batch, outputs["samples"])
 
     def _log_means(self, stage):
         for key, value in zip(("precision", "recall", "fmeasure"), self.scorer.means()):
@@ -213,6 +230,11 @@ class Trainer(torch.nn.Module):
             sums, self._reprojection_sums = self._reprojection_sums, None
             sums = allreduce_metric_sums(torch.zeros(2, dtype=torch.float64) if sums is None else sums.cpu())
             self.log(f"{stage}/reprojection_f1", float(sums[0]) / max(float(sums[1]), 1.0))
+        if self.volume_metric:
+            sums, self._volume_sums = self._volume_sums, None
+            sums = allreduce_metric_sums(torch.zeros(5, dtype=torch.float64) if sums is None else sums.cpu())
+            for i, key in enumerate(self.VOLUME_KEYS):
+                self.log(f"{stage}/{key}", float(sums[i]) / max(float(sums[4]), 1.0))
 
     def validation_epoch_end(self, outputs=None):
         self._log_means("val")
@@ -223,6 +245,7 @@ class Trainer(torch.nn.Module):
         copy per batch: decoded tokens, attach and ground-truth tokens side by side in one tensor."""
         outputs = self.model.eval_step(batch, parse=False)
         self._add_reprojection(batch, outputs["samples"])
+        self._add_volume(batch, outputs["samples"])
         scores = self.scorer.add_batch(outputs["samples"], batch["output_value"], scores=True, keep=keep)
         end = self.cfg.TOKEN.END
         n = outputs["samples"].shape[1]
@@ -243,6 +266,7 @@ class Trainer(torch.nn.Module):
             return
         outputs = self.model(batch)
         self._add_reprojection(batch, outputs["samples"])
+        self._add_volume(batch, outputs["samples"])
         for name, pred, gt, atta in zip(batch["name"], outputs["predicts"], outputs["groundtruths"], outputs["attach"]):
             vp = self._valid_pred(pred)
             scores = self.scorer.add(vp, gt)
@@ -573,6 +597,20 @@ def reprojection_option(hparams, device_kind="line", num_output_dof=6):
         raise ValueError("REPROJECTION_METRIC compares line drawings: the tokens of a sideface input are faces, not lines")
     if v and int(num_output_dof) != 6:
         raise ValueError("REPROJECTION_METRIC renders planks of six output DOF")
+    return v
+
+
+def volume_option(hparams, num_output_dof=6):
+    """``VOLUME_METRIC`` of the hparams, validated -> bool (default False): validation and test also log ``val/`` and ``test/``
+    ``volume_iou`` / ``volume_precision`` / ``volume_recall`` / ``self_overlap``, the means over drawings of the returned programs
+    as solids against their ground truth.  Any input kind; planks of six DOF only."""
+    v = hparams.get("VOLUME_METRIC")
+    if v is None:
+        return False
+    if not isinstance(v, bool):
+        raise ValueError(f"VOLUME_METRIC must be a bool, got {v!r}")
+    if v and int(num_output_dof) != 6:
+        raise ValueError("VOLUME_METRIC compares planks of six output DOF")
     return v
 
 
